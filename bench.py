@@ -6,7 +6,9 @@ itself has no collective (shards are independent streams, round-robin ownership:
 g % world == r, BASELINE.json configs[4]).  A step = one deflate pass over this rank's whole batch of shards, inputs
 resident in HBM before the timed region starts.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Besides the contract fields:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps steps, writes the
+last step's outputs if --dump-outputs DIR is given and prints the headline fields (metric, value, unit, ms_per_step, ratio ...)
+and nothing else.  With --full the line also carries what the legs below measure and check:
   roofline       dominant kernel (lz77), algorithmic bytes / live HIP-event time against 8 TB/s
   roundtrip      configs[1]: EVERY compressed shard of the step inflated back on the device and compared with its input
   inflate        configs[2]: 64 Ki gzip members produced by the CPU oracle (the reference's algorithm, not the GPU deflater),
@@ -260,6 +262,45 @@ def launch_check(world, rank):
     dist.destroy_process_group()
 
 
+def headline(args, world, elapsed, S, B, ratio, checked):
+    """the fields every run prints: the timed steps' rate (all ranks' raw bytes / the slowest rank's time) and what was run"""
+    return {
+        "metric": "GiB/s raw input compressed (level %d, 1 MiB shards)" % args.level,
+        "value": S * B * world * args.steps / GIB / elapsed, "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "config": {"workload": "%d x %d B synthetic Silesia-like shards per GPU, level %d, zlib wrapper; %s" % (S, B, args.level, checked),
+                   "shards_per_gpu": S, "shard_bytes": B, "level": args.level,
+                   "parallelism": "shard-parallel x%d, round-robin ownership (no data-path collective)" % world},
+        "ratio": ratio,
+    }
+
+
+def dump_outputs(d, e, torch, out, olen, st, prefix="", sample=8, budget=48 << 20):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float arrays (so that two builds can be compared output
+    for output; the inputs are the seeded generator's, the same in every run).  Every shard's compressed length, status and the
+    CRC-32 of its compressed stream; the compressed bytes themselves of a fixed, seeded sample of shards (zero past each stream's
+    end), as many whole rows of `out` as fit in `budget` bytes of float32."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    S, stride = int(out.shape[0]), int(out.shape[1])
+    torch.cuda.synchronize()
+    coff = torch.arange(S, dtype=torch.int64, device=out.device) * stride
+    _, crc = e.checksums(out.view(-1), coff, olen, adler=False, crc=True)
+    torch.cuda.synchronize()
+    hl = olen.cpu().numpy().astype(np.int64)
+    k = max(1, min(sample, S, budget // (4 * stride)))
+    cols = min(stride, budget // (4 * k))
+    idx = np.sort(np.random.default_rng(SEED).choice(S, size=k, replace=False))
+    rows = out[torch.from_numpy(idx).to(out.device), :cols].cpu().numpy().astype(np.float32)
+    rows[np.arange(cols)[None, :] >= hl[idx][:, None]] = 0.0
+    arrays = {"out_len": hl.astype(np.float64), "status": st.cpu().numpy().astype(np.float64),
+              "compressed_crc32": crc.cpu().numpy().view(np.uint32).astype(np.float64),
+              "sample_shards": idx.astype(np.float64), "sample_compressed": rows}
+    for name, a in arrays.items():
+        np.save(os.path.join(d, prefix + name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -268,6 +309,11 @@ def main():
     ap.add_argument("--shards", type=int, default=int(os.environ.get("ZMI_BENCH_SHARDS", 65536)), help="shards per GPU")
     ap.add_argument("--shard-bytes", type=int, default=1 << 20)
     ap.add_argument("--level", type=int, default=6)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: device round trip of every shard, host check, stitch, roofline, inflate / levels / "
+                         "PCIe / stream-ABI / real-data legs and the CPU baseline (the options below that name these legs act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed to DIR/<name>.npy (float32 / float64, < 64 MB)")
     ap.add_argument("--verify", type=int, default=64, help="shards additionally checked on the host with the oracle after timing")
     ap.add_argument("--inflate-members", type=int, default=4096,
                     help="distinct gzip members the CPU oracle produces for the inflate leg (tiled on the device to --shards streams)")
@@ -360,6 +406,17 @@ def main():
     stitch_obj = None
     if world > 1:
         dist.all_reduce(csum)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, e, torch, out, olen, st, "" if world == 1 else "rank%d_" % rank)
+    if not args.full:
+        # the plain run: the headline figure and nothing else (every other leg, check and figure is --full)
+        if rank == 0:
+            print(json.dumps(headline(args, world, elapsed, S, B, S * B * world / int(csum.item()),
+                                      "deflate status of every shard checked (the round trips run with --full)")), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        e.close()
+        return
     if not args.no_stitch and world == 1:
         # (no try / except: a stitch that cannot run is a failed run, not a footnote -- the memory plan says why beforehand)
         plan = memory_plan(torch, world, S, B, stride, args.scratch_gib, float(csum.item()) / GIB + 0.1, 0.0)
@@ -650,17 +707,9 @@ def main():
                 break
             except Exception:  # noqa: BLE001
                 continue
-        line = {
-            "metric": "GiB/s raw input compressed (level %d, 1 MiB shards)" % args.level,
-            "value": value, "unit": "GiB/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": "%d x %d B synthetic Silesia-like shards per GPU, level %d, zlib wrapper; all %d compressed shards "
-                                   "inflated back on the device and compared bit-exactly, %d also on the host with the oracle"
-                                   % (S, B, args.level, rt_streams, host_checked),
-                       "shards_per_gpu": S, "shard_bytes": B, "level": args.level,
-                       "parallelism": "shard-parallel x%d, round-robin ownership (no data-path collective)" % world},
-            "ratio": ratio,
+        line = headline(args, world, elapsed, S, B, ratio, "all %d compressed shards inflated back on the device and compared "
+                                                           "bit-exactly, %d also on the host with the oracle" % (rt_streams, host_checked))
+        line.update({
             "roofline": {"bound": "hbm", "kernel": "zmi_lz77_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
                          "read_only_frac": value * GIB / 1e9 / HBM_PEAK_GBS / max(1, world),
@@ -675,7 +724,7 @@ def main():
                                                "per launch group, back to back on the caller's stream"},
                          "launches_per_step": int(launches_per_step)},
             "roundtrip": roundtrip_obj,
-        }
+        })
         if inflate_obj is not None:
             line["inflate"] = inflate_obj
         if levels_obj is not None:

@@ -23,7 +23,7 @@ def main(src, dst, tag):
             rows.setdefault(k, {})[c] = float(v)
             rows[k]["dispatches"] = int(n)
     out = {"_collected": "%s, %s" % (tag, datetime.date.today().isoformat()),
-           "_command": "rocprofv3 --pmc SQ_* -- python bench.py --shards 16384 --steps 1 --warmup 0 --no-cpu --verify 0 --no-extras --no-stitch "
+           "_command": "rocprofv3 --pmc SQ_* -- python bench.py --full --shards 16384 --steps 1 --warmup 0 --no-cpu --verify 0 --no-extras --no-stitch "
                        "(tools/prof_final.sh): deflate kernels = one launch of 16 384 x 1 MiB shards, inflate kernels = the round trip of the "
                        "same 16 384 streams (+ a 64-stream warm-up launch, 0.4 %)",
            "bytes_per_launch": 16384 << 20, "kernels": {}}

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-end evidence collection (run on the GPU box via gpurun, on the SHIPPED commit: no kernel change after it):
 #   gpurun --timeout 2400 -- 'bash tools/prof_final.sh r03'
-# 1. rocprofv3 --kernel-trace --stats of the DEFAULT bench line, extras included (configs[2] inflate, level 1 / 9 sweep, real
+# 1. rocprofv3 --kernel-trace --stats of the --full bench line, extras included (configs[2] inflate, level 1 / 9 sweep, real
 #    data, stream ABI): every kernel gets rows per launch size (grid), so the 64-stream warm-ups do not pollute the averages
 # 2. HBM traffic: separate --pmc passes (FETCH_SIZE, WRITE_SIZE) of one 16 384-shard deflate launch + its round trip
 # 3. SQ counters of the same launch
@@ -12,8 +12,8 @@ export WORLD_SIZE=1 RANK=0 LOCAL_RANK=0
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out; TAG=${1:-r05}
 cd $R
 mkdir -p $O/$TAG/trace $O/$TAG/fetch $O/$TAG/write $O/$TAG/sq
-rocprofv3 --kernel-trace --stats -d $O/$TAG/trace -o t -- python bench.py --steps 2 --warmup 1 --no-cpu --verify 0 > $O/$TAG/trace_bench.json 2> $O/$TAG/trace.log
-SMALL="python bench.py --shards 16384 --steps 1 --warmup 0 --no-cpu --verify 0 --no-extras --no-stitch"
+rocprofv3 --kernel-trace --stats -d $O/$TAG/trace -o t -- python bench.py --full --steps 2 --warmup 1 --no-cpu --verify 0 > $O/$TAG/trace_bench.json 2> $O/$TAG/trace.log
+SMALL="python bench.py --full --shards 16384 --steps 1 --warmup 0 --no-cpu --verify 0 --no-extras --no-stitch"
 rocprofv3 --pmc FETCH_SIZE -d $O/$TAG/fetch -o p -- $SMALL > $O/$TAG/fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE -d $O/$TAG/write -o p -- $SMALL > $O/$TAG/write.log 2>&1
 rocprofv3 --pmc SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY SQ_THREAD_CYCLES_VALU -d $O/$TAG/sq -o p -- $SMALL > $O/$TAG/sq.log 2>&1
@@ -23,13 +23,13 @@ def short(n):
     n = n.split('(')[0].replace('void ', '')
     return n
 con = sqlite3.connect(glob.glob("$O/$TAG/trace/*.db")[0]); cur = con.cursor()
-print("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 2 --warmup 1 --no-cpu --verify 0   (the default bench line incl. its extras;")
+print("# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 2 --warmup 1 --no-cpu --verify 0   (the --full bench line incl. its extras;")
 print("# rows per kernel AND launch size: grid = workgroups; deflate launch group = 16384 shards = 16 GiB raw; inflate launches of 16384 / 4096 / 3 / 64 streams)")
 print("kernel,grid_workgroups,calls,total_us,avg_us")
 rows = cur.execute("select name, grid_x / workgroup_x, count(*), sum(duration), avg(duration) from kernels where name like '%zmi_%' group by name, grid_x / workgroup_x order by sum(duration) desc").fetchall()
 for r in rows:
     print('%s,%d,%d,%.1f,%.1f' % (short(r[0]), r[1], r[2], r[3] / 1e3, r[4] / 1e3))
-print("# PMC passes: python bench.py --shards 16384 --steps 1 --warmup 0 --no-extras --no-stitch (one launch of each deflate kernel = 16384 shards = 16 GiB raw;")
+print("# PMC passes: python bench.py --full --shards 16384 --steps 1 --warmup 0 --no-extras --no-stitch (one launch of each deflate kernel = 16384 shards = 16 GiB raw;")
 print("# inflate kernels: the round trip, one 16384-stream launch + a 64-stream warm-up)")
 print("kernel,counter,sum_over_dispatches,dispatches")
 traffic = {}

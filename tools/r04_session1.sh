@@ -21,4 +21,4 @@ ZMI_LIB=variants/libzmi355_noopt.so python tools/gpu_fast_probe.py --shards 1638
 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1; echo "smoke rc=$?"
 timeout 1500 python -m pytest tests -m gpu -q -x > "$O/pytest_gpu.log" 2>&1; echo "pytest rc=$?"; tail -5 "$O/pytest_gpu.log"
 # 3. the bench through its own launcher (small)
-timeout 600 python bench.py --gpus 1 --shards 4096 --steps 1 --warmup 1 --no-extras --no-cpu --scratch-gib 18 > "$O/bench_small.json" 2> "$O/bench_small.err"; echo "bench rc=$?"; cut -c1-600 "$O/bench_small.json"
+timeout 600 python bench.py --full --gpus 1 --shards 4096 --steps 1 --warmup 1 --no-extras --no-cpu --scratch-gib 18 > "$O/bench_small.json" 2> "$O/bench_small.err"; echo "bench rc=$?"; cut -c1-600 "$O/bench_small.json"

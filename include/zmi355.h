@@ -233,6 +233,61 @@ int zmi_exchange_slabs(zmi_comm* comm, const void* d_slab, const uint64_t* slab_
 int zmi_exchange_slabs_round(zmi_comm* comm, const void* d_slab, const uint64_t* slab_bytes, uint64_t lo,
                              uint64_t chunk_bytes, void* const* d_stage, int root, void* stream);
 
+/* ---- single-stream deflate (pigz-style): one complete raw / zlib / gzip stream from a device buffer ---------------------
+ * The reference's parallel-deflate recipe, zlib-rs/src/deflate.rs:4145-4221 (split_deflate): the input is cut into pieces of
+ * piece_bytes; every piece but the last ends with the empty stored block of a flush (00 00 00 FF FF after the bits of the block
+ * in front: Z_SYNC_FLUSH, deflate.rs:2733-2738), the wrapper appears once, and the trailer carries the check value of the whole
+ * input, combined on the device from the pieces' Adler-32 / CRC-32 (crc32/combine.rs:3-13, adler32.rs:58).  The header bytes are
+ * those of deflateInit2_(level, Z_DEFLATED, 15 / 31, 8, strategy) + deflate() (no deflateSetHeader: MTIME 0, OS 3).
+ *
+ * zmi_deflate_stream_dev   d_in[0 .. n) -> d_out (out_cap bytes; zmi_deflate_stream_bound(n, piece_bytes, wrap) always
+ *                          suffices).  Asynchronous on `stream`, no host synchronisation inside.  Device words written:
+ *                          *d_out_len = stream length, *d_status = 0, or the zlib code of the first piece that failed, or
+ *                          Z_BUF_ERROR (-5) when the stream does not fit out_cap (*d_out_len then tells the size it needs).
+ *                          d_piece_off (NULL or n_pieces + 1 entries): byte offset in d_out of every piece's first deflate byte,
+ *                          then the end of the deflate data.  Every piece starts behind a flush marker, so these minus the header
+ *                          length are restart points for zmi_inflate_split's seg_start.  n_pieces = ceil(n / piece_bytes), 1 for
+ *                          n = 0 (header, 03 00, trailer).  piece_bytes 1 .. 2^30 (ZMI_E_ARG otherwise).
+ *   flags 0                      carry-over: every piece matches into the up to 27 KiB in front of it (Z_SYNC_FLUSH);
+ *         ZMI_STREAM_INDEPENDENT pieces forget history (Z_FULL_FLUSH): [off[i], off[i+1]) inflates alone (raw) to piece i.
+ *   Determinism: the bytes are a function of (input, n, piece_bytes, level, strategy, wrap, flags) alone -- not of the scratch
+ *   limit or of how the call is cut into launch groups.  In independent mode a piece's deflate bytes depend only on its own bytes,
+ *   the piece size min(piece_bytes, n), level, strategy and whether it is the last one: the multi-GPU form below, run with the same
+ *   max_len, is byte-identical to one call on the whole input.
+ *
+ * The per-rank building blocks of the same stream across the GPUs of a node (round-robin pieces, as the stitch above):
+ *   zmi_deflate_pieces_dev   a batch of pieces: d_out_len[i] / d_check[i] (Adler-32 for zlib, CRC-32 for gzip, of the raw bytes;
+ *                            unused for raw) / d_status[i]; pieces at d_out + i * out_stride, out_stride >=
+ *                            zmi_deflate_pieces_stride(max_len).  final_piece != 0: the batch's last piece ends the stream (BFINAL);
+ *                            every other piece ends with the flush marker.  Carry mode needs the contiguous layout (the bytes in front
+ *                            of a piece in d_in are its history); ZMI_STREAM_INDEPENDENT takes any layout.  For the bytes of
+ *                            zmi_deflate_stream_dev pass max_len = min(piece_bytes, total n).
+ *   zmi_checksum_combine_dev (check, raw length) pairs -> the check of the concatenation (*d_out_check) and the total length
+ *                            (*d_out_len; either may be NULL), wrap zlib (Adler-32) or gzip (CRC-32).  Entry r * n_local + j is
+ *                            piece j * world + r (the layout of zmi_exchange_sizes' tables; world 1 = plain order); entries of
+ *                            length 0 count as nothing, whatever their check holds.
+ *   zmi_stream_frame_dev     header at d_out[0 .. zmi_stream_header_bytes(wrap)), trailer behind the *d_payload_len bytes of deflate
+ *                            data the caller packed at d_out + header (zmi_copy_ranges_dev into d_out + header), *d_out_len = total;
+ *                            d_status (may be NULL) as above.
+ *   A rank: pieces, zmi_pack_slab_dev, zmi_exchange_sizes of the sizes and of the checks (and of the raw lengths when the pieces are
+ *   uneven), zmi_stitch_plan_dev, the slab exchange, zmi_copy_ranges_dev into d_out + header, combine, frame (payload length =
+ *   d_totals[world] of the plan). */
+#define ZMI_STREAM_INDEPENDENT 1u
+uint64_t zmi_deflate_stream_bound(uint64_t n, uint32_t piece_bytes, int wrap);
+uint32_t zmi_stream_header_bytes(int wrap);
+uint64_t zmi_deflate_pieces_stride(uint32_t max_len);
+int zmi_deflate_stream_dev(zmi_ctx* ctx, const void* d_in, uint64_t n, uint32_t piece_bytes, int level, int strategy, int wrap,
+                           uint32_t flags, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_piece_off,
+                           int32_t* d_status, void* stream);
+int zmi_deflate_pieces_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_pieces,
+                           uint32_t max_len, int level, int strategy, int wrap, uint32_t flags, int final_piece, void* d_out,
+                           uint64_t out_stride, uint32_t* d_out_len, uint32_t* d_check, int32_t* d_status, void* stream);
+int zmi_checksum_combine_dev(zmi_ctx* ctx, int wrap, const uint32_t* d_check, const uint32_t* d_len, uint32_t world, uint32_t n_local,
+                             uint32_t* d_out_check, uint64_t* d_out_len, void* stream);
+int zmi_stream_frame_dev(zmi_ctx* ctx, int wrap, int level, int strategy, const uint64_t* d_payload_len, const uint32_t* d_check,
+                         const uint64_t* d_raw_len, void* d_out, uint64_t out_cap, uint64_t* d_out_len, int32_t* d_status,
+                         void* stream);
+
 /* ---- host-buffer convenience wrappers: copy in, run the batch on the GPU, copy back ---- */
 int zmi_deflate_batch(zmi_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_shards,
                       int level, int strategy, int wrap, uint8_t* out, uint64_t out_stride, uint32_t* out_len,

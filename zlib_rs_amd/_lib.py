@@ -35,6 +35,17 @@ def lib():
     L.zmi_pack_slab_dev.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp]
     L.zmi_deflate_batch.argtypes = [vp, vp, vp, vp, u32, i32, i32, i32, vp, u64, vp, vp]
     L.zmi_inflate_batch.argtypes = [vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp]
+    # single-stream deflate (csrc/zmi_api.hip, checksum.hip, pack.hip)
+    L.zmi_deflate_stream_bound.restype = u64
+    L.zmi_deflate_stream_bound.argtypes = [u64, u32, i32]
+    L.zmi_stream_header_bytes.restype = u32
+    L.zmi_stream_header_bytes.argtypes = [i32]
+    L.zmi_deflate_pieces_stride.restype = u64
+    L.zmi_deflate_pieces_stride.argtypes = [u32]
+    L.zmi_deflate_stream_dev.argtypes = [vp, vp, u64, u32, i32, i32, i32, u32, vp, u64, vp, vp, vp, vp]
+    L.zmi_deflate_pieces_dev.argtypes = [vp, vp, vp, vp, u32, u32, i32, i32, i32, u32, i32, vp, u64, vp, vp, vp, vp]
+    L.zmi_checksum_combine_dev.argtypes = [vp, i32, vp, vp, u32, u32, vp, vp, vp]
+    L.zmi_stream_frame_dev.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, u64, vp, vp, vp]
     # the multi-GPU stitch (csrc/exchange.hip); RCCL itself is loaded by the library on first use
     L.zmi_comm_unique_id.argtypes = [vp]
     L.zmi_comm_create.argtypes = [C.POINTER(vp), vp, i32, i32, vp]

@@ -247,3 +247,119 @@ extern "C" int zmi_launch_checksum(const uint8_t* d_data, const uint64_t* d_off,
     ZMI_LAUNCH(zmi_checksum_kernel, dim3(n_shards), dim3(256), 0, stream, d_data, d_off, d_len, kind, d_adler, d_crc);
     return 0;
 }
+
+// ---- checksum combine: the check value of a concatenation from the pieces' (check, raw length) pairs -----------------------
+// The reference stitches the trailer of its parallel-deflate recipe serially: crc32_combine (crc32/combine.rs:3-13) and
+// adler32_combine (adler32.rs:58), one call per piece.  Both are associative operators on (check, length) pairs:
+//   CRC-32:   (c1, l1) o (c2, l2) = (c1 * x^(8 * l2) mod P  xor  c2,  l1 + l2)
+//   Adler-32: (a1, l1) o (a2, l2) = (adler32_combine(a1, a2, l2 mod 65521),  l1 + l2)
+// so the device reduces them in a tree: every lane folds a run of consecutive entries, the wave folds its 64 lanes in order
+// with an xor butterfly (the lower partner combines mine o theirs, the upper theirs o mine), wave 0 folds the four wave results,
+// and a second launch folds the per-workgroup results when there were several.  x^(8 * l) is the product of x^(8 * 2^k) over the
+// set bits of l (a table of 64 powers, built at compile time): one multiplication per piece for power-of-two piece sizes.
+// An entry of length 0 is the identity whatever its check field holds (the multi-GPU tables are padded with zeros).
+#define ZMI_COMBINE_T 256u
+#define ZMI_COMBINE_PER_LANE 16u
+struct zmi_xpow_tab { uint32_t v[64]; };
+constexpr zmi_xpow_tab zmi_cx_xpow_tab() {
+    zmi_xpow_tab t{};
+    uint32_t p = 0x00800000u;   // x^8
+    for (int k = 0; k < 64; ++k) { t.v[k] = p; p = zmi_cx_mulmod(p, p); }
+    return t;
+}
+constexpr zmi_xpow_tab kXpowTab = zmi_cx_xpow_tab();
+
+static __device__ __forceinline__ uint32_t zmi_adler_combine_dev(uint32_t a1, uint32_t a2, uint64_t len2) {
+    const uint32_t rem = (uint32_t)(len2 % ZMI_ADLER_BASE);
+    uint32_t s1 = a1 & 0xFFFFu;
+    uint32_t s2 = (uint32_t)(((uint64_t)rem * s1) % ZMI_ADLER_BASE);
+    s1 += (a2 & 0xFFFFu) + ZMI_ADLER_BASE - 1u;
+    s2 += ((a1 >> 16) & 0xFFFFu) + ((a2 >> 16) & 0xFFFFu) + ZMI_ADLER_BASE - rem;
+    if (s1 >= ZMI_ADLER_BASE) s1 -= ZMI_ADLER_BASE;
+    if (s1 >= ZMI_ADLER_BASE) s1 -= ZMI_ADLER_BASE;
+    if (s2 >= 2u * ZMI_ADLER_BASE) s2 -= 2u * ZMI_ADLER_BASE;
+    if (s2 >= ZMI_ADLER_BASE) s2 -= ZMI_ADLER_BASE;
+    return (s2 << 16) | s1;
+}
+// (c1, l1) o (c2, l2) in place of (c1, l1); pw = the x^(8 * 2^k) table
+static __device__ __forceinline__ void zmi_combine_pair(bool adler, const uint32_t* pw, uint32_t& c1, uint64_t& l1, uint32_t c2,
+                                                        uint64_t l2) {
+    if (l2 == 0) return;
+    if (l1 == 0) { c1 = c2; l1 = l2; return; }
+    if (adler) {
+        c1 = zmi_adler_combine_dev(c1, c2, l2);
+    } else {
+        for (uint64_t b = l2; b; b &= b - 1u) c1 = zmi_gf2_mulmod(c1, pw[__builtin_ctzll(b)]);
+        c1 ^= c2;
+    }
+    l1 += l2;
+}
+
+// One workgroup folds the logical entries [blockIdx.x * per_block, + per_block) of n.  Logical entry g is table entry
+// (g % world) * n_local + g / world (the rank-major all-gathered tables; world 1 = plain order).  Lengths come from len32
+// (the tables) or, in the second pass over the workgroups' results, from len64.  out_check / out_len[blockIdx.x] = the fold.
+__global__ void __launch_bounds__(ZMI_COMBINE_T) zmi_combine_kernel(const uint32_t* __restrict__ check, const uint32_t* __restrict__ len32,
+                                                                   const uint64_t* __restrict__ len64, uint32_t n, uint32_t world,
+                                                                   uint32_t n_local, uint32_t per_block, uint32_t adler,
+                                                                   uint32_t* __restrict__ out_check, uint64_t* __restrict__ out_len) {
+    __shared__ uint32_t pw[64];
+    __shared__ uint32_t wc[ZMI_COMBINE_T / 64u];
+    __shared__ uint64_t wl[ZMI_COMBINE_T / 64u];
+    const uint32_t t = threadIdx.x;
+    if (t < 64u) pw[t] = kXpowTab.v[t];
+    __syncthreads();
+    const bool ad = adler != 0u;
+    const uint64_t b0 = (uint64_t)blockIdx.x * per_block;
+    const uint64_t b1 = b0 + per_block < n ? b0 + per_block : n;
+    const uint32_t per_lane = (per_block + ZMI_COMBINE_T - 1u) / ZMI_COMBINE_T;
+    uint32_t c = ad ? 1u : 0u;
+    uint64_t l = 0;
+    for (uint64_t g = b0 + (uint64_t)t * per_lane, ge = g + per_lane; g < ge && g < b1; ++g) {
+        const uint64_t idx = world == 1u ? g : (g % world) * n_local + g / world;
+        zmi_combine_pair(ad, pw, c, l, check[idx], len64 ? len64[idx] : (uint64_t)len32[idx]);
+    }
+    // ordered butterfly: after step d every lane holds the fold of its aligned run of 2d lanes
+    const uint32_t lane = zmi_lane();
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint32_t oc = __shfl_xor(c, (int)d);
+        const uint32_t olo = __shfl_xor((uint32_t)l, (int)d), ohi = __shfl_xor((uint32_t)(l >> 32), (int)d);
+        const uint64_t ol = ((uint64_t)ohi << 32) | olo;
+        if (lane & d) {
+            uint32_t c2 = oc;
+            uint64_t l2 = ol;
+            zmi_combine_pair(ad, pw, c2, l2, c, l);
+            c = c2;
+            l = l2;
+        } else {
+            zmi_combine_pair(ad, pw, c, l, oc, ol);
+        }
+    }
+    if (lane == 0) { wc[zmi_wave()] = c; wl[zmi_wave()] = l; }
+    __syncthreads();
+    if (t == 0) {
+        for (uint32_t w = 1; w < ZMI_COMBINE_T / 64u; ++w) zmi_combine_pair(ad, pw, c, l, wc[w], wl[w]);
+        out_check[blockIdx.x] = c;
+        out_len[blockIdx.x] = l;
+    }
+}
+
+// d_partial: room for zmi_combine_partials(n) check words and as many u64 lengths (NULL when that is 1)
+extern "C" uint32_t zmi_combine_partials(uint32_t n) {
+    const uint32_t per_block = ZMI_COMBINE_T * ZMI_COMBINE_PER_LANE;
+    return n <= per_block ? 1u : (uint32_t)(((uint64_t)n + per_block - 1u) / per_block);
+}
+extern "C" int zmi_launch_checksum_combine(const uint32_t* d_check, const uint32_t* d_len, uint32_t n, uint32_t world, uint32_t n_local,
+                                           uint32_t adler, uint32_t* d_pc, uint64_t* d_pl, uint32_t* d_out_check, uint64_t* d_out_len,
+                                           hipStream_t stream) {
+    const uint32_t nb = zmi_combine_partials(n);
+    if (nb == 1u) {
+        ZMI_LAUNCH(zmi_combine_kernel, dim3(1), dim3(ZMI_COMBINE_T), 0, stream, d_check, d_len, (const uint64_t*)nullptr, n, world, n_local,
+                   n, adler, d_out_check, d_out_len);
+        return 0;
+    }
+    ZMI_LAUNCH(zmi_combine_kernel, dim3(nb), dim3(ZMI_COMBINE_T), 0, stream, d_check, d_len, (const uint64_t*)nullptr, n, world, n_local,
+               ZMI_COMBINE_T * ZMI_COMBINE_PER_LANE, adler, d_pc, d_pl);
+    ZMI_LAUNCH(zmi_combine_kernel, dim3(1), dim3(ZMI_COMBINE_T), 0, stream, (const uint32_t*)d_pc, (const uint32_t*)nullptr,
+               (const uint64_t*)d_pl, nb, 1u, nb, nb, adler, d_out_check, d_out_len);
+    return 0;
+}

@@ -18,10 +18,13 @@
 #define PK_T 256u
 #define PK_TILE 4096u
 
+// base (may be NULL): a device word the offsets start from -- the end of the previous launch group of a single stream
+// (zmi_deflate_stream_dev), read before anything is written, so it may be off[0] itself
 __global__ void __launch_bounds__(1024) zmi_scan_sizes_kernel(const uint32_t* __restrict__ len, uint32_t n,
-                                                               uint64_t* __restrict__ off) {
+                                                               uint64_t* off, const uint64_t* base) {
     __shared__ uint64_t part[1024];
     const uint32_t t = threadIdx.x;
+    const uint64_t b = base ? *base : 0ull;
     const uint32_t per = (n + 1023u) / 1024u;
     const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
     uint64_t sum = 0;
@@ -34,9 +37,9 @@ __global__ void __launch_bounds__(1024) zmi_scan_sizes_kernel(const uint32_t* __
         part[t] += v;
         __syncthreads();
     }
-    uint64_t o = part[t] - sum;
+    uint64_t o = b + part[t] - sum;
     for (uint32_t i = lo; i < hi; ++i) { off[i] = o; o += len[i]; }
-    if (t == 1023u) off[n] = part[1023];
+    if (t == 1023u) off[n] = b + part[1023];
 }
 
 // n * split jobs: job b handles tiles b % split, b % split + split, ... of range b / split; the grid is the number of jobs, or
@@ -101,7 +104,11 @@ extern "C" int zmi_launch_clamp_lens(const uint32_t* d_len, const uint32_t* d_ca
 }
 
 extern "C" int zmi_launch_scan_sizes(const uint32_t* d_len, uint32_t n, uint64_t* d_off, hipStream_t stream) {
-    ZMI_LAUNCH(zmi_scan_sizes_kernel, dim3(1), dim3(1024), 0, stream, d_len, n, d_off);
+    ZMI_LAUNCH(zmi_scan_sizes_kernel, dim3(1), dim3(1024), 0, stream, d_len, n, d_off, (const uint64_t*)nullptr);
+    return 0;
+}
+extern "C" int zmi_launch_scan_sizes_base(const uint32_t* d_len, uint32_t n, uint64_t* d_off, const uint64_t* d_base, hipStream_t stream) {
+    ZMI_LAUNCH(zmi_scan_sizes_kernel, dim3(1), dim3(1024), 0, stream, d_len, n, d_off, d_base);
     return 0;
 }
 
@@ -137,5 +144,97 @@ extern "C" int zmi_launch_copy_ranges_few(const uint8_t* d_src, const uint64_t* 
     const uint32_t jobs = jobs64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)jobs64;
     ZMI_LAUNCH(zmi_copy_ranges_kernel, dim3(jobs < groups ? jobs : groups), dim3(PK_T), 0, stream, d_src, d_src_off, src_stride, d_len, d_dst,
                d_dst_off, dst_cap, split, jobs);
+    return 0;
+}
+
+// ---- the single stream (zmi_deflate_stream_dev, zmi_stream_frame_dev) -------------------------------------------------------
+// The reference's split_deflate (zlib-rs/src/deflate.rs:4145-4221) writes the wrapper once, every piece but the last behind a
+// flush marker, and one trailer with the combined check value.  The pieces' deflate bytes are packed by the copy kernel above at
+// d_out + h; these kernels lay the pieces out and write what surrounds them.
+
+// piece i of an n-byte buffer: [i * piece_bytes, + min(piece_bytes, n - i * piece_bytes)); n = 0 is one empty piece
+__global__ void __launch_bounds__(256) zmi_piece_layout_kernel(uint64_t n, uint32_t piece_bytes, uint32_t count, uint64_t* __restrict__ off,
+                                                               uint32_t* __restrict__ len) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t o = (uint64_t)i * piece_bytes;
+    off[i] = o;
+    len[i] = n - o < piece_bytes ? (uint32_t)(n - o) : piece_bytes;
+}
+extern "C" int zmi_launch_piece_layout(uint64_t n, uint32_t piece_bytes, uint32_t count, uint64_t* d_off, uint32_t* d_len, hipStream_t stream) {
+    if (count == 0) return 0;
+    ZMI_LAUNCH(zmi_piece_layout_kernel, dim3((count + 255u) / 256u), dim3(256), 0, stream, n, piece_bytes, count, d_off, d_len);
+    return 0;
+}
+
+// header bytes of deflateInit2_(level, Z_DEFLATED, 15 / 31, 8, strategy) + deflate() without deflateSetHeader (zlib_abi.hip
+// put_header; deflate.rs:1572-1601, 2574-2700): zlib CMF 0x78, FLEVEL from level and strategy, FCHECK; gzip magic, CM 8, no flags,
+// MTIME 0, XFL, OS 3.  Returns h.
+static __device__ __forceinline__ uint32_t zmi_stream_header(uint32_t wrap, uint32_t level, uint32_t strategy, uint8_t* hb) {
+    if (wrap == 1u) {
+        const uint32_t lf = (strategy >= 2u || level < 2u) ? 0u : (level < 6u ? 1u : (level == 6u ? 2u : 3u));
+        uint32_t h = (0x78u << 8) | (lf << 6);
+        h += 31u - (h % 31u);
+        hb[0] = (uint8_t)(h >> 8);
+        hb[1] = (uint8_t)h;
+        return 2u;
+    }
+    if (wrap == 2u) {
+        const uint8_t g[10] = {0x1F, 0x8B, 8, 0, 0, 0, 0, 0, (uint8_t)(level == 9u ? 2u : ((strategy >= 2u || level < 2u) ? 4u : 0u)), 3};
+        for (int i = 0; i < 10; ++i) hb[i] = g[i];
+        return 10u;
+    }
+    return 0u;
+}
+
+// Block 0, thread 0: header at out[0..h), trailer behind out[h + *payload] (Adler-32 big-endian / CRC-32 and ISIZE little-endian),
+// *out_len = h + payload + trailer.  A stream that does not fit out_cap gets no trailer and status Z_BUF_ERROR (*out_len still
+// tells the size it needs).  Every thread of the grid: index[i] += h (piece offsets relative to the payload -> offsets in out) and
+// the first non-zero piece status lands in *status (which the caller zeroed).  The last index entry, the end of the deflate data,
+// is written by thread 0 alone: it may be the payload word itself (zmi_deflate_stream_dev scans into the caller's index), and a
+// workgroup that shifted it before thread 0 read it would move the trailer.
+__global__ void __launch_bounds__(256) zmi_frame_kernel(uint8_t* __restrict__ out, uint64_t out_cap, uint32_t wrap, uint32_t level,
+                                                        uint32_t strategy, const uint64_t* payload,
+                                                        const uint32_t* __restrict__ check, const uint64_t* __restrict__ raw_len,
+                                                        uint64_t* __restrict__ out_len, int32_t* status, const int32_t* __restrict__ piece_st,
+                                                        uint32_t n_st, uint64_t* index, uint32_t n_index) {
+    uint8_t hb[10];
+    const uint32_t h = zmi_stream_header(wrap, level, strategy, hb);
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint64_t g0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (uint64_t i = g0; i + 1u < n_index; i += stride) index[i] += h;
+    if (status)
+        for (uint64_t i = g0; i < n_st; i += stride)
+            if (piece_st[i] != 0) atomicCAS(status, 0, piece_st[i]);
+    if (g0 != 0) return;
+    const uint64_t pl = *payload;
+    if (n_index) index[n_index - 1u] = h + pl;
+    const uint32_t tl = wrap == 1u ? 4u : (wrap == 2u ? 8u : 0u);
+    const uint64_t total = h + pl + tl;
+    *out_len = total;
+    if (total > out_cap) {
+        if (status) atomicCAS(status, 0, ZMI_BUF_ERROR);
+        return;
+    }
+    for (uint32_t i = 0; i < h; ++i) out[i] = hb[i];
+    uint8_t* tr = out + h + pl;
+    const uint32_t c = check ? *check : 0u;
+    if (wrap == 1u) {
+        for (int i = 0; i < 4; ++i) tr[i] = (uint8_t)(c >> (24 - 8 * i));
+    } else if (wrap == 2u) {
+        const uint32_t isz = (uint32_t)*raw_len;
+        for (int i = 0; i < 4; ++i) { tr[i] = (uint8_t)(c >> (8 * i)); tr[4 + i] = (uint8_t)(isz >> (8 * i)); }
+    }
+}
+extern "C" uint32_t zmi_stream_header_len(int wrap) { return wrap == 1 ? 2u : (wrap == 2 ? 10u : 0u); }
+extern "C" int zmi_launch_frame(uint8_t* d_out, uint64_t out_cap, uint32_t wrap, uint32_t level, uint32_t strategy, const uint64_t* d_payload,
+                                const uint32_t* d_check, const uint64_t* d_raw_len, uint64_t* d_out_len, int32_t* d_status,
+                                const int32_t* d_piece_st, uint32_t n_st, uint64_t* d_index, uint32_t n_index, hipStream_t stream) {
+    const uint32_t work = n_st > n_index ? n_st : n_index;
+    uint32_t blocks = (work + 255u) / 256u;
+    if (blocks < 1u) blocks = 1u;
+    if (blocks > 1024u) blocks = 1024u;
+    ZMI_LAUNCH(zmi_frame_kernel, dim3(blocks), dim3(256), 0, stream, d_out, out_cap, wrap, level, strategy, d_payload, d_check, d_raw_len,
+               d_out_len, d_status, d_piece_st, n_st, d_index, n_index);
     return 0;
 }

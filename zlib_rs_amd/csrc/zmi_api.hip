@@ -102,6 +102,8 @@ struct zmi_ctx {
     hipStream_t host_stream = nullptr;  // zmi_ctx_set_stream: where the host-buffer wrappers copy and launch
     hipStream_t side = nullptr;         // deflate: the wrapper checksums run here, beside the match search (zmi_deflate_impl)
     hipEvent_t ev_fork{}, ev_join{};
+    zmi_buf sd_meta, sd_slots;          // zmi_deflate_stream_dev: per-piece tables / one launch group's output slots
+    zmi_buf comb;                       // zmi_checksum_combine_dev: the per-workgroup partial folds
 };
 
 static int zmi_reserve(zmi_buf& b, size_t bytes) {
@@ -150,6 +152,9 @@ extern "C" int zmi_ctx_destroy(zmi_ctx* c) {
     if (c->side) { (void)hipStreamDestroy(c->side); (void)hipEventDestroy(c->ev_fork); (void)hipEventDestroy(c->ev_join); }
     if (c->sp_out.p) (void)hipFree(c->sp_out.p);
     if (c->st_scan.p) (void)hipFree(c->st_scan.p);
+    if (c->sd_meta.p) (void)hipFree(c->sd_meta.p);
+    if (c->sd_slots.p) (void)hipFree(c->sd_slots.p);
+    if (c->comb.p) (void)hipFree(c->comb.p);
     for (int k = 0; k < 2; ++k) if (c->st_pin[k].p) (void)hipHostFree(c->st_pin[k].p);
     if (c->st_pin_ev_live) { (void)hipEventDestroy(c->st_pin_ev[0]); (void)hipEventDestroy(c->st_pin_ev[1]); }
     if (c->hb_live) {
@@ -355,10 +360,13 @@ extern "C" int zmi_pack_slab_dev(zmi_ctx* c, const void* d_slots, uint64_t slot_
     return zmi_copy_ranges_dev(c, d_slots, nullptr, slot_stride, d_len, n, max_len, d_slab, d_off, slab_cap, stream);
 }
 
+// carry: -1 = what chain_mode implies, 0 = segments forget history (independent pieces of one stream), 1 = window carry-over.
+// launch_n: the number of segments the small-launch rule below judges (0: n) -- the whole stream's when a stream is compressed in
+// several launch groups, so that the bytes do not depend on the grouping.
 static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
                             uint32_t max_len, int level, int strategy, int wrap, uint32_t chain_mode, uint32_t dict_len,
                             uint32_t window_bits, void* d_out, uint64_t out_stride, uint32_t* d_out_len, int32_t* d_status,
-                            void* stream_);
+                            void* stream_, int carry = -1, uint64_t launch_n = 0);
 
 extern "C" int zmi_deflate_batch_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
                                      uint32_t n, uint32_t max_len, int level, int strategy, int wrap, void* d_out,
@@ -404,7 +412,7 @@ extern "C" int zmi_deflate_chain_window_dev(zmi_ctx* c, const void* d_in, const 
 static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
                             uint32_t max_len, int level, int strategy, int wrap, uint32_t chain_mode, uint32_t dict_len,
                             uint32_t window_bits, void* d_out, uint64_t out_stride, uint32_t* d_out_len, int32_t* d_status,
-                            void* stream_) {
+                            void* stream_, int carry, uint64_t launch_n) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (level == -1) level = 6;
     if (level < 0 || level > 9) return zmi_fail(ZMI_E_ARG, "level must be -1..9");
@@ -491,6 +499,7 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     lp.carry = chain_mode != 0u ? 1u : 0u;   // segments of one stream: a segment sees the window in front of it
     lp.dict_len = chain_mode != 0u ? dict_len : 0u;
     if (const char* cv = zmi_tune("ZMI_CARRY")) lp.carry = (chain_mode != 0u && atoi(cv)) ? 1u : 0u;
+    if (carry >= 0) lp.carry = (chain_mode != 0u && carry) ? 1u : 0u;
     // hash-building waves: 1 for the deep chains (the searchers are the whole kernel there), 2 for the short ones (14 searcher
     // waves outrun one producer: budget 5 measured 227 ms with two, 273 ms with one), 3 at level 1, whose searchers do so
     // little per position that even two producers set the pace (97.1 -> 95.2 ms per 16 Ki shards; at level 3 a third
@@ -525,7 +534,9 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     // 2.3076 with 4 KiB)
     // (only for the segments of ONE stream -- chain mode: what a batch of independent shards compresses to does not depend on how
     // many of them a launch holds, tests/test_gpu_parity.py::test_host_batch_pipeline_on_gpu)
-    const bool small_launch = chain_mode != 0u && (uint64_t)n * ((max_len + 65535u) / 65536u) < 512u;
+    // (independent pieces of a single stream, carry 0, never: a piece's bytes depend on its own input alone, whichever GPU and
+    // whichever launch compresses it -- zmi_deflate_stream_dev)
+    const bool small_launch = chain_mode != 0u && carry != 0 && (launch_n ? launch_n : n) * ((max_len + 65535u) / 65536u) < 512u;
     if (small_launch) ep.block_span = 8192u;
     const char* span_env = zmi_tune("ZMI_BLOCK_SPAN");
     if (span_env && atoi(span_env) >= 64) ep.block_span = (uint32_t)atoi(span_env);
@@ -579,6 +590,178 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
         zmi_launch_encode((const uint8_t*)d_in, d_in_off, d_in_len, (uint32_t)first, cnt, (uint32_t*)c->match.p,
                           per_shard / 4u, d_adler, d_crc, (uint8_t*)d_out, out_stride, (uint32_t)out_stride, d_out_len,
                           d_status, pieces, (uint32_t*)c->pieces.p, d_dec, dec_bytes / 4u, ep, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+// ---- single-stream deflate (pigz-style): one raw / zlib / gzip stream from many pieces -----------------------------------------
+// The reference's parallel-deflate recipe, zlib-rs/src/deflate.rs:4145-4221 (split_deflate): every piece but the last ends with
+// the empty stored block of a flush (Z_SYNC_FLUSH, deflate.rs:2733-2738; Z_FULL_FLUSH also forgets history, :2739-2752), the
+// wrapper appears once, and the trailer carries the combined check value (crc32/combine.rs:3-13, adler32.rs:58).  Here the pieces
+// are the segments of the chained encoder, the checks are combined by a reduction on the device (checksum.hip) and the frame is
+// written by a kernel (pack.hip): no host round trip anywhere.
+extern "C" uint64_t zmi_deflate_pieces_stride(uint32_t max_len) { return zmi_deflate_bound(max_len, ZMI_WRAP_RAW) + 16u; }
+extern "C" uint32_t zmi_stream_header_bytes(int wrap) { return zmi_stream_header_len(wrap); }
+
+extern "C" uint64_t zmi_deflate_stream_bound(uint64_t n, uint32_t piece_bytes, int wrap) {
+    if (piece_bytes == 0) return 0;
+    const uint64_t np = n ? (n + piece_bytes - 1u) / piece_bytes : 1u;
+    const uint32_t max_len = n < piece_bytes ? (uint32_t)n : piece_bytes;
+    return np * zmi_deflate_pieces_stride(max_len) + zmi_stream_header_len(wrap) + (wrap == ZMI_WRAP_ZLIB ? 4u : (wrap == ZMI_WRAP_GZIP ? 8u : 0u));
+}
+
+// d_check[i] = Adler-32 (zlib) / CRC-32 (gzip) of piece i's raw bytes; nothing for raw
+static int zmi_piece_checks(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n, int wrap,
+                            uint32_t* d_check, hipStream_t stream) {
+    if (wrap == ZMI_WRAP_RAW || n == 0) return ZMI_E_OK;
+    {
+        zmi_scope_timer tm(c, ZMI_K_CHECKSUM, stream);
+        zmi_launch_checksum((const uint8_t*)d_in, d_in_off, d_in_len, n, wrap == ZMI_WRAP_ZLIB ? 1u : 2u, d_check, d_check, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+extern "C" int zmi_deflate_pieces_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
+                                      uint32_t max_len, int level, int strategy, int wrap, uint32_t flags, int final_piece,
+                                      void* d_out, uint64_t out_stride, uint32_t* d_out_len, uint32_t* d_check, int32_t* d_status,
+                                      void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (flags & ~(uint32_t)ZMI_STREAM_INDEPENDENT) return zmi_fail(ZMI_E_ARG, "zmi_deflate_pieces_dev: unknown flags");
+    if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_GZIP) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip");
+    if (n && (!d_in || !d_in_off || !d_in_len || !d_out || !d_out_len || !d_status || (wrap != ZMI_WRAP_RAW && !d_check)))
+        return zmi_fail(ZMI_E_ARG, "null argument");
+    if (out_stride < zmi_deflate_pieces_stride(max_len)) return zmi_fail(ZMI_E_ARG, "out_stride must be >= zmi_deflate_pieces_stride(max_len)");
+    if (n == 0) return ZMI_E_OK;
+    const bool indep = (flags & ZMI_STREAM_INDEPENDENT) != 0u;
+    ZMI_ON_DEVICE(c);
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = zmi_piece_checks(c, d_in, d_in_off, d_in_len, n, wrap, d_check, stream);
+    if (rc) return rc;
+    return zmi_deflate_impl(c, d_in, d_in_off, d_in_len, n, max_len, level, strategy, ZMI_WRAP_RAW, final_piece ? 1u : 2u, 0u, 15u, d_out,
+                            out_stride, d_out_len, d_status, stream_, indep ? 0 : 1, 0u);
+}
+
+extern "C" int zmi_checksum_combine_dev(zmi_ctx* c, int wrap, const uint32_t* d_check, const uint32_t* d_len, uint32_t world,
+                                        uint32_t n_local, uint32_t* d_out_check, uint64_t* d_out_len, void* stream) {
+    if (!c || (!d_out_check && !d_out_len)) return zmi_fail(ZMI_E_ARG, "null argument");
+    if (wrap != ZMI_WRAP_ZLIB && wrap != ZMI_WRAP_GZIP) return zmi_fail(ZMI_E_ARG, "zmi_checksum_combine_dev: wrap must be zlib or gzip");
+    const uint64_t n64 = (uint64_t)world * n_local;
+    if (world == 0 || n64 > 0xFFFFFFFFull) return zmi_fail(ZMI_E_ARG, "zmi_checksum_combine_dev: world * n_local must be 1 .. 2^32 - 1 entries");
+    if (n64 && (!d_check || !d_len)) return zmi_fail(ZMI_E_ARG, "null argument");
+    ZMI_ON_DEVICE(c);
+    const uint32_t n = (uint32_t)n64, nb = zmi_combine_partials(n);
+    // partials: nb u64 lengths | a u64 | nb u32 checks | a u32 (the u64 / u32 stand in for a result the caller does not want)
+    int rc = zmi_reserve(c->comb, (size_t)nb * 12u + 12u);
+    if (rc) return rc;
+    uint64_t* pl = (uint64_t*)c->comb.p;
+    uint32_t* pc = (uint32_t*)(pl + nb + 1u);
+    uint64_t* rl = d_out_len ? d_out_len : pl + nb;
+    uint32_t* rc_ = d_out_check ? d_out_check : pc + nb;
+    {
+        zmi_scope_timer tm(c, ZMI_K_CHECKSUM, (hipStream_t)stream);
+        zmi_launch_checksum_combine(d_check, d_len, n, world, n_local, wrap == ZMI_WRAP_ZLIB ? 1u : 0u, pc, pl, rc_, rl, (hipStream_t)stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+extern "C" int zmi_stream_frame_dev(zmi_ctx* c, int wrap, int level, int strategy, const uint64_t* d_payload_len, const uint32_t* d_check,
+                                    const uint64_t* d_raw_len, void* d_out, uint64_t out_cap, uint64_t* d_out_len, int32_t* d_status,
+                                    void* stream) {
+    if (!c || !d_payload_len || !d_out || !d_out_len) return zmi_fail(ZMI_E_ARG, "null argument");
+    if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_GZIP) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip");
+    if (wrap != ZMI_WRAP_RAW && !d_check) return zmi_fail(ZMI_E_ARG, "zmi_stream_frame_dev: the check value is needed");
+    if (wrap == ZMI_WRAP_GZIP && !d_raw_len) return zmi_fail(ZMI_E_ARG, "zmi_stream_frame_dev: gzip needs the raw length (ISIZE)");
+    if (level == -1) level = 6;
+    if (level < 0 || level > 9 || strategy < 0 || strategy > 4) return zmi_fail(ZMI_E_ARG, "level must be -1..9, strategy 0..4");
+    ZMI_ON_DEVICE(c);
+    if (d_status) ZMI_HIP(hipMemsetAsync(d_status, 0, 4, (hipStream_t)stream));
+    {
+        zmi_scope_timer tm(c, ZMI_K_PACK, (hipStream_t)stream);
+        zmi_launch_frame((uint8_t*)d_out, out_cap, (uint32_t)wrap, (uint32_t)level, (uint32_t)strategy, d_payload_len, d_check, d_raw_len,
+                         d_out_len, d_status, nullptr, 0u, nullptr, 0u, (hipStream_t)stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+extern "C" int zmi_deflate_stream_dev(zmi_ctx* c, const void* d_in, uint64_t n, uint32_t piece_bytes, int level, int strategy, int wrap,
+                                      uint32_t flags, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_piece_off,
+                                      int32_t* d_status, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (piece_bytes == 0 || piece_bytes > (1u << 30)) return zmi_fail(ZMI_E_ARG, "piece_bytes must be 1 .. 2^30");
+    if (flags & ~(uint32_t)ZMI_STREAM_INDEPENDENT) return zmi_fail(ZMI_E_ARG, "zmi_deflate_stream_dev: unknown flags");
+    if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_GZIP) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip");
+    if (level == -1) level = 6;
+    if (level < 0 || level > 9) return zmi_fail(ZMI_E_ARG, "level must be -1..9");
+    if (strategy < 0 || strategy > 4) return zmi_fail(ZMI_E_ARG, "strategy must be 0..4");
+    if ((n && !d_in) || !d_out || !d_out_len || !d_status) return zmi_fail(ZMI_E_ARG, "null argument");
+    const uint64_t np64 = n ? (n + piece_bytes - 1u) / piece_bytes : 1u;
+    if (np64 > 0x7FFFFFFFull) return zmi_fail(ZMI_E_ARG, "zmi_deflate_stream_dev: more than 2^31 - 1 pieces");
+    const uint32_t np = (uint32_t)np64;
+    const bool indep = (flags & ZMI_STREAM_INDEPENDENT) != 0u;
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+
+    // per-piece tables: in_off u64 | piece offsets u64 [np + 1] (unless the caller's index holds them) | raw total u64 |
+    // in_len u32 | out_len u32 | status i32 | check u32 | combined check u32
+    const size_t own_off = d_piece_off ? 0u : ((size_t)np + 1u) * 8u;
+    int rc = zmi_reserve(c->sd_meta, (size_t)np * 8u + own_off + 8u + (size_t)np * 16u + 16u);
+    if (rc) return rc;
+    uint64_t* d_off = (uint64_t*)c->sd_meta.p;
+    uint64_t* d_poff = d_piece_off ? d_piece_off : d_off + np;
+    uint64_t* d_raw = (uint64_t*)((uint8_t*)c->sd_meta.p + (size_t)np * 8u + own_off);
+    uint32_t* d_len = (uint32_t*)(d_raw + 1);
+    uint32_t* d_olen = d_len + np;
+    int32_t* d_st = (int32_t*)(d_olen + np);
+    uint32_t* d_chk = (uint32_t*)(d_st + np);
+    uint32_t* d_comb = d_chk + np;
+
+    // launch groups: one group's output slots and the encoder's match scratch together stay within the scratch limit
+    const uint32_t max_len = n < piece_bytes ? (uint32_t)n : piece_bytes;
+    const uint64_t stride = zmi_deflate_pieces_stride(max_len);
+    const uint64_t match_per = ((((uint64_t)max_len + 63u) & ~63ull) ? (((uint64_t)max_len + 63u) & ~63ull) : 64u) * 4u;
+    uint64_t group = c->scratch_limit / (stride + match_per + match_per / 16u);
+    if (const char* gv = zmi_tune("ZMI_STREAM_GROUP")) if (atoll(gv) > 0) group = (uint64_t)atoll(gv);
+    if (group == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one piece");
+    if (group > np) group = np;
+    rc = zmi_reserve(c->sd_slots, (size_t)(group * stride));
+    if (rc) return rc;
+
+    ZMI_HIP(hipMemsetAsync(d_status, 0, 4, stream));
+    ZMI_HIP(hipMemsetAsync(d_poff, 0, 8, stream));   // where the first group's pack starts
+    zmi_launch_piece_layout(n, piece_bytes, np, d_off, d_len, stream);
+    rc = zmi_piece_checks(c, d_in, d_off, d_len, np, wrap, d_chk, stream);
+    if (rc) return rc;
+    const uint32_t h = zmi_stream_header_len(wrap);
+    uint8_t* const payload = (uint8_t*)d_out + h;
+    const uint64_t payload_cap = out_cap > h ? out_cap - h : 0u;
+    for (uint64_t first = 0; first < np; first += group) {
+        const uint32_t cnt = (uint32_t)(np - first < group ? np - first : group);
+        const bool last = first + cnt == np;
+        // carry-over across a group boundary: the group's first piece sees the history in front of it (lz77.hip reads it as
+        // dict_len bytes in front of the launch's first segment; anything beyond the window is the same as a full window)
+        const uint64_t before = indep ? 0u : first * (uint64_t)piece_bytes;
+        rc = zmi_deflate_impl(c, d_in, d_off + first, d_len + first, cnt, max_len, level, strategy, ZMI_WRAP_RAW, last ? 1u : 2u,
+                              (uint32_t)(before < 65536u ? before : 65536u), 15u, c->sd_slots.p, stride, d_olen + first, d_st + first,
+                              stream_, indep ? 0 : 1, np);
+        if (rc) return rc;
+        // the group's pieces go behind the previous group's, the running offset never leaves the device
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_scan_sizes_base(d_olen + first, cnt, d_poff + first, d_poff + first, stream);
+        zmi_launch_copy_ranges((const uint8_t*)c->sd_slots.p, nullptr, stride, d_olen + first, cnt, payload, d_poff + first, payload_cap,
+                               stride > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)stride, stream);
+    }
+    if (wrap != ZMI_WRAP_RAW) {
+        rc = zmi_checksum_combine_dev(c, wrap, d_chk, d_len, 1u, np, d_comb, d_raw, stream_);
+        if (rc) return rc;
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_frame((uint8_t*)d_out, out_cap, (uint32_t)wrap, (uint32_t)level, (uint32_t)strategy, d_poff + np, d_comb, d_raw, d_out_len,
+                         d_status, d_st, np, d_piece_off, d_piece_off ? np + 1u : 0u, stream);
     }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;

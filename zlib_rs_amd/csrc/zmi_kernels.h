@@ -63,6 +63,19 @@ int zmi_launch_gen(uint8_t* d_out, uint64_t seed, uint32_t first_shard, uint32_t
 int zmi_launch_gen_strided(uint8_t* d_out, uint64_t seed, uint32_t first_shard, uint32_t shard_step, uint32_t n_shards,
                            uint32_t shard_bytes, hipStream_t stream);
 int zmi_launch_scan_sizes(const uint32_t* d_len, uint32_t n, uint64_t* d_off, hipStream_t stream);
+// the same scan, offsets starting at *d_base (a device word; may be d_off[0] itself)
+int zmi_launch_scan_sizes_base(const uint32_t* d_len, uint32_t n, uint64_t* d_off, const uint64_t* d_base, hipStream_t stream);
+// single-stream deflate (pack.hip, checksum.hip): the pieces of a buffer, the wrapper around their packed deflate bytes, and the
+// check value of the concatenation from the pieces' (check, raw length) pairs
+int zmi_launch_piece_layout(uint64_t n, uint32_t piece_bytes, uint32_t count, uint64_t* d_off, uint32_t* d_len, hipStream_t stream);
+uint32_t zmi_stream_header_len(int wrap);
+int zmi_launch_frame(uint8_t* d_out, uint64_t out_cap, uint32_t wrap, uint32_t level, uint32_t strategy, const uint64_t* d_payload,
+                     const uint32_t* d_check, const uint64_t* d_raw_len, uint64_t* d_out_len, int32_t* d_status, const int32_t* d_piece_st,
+                     uint32_t n_st, uint64_t* d_index, uint32_t n_index, hipStream_t stream);
+uint32_t zmi_combine_partials(uint32_t n);
+int zmi_launch_checksum_combine(const uint32_t* d_check, const uint32_t* d_len, uint32_t n, uint32_t world, uint32_t n_local,
+                                uint32_t adler, uint32_t* d_pc, uint64_t* d_pl, uint32_t* d_out_check, uint64_t* d_out_len,
+                                hipStream_t stream);
 int zmi_launch_copy_ranges(const uint8_t* d_src, const uint64_t* d_src_off, uint64_t src_stride, const uint32_t* d_len,
                            uint32_t n, uint8_t* d_dst, const uint64_t* d_dst_off, uint64_t dst_cap, uint32_t max_len,
                            hipStream_t stream);

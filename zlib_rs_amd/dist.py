@@ -143,6 +143,33 @@ def stitch_on_device(engine, slabs, size_table, out=None):
     return out, total
 
 
+def stitch_single_stream_on_device(engine, slabs, size_table, check_table, raw_len_table, level=6, strategy=0, wrap=2, out=None):
+    """The single-stream counterpart of stitch_on_device: the per-rank slabs of pieces made by Engine.deflate_pieces (every piece
+    but the last behind a flush marker) become ONE raw / zlib / gzip stream -- the wrapper once, the pieces in global order at
+    out[header:], the trailer from the device combine of the all-gathered check / raw-length tables (all [world, n_local], rank-major,
+    padded with zeros).  Returns (stream uint8 view, total bytes).  With independent pieces this is byte-identical to one
+    Engine.deflate_stream(independent=True) call on the whole input."""
+    world = int(size_table.shape[0])
+    table = size_table.to(torch.int32).contiguous().to(engine.device)
+    goff, soff, totals = engine.stitch_plan(table)
+    h = engine.stream_header_bytes(wrap)
+    if out is None:
+        out = torch.empty(h + totals[world] + 16, dtype=torch.uint8, device=engine.device)
+    max_len = int(table.max().item()) if table.numel() else 0
+    for r, sl in enumerate(slabs):
+        engine.copy_ranges(sl, soff[r, :-1].contiguous(), 0, table[r].contiguous(), max(1, max_len), out[h:], goff[r].contiguous())
+    check = raw = None
+    if wrap != 0:
+        check, raw = engine.checksum_combine(check_table.to(torch.int32).contiguous().to(engine.device),
+                                             raw_len_table.to(torch.int32).contiguous().to(engine.device), wrap, world)
+    payload = torch.tensor([totals[world]], dtype=torch.int64, device=engine.device)
+    from .engine import _len_status
+    length, status = _len_status(engine.stream_frame(out, payload, check, raw, wrap, level, strategy))
+    if status != 0:
+        raise RuntimeError("zmi_stream_frame_dev: status %d" % status)
+    return out[:length], length
+
+
 def max_over_ranks(seconds, device):
     t = torch.tensor([seconds], dtype=torch.float64, device=device)
     if dist.is_initialized() and dist.get_world_size() > 1:

@@ -149,6 +149,67 @@ class Engine:
                                                 status.data_ptr(), _stream_ptr()), "zmi_deflate_batch_dev")
         return out, out_len, status
 
+    # ---- one stream (pigz-style): the pieces of a buffer as ONE raw / zlib / gzip stream (include/zmi355.h) ----
+    def stream_bound(self, n, piece_bytes=1 << 20, wrap=WRAP_GZIP):
+        return int(self.L.zmi_deflate_stream_bound(int(n), int(piece_bytes), int(wrap)))
+
+    def stream_header_bytes(self, wrap):
+        return int(self.L.zmi_stream_header_bytes(int(wrap)))
+
+    def deflate_stream(self, data, level=6, strategy=0, wrap=WRAP_GZIP, piece_bytes=1 << 20, independent=False, index=False, out=None):
+        """data: uint8 device tensor -> a uint8 view of exactly the stream (and, with index=True, the int64 byte offsets in it of every
+        piece's first deflate byte plus the end of the deflate data).  Carry-over pieces by default (Z_SYNC_FLUSH between them);
+        independent=True: every piece forgets history (Z_FULL_FLUSH) and decodes alone.  One synchronisation, for the length."""
+        n = int(data.numel())
+        n_pieces = max(1, -(-n // int(piece_bytes)))
+        if out is None:
+            out = torch.empty(self.stream_bound(n, piece_bytes, wrap), dtype=torch.uint8, device=self.device)
+        meta = torch.zeros(2, dtype=torch.int64, device=self.device)     # length | status (int32)
+        idx = torch.empty(n_pieces + 1, dtype=torch.int64, device=self.device) if index else None
+        _lib.check(self.L.zmi_deflate_stream_dev(self._ctx, data.data_ptr() if n else None, n, int(piece_bytes), int(level), int(strategy),
+                                                 int(wrap), 1 if independent else 0, out.data_ptr(), int(out.numel()), meta.data_ptr(),
+                                                 idx.data_ptr() if index else None, meta.data_ptr() + 8, _stream_ptr()),
+                   "zmi_deflate_stream_dev")
+        length, status = _len_status(meta)
+        if status != 0:
+            raise RuntimeError("zmi_deflate_stream_dev: status %d (stream of %d bytes, room for %d)" % (status, length, out.numel()))
+        return (out[:length], idx) if index else out[:length]
+
+    def deflate_pieces(self, data, offsets, lengths, max_len, level=6, strategy=0, wrap=WRAP_GZIP, independent=True, final=True):
+        """One rank's pieces of a single stream: (slots [n, stride] uint8, sizes int32 [n], checks int32 [n], status int32 [n])."""
+        n = int(lengths.numel())
+        stride = int(self.L.zmi_deflate_pieces_stride(int(max_len)))
+        slots = torch.empty((max(n, 1), stride), dtype=torch.uint8, device=self.device)
+        sizes = torch.zeros(n, dtype=torch.int32, device=self.device)
+        checks = torch.zeros(n, dtype=torch.int32, device=self.device)
+        status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        _lib.check(self.L.zmi_deflate_pieces_dev(self._ctx, data.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, int(max_len),
+                                                 int(level), int(strategy), int(wrap), 1 if independent else 0, 1 if final else 0,
+                                                 slots.data_ptr(), stride, sizes.data_ptr(), checks.data_ptr(), status.data_ptr(),
+                                                 _stream_ptr()), "zmi_deflate_pieces_dev")
+        return slots, sizes, checks, status
+
+    def checksum_combine(self, checks, lengths, wrap=WRAP_GZIP, world=1):
+        """(check, raw length) pairs -> (check int32 [1], total length int64 [1]) of the concatenation, on the device.  With world > 1
+        the tables are rank-major ([world, n_local]: entry [r, j] is piece j * world + r), as dist's all-gathered tables are."""
+        n = int(lengths.numel())
+        c = torch.empty(1, dtype=torch.int32, device=self.device)
+        t = torch.empty(1, dtype=torch.int64, device=self.device)
+        _lib.check(self.L.zmi_checksum_combine_dev(self._ctx, int(wrap), checks.data_ptr() if n else None, lengths.data_ptr() if n else None,
+                                                   int(world), n // int(world), c.data_ptr(), t.data_ptr(), _stream_ptr()),
+                   "zmi_checksum_combine_dev")
+        return c, t
+
+    def stream_frame(self, out, payload_len, check, raw_len, wrap=WRAP_GZIP, level=6, strategy=0):
+        """header and trailer around the payload_len (int64 device word) bytes of deflate data at out[header:]; returns the int64
+        [2] device words length | status"""
+        meta = torch.zeros(2, dtype=torch.int64, device=self.device)
+        _lib.check(self.L.zmi_stream_frame_dev(self._ctx, int(wrap), int(level), int(strategy), payload_len.data_ptr(),
+                                               check.data_ptr() if check is not None else None,
+                                               raw_len.data_ptr() if raw_len is not None else None, out.data_ptr(), int(out.numel()),
+                                               meta.data_ptr(), meta.data_ptr() + 8, _stream_ptr()), "zmi_stream_frame_dev")
+        return meta
+
     # ---- inflate ----
     def inflate_batch(self, data, offsets, lengths, out, out_offsets, out_caps, wrap=WRAP_ZLIB, out_len=None, status=None):
         n = int(lengths.numel())
@@ -173,6 +234,13 @@ class Engine:
         _lib.check(self.L.zmi_checksum_batch_dev(self._ctx, data.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, kind,
                                                  a.data_ptr(), c.data_ptr(), _stream_ptr()), "zmi_checksum_batch_dev")
         return a, c
+
+
+def _len_status(meta):
+    """int64 [2] device words (length, int32 status in the low half of the second) -> host ints, one synchronisation"""
+    length, st = meta.tolist()
+    st &= 0xFFFFFFFF
+    return int(length), st - (1 << 32) if st >= 1 << 31 else st
 
 
 def uniform_layout(n, shard_bytes, device):

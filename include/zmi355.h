@@ -79,7 +79,7 @@ int zmi_ctx_last_codes_used(zmi_ctx* ctx, uint32_t* entries);
 int zmi_ctx_reset_codes_used(zmi_ctx* ctx);
 
 /* per-kernel HIP-event timing for benchmarking: kernels 0 checksum, 1 lz77, 2 encode, 3 inflate (decode),
- * 4 verify, 5 cost parse (deflate levels 3-9), 6 inflate (resolve), 7 pack / stitch copies.  zmi_ctx_get_timing synchronises, returns the sums (ms) / launch counts since the
+ * 4 verify, 5 cost parse (deflate levels 3-9) / window scan (zmi_inflate_stream_dev), 6 inflate (resolve), 7 pack / stitch copies.  zmi_ctx_get_timing synchronises, returns the sums (ms) / launch counts since the
  * previous call (arrays of 8) and resets them. */
 int zmi_ctx_set_timing(zmi_ctx* ctx, int on);
 int zmi_ctx_get_timing(zmi_ctx* ctx, double* ms_sums, uint32_t* counts);
@@ -287,6 +287,46 @@ int zmi_checksum_combine_dev(zmi_ctx* ctx, int wrap, const uint32_t* d_check, co
 int zmi_stream_frame_dev(zmi_ctx* ctx, int wrap, int level, int strategy, const uint64_t* d_payload_len, const uint32_t* d_check,
                          const uint64_t* d_raw_len, void* d_out, uint64_t out_cap, uint64_t* d_out_len, int32_t* d_status,
                          void* stream);
+
+/* ---- single-stream inflate (pigz-style): the inverse of zmi_deflate_stream_dev --------------------------------------------------
+ * zmi_inflate_stream_dev    d_in[0 .. in_len) holds ONE member: raw, zlib, gzip, or ZMI_WRAP_AUTO (zlib or gzip by its first bytes).
+ *                           d_cuts[0 .. n_cuts) are byte offsets in d_in where pieces start: entry 0 is the end of the header, the
+ *                           rest ascend (the first n_pieces entries of zmi_deflate_stream_dev's index are valid as they stand).  Every
+ *                           cut is only a proposal: it counts if the decode of the piece in front of it ended exactly there, on a block
+ *                           boundary, with all its output complete (the rule of zmi_inflate_split).  piece_out_max (1 .. 2^30) bounds the
+ *                           output of any one piece and sizes the decode regions (this library's streams: piece_bytes; pigz: 128 KiB).
+ *                           Asynchronous on `stream`, no host synchronisation inside, any length.  Device words written:
+ *                           *d_status  0: the stream ended and its check value (and gzip ISIZE, the low 32 bits of the length) match;
+ *                                      Z_DATA_ERROR (-3): a corrupt block, a distance in front of the stream's start, a bad header, a
+ *                                      wrong check value or length, a cut that did not verify; Z_BUF_ERROR (-5): truncated input, a piece
+ *                                      that produced more than piece_out_max, or the output does not fit out_cap (*d_out_len then tells
+ *                                      the size it needs); Z_NEED_DICT (2): the zlib FDICT flag (preset dictionaries are not supported).
+ *                                      Never status 0 with wrong bytes.
+ *                           *d_detail  which case (ZMI_SI_* below) in its low 8 bits; for ZMI_SI_CUT the index of the first cut that
+ *                                      did not verify, for ZMI_SI_PIECE / ZMI_SI_DATA / ZMI_SI_FAR the index of the piece, above them.
+ *                           *d_out_len the length of the output; *d_in_used header + deflate data + trailer (the next gzip member
+ *                                      starts there).  Nothing at or behind d_out + out_cap is written.
+ *                           The result does not depend on the scratch limit: pieces beyond it run in launch groups whose output offsets
+ *                           and 32 KiB window carry over on the device.
+ * zmi_stream_find_cuts_dev  parses the header and writes its end to d_cuts[0], then proposes the byte behind every byte-aligned
+ *                           00 00 FF FF behind it, proposals at least min_gap input bytes apart, at most cap entries in all;
+ *                           *d_n_cuts = entries written (a device word: reading it is the caller's one synchronisation).  False
+ *                           proposals (a stored block holding the pattern) are caught by the cut verification above. */
+#define ZMI_SI_HEADER 1  /* bad header (status Z_DATA_ERROR) */
+#define ZMI_SI_TRUNC 2   /* the input ends inside the header, the deflate data or the trailer (Z_BUF_ERROR) */
+#define ZMI_SI_CUT 3     /* a cut did not verify (Z_DATA_ERROR); index = the cut */
+#define ZMI_SI_PIECE 4   /* a piece produced more than piece_out_max (Z_BUF_ERROR); index = the piece */
+#define ZMI_SI_DATA 5    /* a corrupt block (Z_DATA_ERROR); index = the piece */
+#define ZMI_SI_FAR 6     /* a distance reaches in front of the stream's start (Z_DATA_ERROR); index = the piece */
+#define ZMI_SI_CHECK 7   /* wrong Adler-32 / CRC-32 (Z_DATA_ERROR) */
+#define ZMI_SI_LENGTH 8  /* wrong gzip ISIZE (Z_DATA_ERROR) */
+#define ZMI_SI_OUT 9     /* the output does not fit out_cap (Z_BUF_ERROR) */
+#define ZMI_SI_DICT 10   /* zlib FDICT set (Z_NEED_DICT) */
+int zmi_inflate_stream_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, int wrap, const uint64_t* d_cuts, uint32_t n_cuts,
+                           uint32_t piece_out_max, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used,
+                           int32_t* d_status, int32_t* d_detail, void* stream);
+int zmi_stream_find_cuts_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, int wrap, uint64_t min_gap, uint64_t* d_cuts, uint32_t cap,
+                             uint32_t* d_n_cuts, void* stream);
 
 /* ---- host-buffer convenience wrappers: copy in, run the batch on the GPU, copy back ---- */
 int zmi_deflate_batch(zmi_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_shards,

@@ -2026,3 +2026,558 @@ extern "C" int zmi_launch_inflate_verify(const uint8_t* d_in, const uint64_t* d_
                wrap, d_check, d_adler, d_crc, n_streams, d_status, d_detail);
     return 0;
 }
+
+// ==== single-stream inflate (zmi_inflate_stream_dev, zmi_stream_find_cuts_dev) ================================================
+// One raw / zlib / gzip stream whose pieces start behind flush markers (zmi_deflate_stream_dev, pigz) is decoded piece-parallel:
+// every piece is decoded by the kernel above as a raw stream that may reach 32 KiB in front of itself (taken on trust), its
+// holes are resolved into 16-BIT SYMBOLS (0..255 a literal, 256 + h byte h of the 32 KiB window in front of the piece), the
+// windows of all pieces come from an associative scan over per-piece window maps, and one elementwise pass writes the bytes.
+// Nothing in a piece waits for the bytes of the piece in front of it.
+#define SI_HIST 32768u              // the window in front of a piece
+#define SI_RING 4096u               // symbolic resolve: symbols of output history kept in LDS (8 KiB)
+#define SI_MASK (SI_RING - 1u)
+#define SI_CH 1024u                 // positions per chunk (16 bitmap words); regions are multiples of this
+#define SI_CW (SI_CH / 64u)
+#define SI_NEAR 2048u               // a source further back than this is read from the piece's symbols in HBM
+#define SI_LOAD 512u                // positions staged per wave step (8 per lane)
+// the ring holds [c0 - SI_NEAR, loaded) while the holes of chunk c0 are filled: loaded <= c0 + SI_CH + 258 + SI_LOAD - 1
+static_assert(SI_NEAR + SI_CH + 258u + SI_LOAD - 1u <= SI_RING, "symbolic resolve ring budget");
+// a far source ends in front of the chunk being resolved (everything there was written back)
+static_assert(SI_NEAR >= SI_CH + 258u, "far sources must be final in HBM");
+
+// detail kinds (low 8 bits of *d_detail; the index of the cut / piece concerned above them), include/zmi355.h
+#define SI_D_HEADER 1u
+#define SI_D_TRUNC 2u
+#define SI_D_CUT 3u
+#define SI_D_PIECE 4u
+#define SI_D_DATA 5u
+#define SI_D_FAR 6u
+#define SI_D_CHECK 7u
+#define SI_D_LENGTH 8u
+#define SI_D_OUT 9u
+#define SI_D_DICT 10u
+
+// one symbol of the piece's output that this wave wrote back earlier: read past the CU's L1
+static __device__ __forceinline__ uint16_t si_ld_final(const uint16_t* sym, uint32_t x) {
+    const uint32_t* q = (const uint32_t*)(sym + (x & ~1u));
+#ifdef ZMI_EMU
+    const uint32_t w = *q;
+#else
+    const uint32_t w = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+    return (uint16_t)(w >> (16u * (x & 1u)));
+}
+// source symbol x of a piece (x < 0: byte SI_HIST + x of the window in front of it)
+static __device__ __forceinline__ uint16_t si_src(const uint16_t* ring, const uint16_t* sym, int32_t x, bool far) {
+    if (x < 0) return (uint16_t)(256 + (int32_t)SI_HIST + (x < -(int32_t)SI_HIST ? -(int32_t)SI_HIST : x));
+    return far ? si_ld_final(sym, (uint32_t)x) : ring[(uint32_t)x & SI_MASK];
+}
+
+// One wave per piece: the decode output (literals, 3-byte records in the holes, one bitmap bit per hole) streams through an LDS
+// ring of u16 symbols, chunk by chunk; the holes of a chunk are taken 64 at a time, one per lane, and a hole is filled once its
+// source ends in front of the first unfinished hole (then every symbol it reads is final -- a self-overlapping copy reads only
+// its first `dist` symbols); finished chunks are written back to sym as u16.
+__global__ void __launch_bounds__(64) zmi_si_resolve_kernel(const uint8_t* __restrict__ dec, uint64_t stride, const uint32_t* __restrict__ out_len,
+                                                            uint32_t cap, const uint64_t* __restrict__ bitmap, const uint64_t* __restrict__ bm_off,
+                                                            uint16_t* sym) {
+    __shared__ __attribute__((aligned(16))) uint16_t ring[SI_RING];
+    __shared__ uint16_t list[22u * SI_CW];   // hole positions of the chunk (a hole is >= 3 bytes: <= 22 per bitmap word)
+    const uint32_t lane = zmi_lane();
+    const uint32_t s = blockIdx.x;
+    const uint64_t bmo = bm_off[s];
+    uint32_t L = out_len[s];
+    if (L > cap) L = cap;
+    if (bmo == ~0ull) L = 0u;
+    const uint8_t* src = dec + (uint64_t)s * stride;
+    uint16_t* out = sym + (uint64_t)s * stride;
+    const uint64_t* bm = bitmap + bmo;
+    const uint32_t nwords = (L + 63u) >> 6;
+    uint32_t loaded = 0;
+    for (uint32_t c0 = 0; c0 < L; c0 += SI_CH) {
+        const uint32_t upto = c0 + SI_CH + 258u < L ? c0 + SI_CH + 258u : L;
+        zmi_wave_order();
+        while (loaded < upto) {   // (the region has SI_LOAD bytes of slack behind every piece's capacity)
+            const uint32_t x = loaded + 8u * lane;
+            const uint32_t v0 = *(const uint32_t*)(src + x), v1 = *(const uint32_t*)(src + x + 4u);
+            uint4 q;
+            q.x = (v0 & 0xFFu) | ((v0 & 0xFF00u) << 8);
+            q.y = ((v0 >> 16) & 0xFFu) | ((v0 >> 8) & 0xFF0000u);
+            q.z = (v1 & 0xFFu) | ((v1 & 0xFF00u) << 8);
+            q.w = ((v1 >> 16) & 0xFFu) | ((v1 >> 8) & 0xFF0000u);
+            *(uint4*)(ring + (x & SI_MASK)) = q;
+            loaded += SI_LOAD;
+        }
+        zmi_wave_order();
+        const uint32_t w0 = c0 >> 6;
+        const uint64_t bv = (lane < SI_CW && w0 + lane < nwords) ? bm[w0 + lane] : 0ull;
+        const uint32_t pc = (uint32_t)__popcll(bv);
+        const uint32_t incl = zmi_wave_incl_scan(pc);
+        const uint32_t total = zmi_readlane(incl, 63u);
+        if (total) {
+            {
+                uint64_t t = bv;
+                uint32_t k = incl - pc;
+                while (t) {
+                    list[k++] = (uint16_t)(lane * 64u + (uint32_t)__ffsll((unsigned long long)t) - 1u);
+                    t &= t - 1ull;
+                }
+            }
+            zmi_wave_order();
+            for (uint32_t b0 = 0; b0 < total; b0 += 64u) {
+                const uint32_t nb = total - b0 < 64u ? total - b0 : 64u;
+                const bool active = lane < nb;
+                const uint32_t p = c0 + (active ? (uint32_t)list[b0 + lane] : 0u);
+                uint32_t mlen = 0, md = 1;
+                if (active) {
+                    const uint32_t rec = (ring[p & SI_MASK] & 0xFFu) | ((uint32_t)(ring[(p + 1u) & SI_MASK] & 0xFFu) << 8) |
+                                         ((uint32_t)(ring[(p + 2u) & SI_MASK] & 0xFFu) << 16);
+                    mlen = (rec >> 15) + 3u;
+                    mlen = mlen > 258u ? 258u : mlen;
+                    md = (rec & 0x7FFFu) + 1u;
+                }
+                const int32_t s0 = (int32_t)p - (int32_t)md;
+                const int32_t e = s0 + (int32_t)(mlen < md ? mlen : md);   // end of what the hole reads
+                const bool far = md > SI_NEAR;
+                uint64_t done = nb == 64u ? 0ull : ~0ull << nb;
+                zmi_wave_order();   // every record is read before any hole is filled
+                while (~done) {
+                    const uint32_t D = (uint32_t)__ffsll((unsigned long long)~done) - 1u;
+                    const int32_t pD = (int32_t)zmi_readlane(p, D);
+                    const uint64_t R = __ballot(active && !((done >> lane) & 1ull) && e <= pD);
+                    if ((R >> lane) & 1ull) {
+                        const bool wrapc = md < mlen;
+                        for (uint32_t i = 0; i < mlen; i += 8u) {
+                            uint16_t v[8];
+#pragma unroll
+                            for (uint32_t k = 0; k < 8u; ++k) {
+                                const uint32_t ii = i + k;
+                                v[k] = ii < mlen ? si_src(ring, out, s0 + (int32_t)(wrapc ? ii % md : ii), far) : (uint16_t)0;
+                            }
+#pragma unroll
+                            for (uint32_t k = 0; k < 8u; ++k)
+                                if (i + k < mlen) ring[(p + i + k) & SI_MASK] = v[k];
+                        }
+                    }
+                    done |= R;
+                    zmi_wave_order();
+                }
+            }
+        }
+        // [c0, c0 + SI_CH) is final: back to HBM (the region is a multiple of SI_CH)
+        for (uint32_t k = 8u * lane; k < SI_CH; k += SI_LOAD) {
+            const uint32_t x = c0 + k;
+            if (x < L) *(uint4*)(out + x) = *(const uint4*)(ring + (x & SI_MASK));
+        }
+        zmi_wave_order();
+        __threadfence();   // the far reads of later chunks find these symbols
+    }
+}
+extern "C" int zmi_launch_si_resolve(const uint8_t* d_dec, uint64_t stride, const uint32_t* d_out_len, uint32_t cap, uint32_t n,
+                                     const uint64_t* d_bitmap, const uint64_t* d_bm_off, uint16_t* d_sym, hipStream_t stream) {
+    if (n == 0) return 0;
+    ZMI_LAUNCH(zmi_si_resolve_kernel, dim3(n), dim3(64), 0, stream, d_dec, stride, d_out_len, cap, d_bitmap, d_bm_off, d_sym);
+    return 0;
+}
+
+// ---- the window scan ----------------------------------------------------------------------------------------------------------
+// The last 32 KiB of (window in front of piece i ++ its output) is a map over the window in front: M_i[k] = a literal or 256 + h.
+// Maps compose associatively ((M o A)[k] = M[k] < 256 ? M[k] : A[M[k] - 256]), so the windows of a launch group come from three
+// passes of depth B, n / B and B: per block of B pieces the composed map (agg), a chain over the blocks from the carried window
+// (wstart, and the carry for the next group), and per block the windows in front of its pieces (win).
+static __device__ __forceinline__ uint32_t si_map(const uint16_t* S, uint32_t L, uint32_t k) {
+    const uint32_t t = k + L;
+    if (t < SI_HIST) return 256u + t;
+    const uint32_t m = S[(uint64_t)L - SI_HIST + k];
+    return m >= 256u + SI_HIST ? 256u : m;   // (only a failed piece holds anything else; its status says so)
+}
+#define SI_SCAN_T 1024u
+#define SI_PER (SI_HIST / SI_SCAN_T)
+__global__ void __launch_bounds__(SI_SCAN_T) zmi_si_wagg_kernel(const uint16_t* __restrict__ sym, uint64_t stride, const uint32_t* __restrict__ len,
+                                                                uint32_t n, uint32_t B, uint16_t* __restrict__ agg) {
+    __shared__ uint16_t A[SI_HIST];
+    const uint32_t t = threadIdx.x, b = blockIdx.x;
+    const uint32_t lo = b * B, hi = lo + B < n ? lo + B : n;
+    for (uint32_t j = 0; j < SI_PER; ++j) A[t + SI_SCAN_T * j] = (uint16_t)(256u + t + SI_SCAN_T * j);
+    __syncthreads();
+    for (uint32_t i = lo; i < hi; ++i) {
+        const uint16_t* S = sym + (uint64_t)i * stride;
+        const uint32_t L = len[i];
+        uint16_t r[SI_PER];
+        for (uint32_t j = 0; j < SI_PER; ++j) {
+            const uint32_t m = si_map(S, L, t + SI_SCAN_T * j);
+            r[j] = m < 256u ? (uint16_t)m : A[m - 256u];
+        }
+        __syncthreads();
+        for (uint32_t j = 0; j < SI_PER; ++j) A[t + SI_SCAN_T * j] = r[j];
+        __syncthreads();
+    }
+    for (uint32_t j = 0; j < SI_PER; ++j) agg[(uint64_t)b * SI_HIST + t + SI_SCAN_T * j] = A[t + SI_SCAN_T * j];
+}
+__global__ void __launch_bounds__(SI_SCAN_T) zmi_si_wchain_kernel(const uint16_t* __restrict__ agg, uint32_t nb, uint8_t* carry,
+                                                                  uint8_t* __restrict__ wstart) {
+    __shared__ uint8_t W[SI_HIST];
+    const uint32_t t = threadIdx.x;
+    for (uint32_t j = 0; j < SI_PER; ++j) W[t + SI_SCAN_T * j] = carry[t + SI_SCAN_T * j];
+    __syncthreads();
+    for (uint32_t b = 0; b < nb; ++b) {
+        uint8_t r[SI_PER];
+        for (uint32_t j = 0; j < SI_PER; ++j) {
+            const uint32_t k = t + SI_SCAN_T * j;
+            wstart[(uint64_t)b * SI_HIST + k] = W[k];
+            const uint32_t a = agg[(uint64_t)b * SI_HIST + k];
+            r[j] = a < 256u ? (uint8_t)a : W[a - 256u];
+        }
+        __syncthreads();
+        for (uint32_t j = 0; j < SI_PER; ++j) W[t + SI_SCAN_T * j] = r[j];
+        __syncthreads();
+    }
+    for (uint32_t j = 0; j < SI_PER; ++j) carry[t + SI_SCAN_T * j] = W[t + SI_SCAN_T * j];
+}
+__global__ void __launch_bounds__(SI_SCAN_T) zmi_si_wfill_kernel(const uint16_t* __restrict__ sym, uint64_t stride, const uint32_t* __restrict__ len,
+                                                                 uint32_t n, uint32_t B, const uint8_t* __restrict__ wstart, uint8_t* __restrict__ win) {
+    __shared__ uint8_t W[SI_HIST];
+    const uint32_t t = threadIdx.x, b = blockIdx.x;
+    const uint32_t lo = b * B, hi = lo + B < n ? lo + B : n;
+    for (uint32_t j = 0; j < SI_PER; ++j) W[t + SI_SCAN_T * j] = wstart[(uint64_t)b * SI_HIST + t + SI_SCAN_T * j];
+    __syncthreads();
+    for (uint32_t i = lo; i < hi; ++i) {
+        const uint16_t* S = sym + (uint64_t)i * stride;
+        const uint32_t L = len[i];
+        uint8_t r[SI_PER];
+        for (uint32_t j = 0; j < SI_PER; ++j) {
+            const uint32_t k = t + SI_SCAN_T * j;
+            win[(uint64_t)i * SI_HIST + k] = W[k];
+            const uint32_t m = si_map(S, L, k);
+            r[j] = m < 256u ? (uint8_t)m : W[m - 256u];
+        }
+        __syncthreads();
+        for (uint32_t j = 0; j < SI_PER; ++j) W[t + SI_SCAN_T * j] = r[j];
+        __syncthreads();
+    }
+}
+extern "C" uint32_t zmi_si_scan_blocks(uint32_t n, uint32_t B) { return (n + B - 1u) / B; }
+extern "C" int zmi_launch_si_window_scan(const uint16_t* d_sym, uint64_t stride, const uint32_t* d_len, uint32_t n, uint32_t B, uint16_t* d_agg,
+                                         uint8_t* d_carry, uint8_t* d_wstart, uint8_t* d_win, hipStream_t stream) {
+    if (n == 0) return 0;
+    const uint32_t nb = (n + B - 1u) / B;
+    ZMI_LAUNCH(zmi_si_wagg_kernel, dim3(nb), dim3(SI_SCAN_T), 0, stream, d_sym, stride, d_len, n, B, d_agg);
+    ZMI_LAUNCH(zmi_si_wchain_kernel, dim3(1), dim3(SI_SCAN_T), 0, stream, (const uint16_t*)d_agg, nb, d_carry, d_wstart);
+    ZMI_LAUNCH(zmi_si_wfill_kernel, dim3(nb), dim3(SI_SCAN_T), 0, stream, d_sym, stride, d_len, n, B, (const uint8_t*)d_wstart, d_win);
+    return 0;
+}
+
+// ---- substitute: d_out[off[i] + x] = symbol x of piece i, a window reference looked up in the window in front of it -------------
+// Elementwise, 16 symbols a thread; nothing at or behind out_cap is written.  A reference into the part of the first window that
+// lies in front of the stream's start is "invalid distance too far back": the piece's index goes to *bad.
+#define SI_SUB_T 256u
+#define SI_SUB_TILE (SI_SUB_T * 16u)
+__global__ void __launch_bounds__(SI_SUB_T) zmi_si_subst_kernel(const uint16_t* __restrict__ sym, uint64_t stride, const uint32_t* __restrict__ len,
+                                                                const uint64_t* __restrict__ off, const uint8_t* __restrict__ win, uint32_t tiles,
+                                                                uint32_t first, uint8_t* __restrict__ out, uint64_t out_cap,
+                                                                unsigned long long* bad) {
+    const uint32_t i = blockIdx.x / tiles, tile = blockIdx.x % tiles;
+    const uint32_t x0 = tile * SI_SUB_TILE + threadIdx.x * 16u;
+    const uint32_t L = len[i];
+    if (x0 >= L) return;
+    const uint64_t o = off[i] + x0;
+    if (o >= out_cap) return;
+    const uint16_t* S = sym + (uint64_t)i * stride + x0;
+    const uint8_t* Wn = win + (uint64_t)i * SI_HIST;
+    const uint64_t T = off[i];   // output in front of the piece: the window's first SI_HIST - T bytes do not exist
+    const uint32_t undef = T >= SI_HIST ? 0u : SI_HIST - (uint32_t)T;
+    const uint4 a = *(const uint4*)S, b = *(const uint4*)(S + 8);
+    const uint32_t h[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    bool far = false;
+#pragma unroll
+    for (uint32_t k = 0; k < 16u; ++k) {
+        uint32_t m = (h[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
+        if (m >= 256u) {
+            uint32_t r = m - 256u;
+            r = r < SI_HIST ? r : SI_HIST - 1u;
+            far |= r < undef && x0 + k < L;
+            m = Wn[r];
+        }
+        w[k >> 2] |= m << (8u * (k & 3u));
+    }
+    if (far) atomicMin(bad, (unsigned long long)(((uint64_t)(first + i) << 40) | ((uint64_t)(first + i) << 8) | SI_D_FAR));
+    const uint32_t cnt = L - x0 < 16u ? L - x0 : 16u;
+    uint8_t* d = out + o;
+    if (cnt == 16u && o + 16u <= out_cap && ((uintptr_t)d & 15u) == 0u) {
+        uint4 q; q.x = w[0]; q.y = w[1]; q.z = w[2]; q.w = w[3];
+        *(uint4*)d = q;
+    } else if (cnt == 16u && o + 16u <= out_cap && ((uintptr_t)d & 3u) == 0u) {
+        for (uint32_t k = 0; k < 4u; ++k) ((uint32_t*)d)[k] = w[k];
+    } else {
+        for (uint32_t k = 0; k < cnt; ++k)
+            if (o + k < out_cap) d[k] = (uint8_t)(w[k >> 2] >> (8u * (k & 3u)));
+    }
+}
+extern "C" int zmi_launch_si_subst(const uint16_t* d_sym, uint64_t stride, const uint32_t* d_len, const uint64_t* d_off, const uint8_t* d_win,
+                                   uint32_t n, uint32_t piece_cap, uint32_t first, uint8_t* d_out, uint64_t out_cap, uint64_t* d_bad,
+                                   hipStream_t stream) {
+    if (n == 0) return 0;
+    const uint32_t tiles = (piece_cap + SI_SUB_TILE - 1u) / SI_SUB_TILE;
+    ZMI_LAUNCH(zmi_si_subst_kernel, dim3(n * tiles), dim3(SI_SUB_T), 0, stream, d_sym, stride, d_len, d_off, d_win, tiles, first, d_out, out_cap,
+               (unsigned long long*)d_bad);
+    return 0;
+}
+
+// ---- wrapper, pieces, verification, trailer --------------------------------------------------------------------------------------
+// hdr words: [0] header length, [1] kind (0 raw, 1 zlib, 2 gzip), [2] status, [3] detail
+static __device__ uint32_t si_crc_byte(uint32_t c, uint32_t b) {
+    c ^= b;
+    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0xEDB88320u & (0u - (c & 1u)));
+    return c;
+}
+// The header state machine of the reference (zlib-rs/src/inflate.rs:927-1275) on one thread: zlib CMF / FLG (method 8, window <=
+// 32 KiB, FCHECK, FDICT -> Z_NEED_DICT), gzip magic, CM 8, reserved flags, MTIME / XFL / OS, FEXTRA, FNAME, FCOMMENT, FHCRC (the low
+// 16 bits of the CRC-32 of the header bytes in front of it).
+__global__ void __launch_bounds__(64) zmi_si_header_kernel(const uint8_t* __restrict__ in, uint64_t n, uint32_t wrap, uint32_t* hdr) {
+    if (threadIdx.x != 0) return;
+    uint32_t kind = wrap, st = 0, det = 0;
+    uint64_t h = 0;
+    if (wrap == 3u) kind = (n >= 2u && in[0] == 0x1Fu && in[1] == 0x8Bu) ? 2u : 1u;
+    if (kind == 1u) {
+        if (n < 2u) { st = (uint32_t)ZMI_BUF_ERROR; det = SI_D_TRUNC; }
+        else {
+            const uint32_t cmf = in[0], flg = in[1];
+            if ((cmf & 15u) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u) { st = (uint32_t)ZMI_DATA_ERROR; det = SI_D_HEADER; }
+            else if (flg & 0x20u) { st = 2u; det = SI_D_DICT; }
+            h = 2u;
+        }
+    } else if (kind == 2u) {
+        if (n < 10u) { st = (uint32_t)ZMI_BUF_ERROR; det = SI_D_TRUNC; }
+        else if (in[0] != 0x1Fu || in[1] != 0x8Bu || in[2] != 8u || (in[3] & 0xE0u)) { st = (uint32_t)ZMI_DATA_ERROR; det = SI_D_HEADER; }
+        else {
+            const uint32_t flg = in[3];
+            h = 10u;
+            bool trunc = false;
+            if (flg & 4u) {
+                if (h + 2u > n) trunc = true;
+                else h += 2u + (in[h] | ((uint32_t)in[h + 1u] << 8));
+            }
+            for (uint32_t f = 8u; f <= 16u && !trunc; f <<= 1)
+                if (flg & f) {
+                    while (h < n && in[h] != 0u) ++h;
+                    if (h >= n) trunc = true; else ++h;
+                }
+            if (!trunc && (flg & 2u)) {
+                if (h + 2u > n) trunc = true;
+                else {
+                    uint32_t c = 0xFFFFFFFFu;
+                    for (uint64_t k = 0; k < h; ++k) c = si_crc_byte(c, in[k]);
+                    c = ~c;
+                    if ((c & 0xFFFFu) != (in[h] | ((uint32_t)in[h + 1u] << 8))) { st = (uint32_t)ZMI_DATA_ERROR; det = SI_D_HEADER; }
+                    h += 2u;
+                }
+            }
+            if (trunc || h > n) { st = (uint32_t)ZMI_BUF_ERROR; det = SI_D_TRUNC; h = n; }
+        }
+    }
+    hdr[0] = (uint32_t)h; hdr[1] = kind; hdr[2] = st; hdr[3] = det;
+}
+
+// piece i of the launch group (global index first + i): input [cut[g], cut[g + 1]) (the last one to the end of the input), its
+// decode region at i * stride; history 32 KiB on trust (none for the first piece of the stream).  Cuts that do not ascend inside the
+// input give an empty piece, which fails verification.
+__global__ void __launch_bounds__(256) zmi_si_setup_kernel(const uint64_t* __restrict__ cuts, uint32_t n_cuts, uint64_t in_len, uint32_t first,
+                                                           uint32_t cnt, uint64_t stride, uint32_t cap, uint64_t* __restrict__ in_off,
+                                                           uint32_t* __restrict__ in_n, uint64_t* __restrict__ out_off, uint32_t* __restrict__ ocap,
+                                                           uint32_t* __restrict__ hist) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= cnt) return;
+    const uint32_t g = first + i;
+    const uint64_t a = cuts[g], b = g + 1u < n_cuts ? cuts[g + 1u] : in_len;
+    in_off[i] = a <= in_len ? a : in_len;
+    in_n[i] = (b > a && b <= in_len && b - a <= 0xFFFFFF00ull) ? (uint32_t)(b - a) : 0u;
+    out_off[i] = (uint64_t)i * stride;
+    ocap[i] = cap;
+    hist[i] = g == 0u ? 0u : SI_HIST;
+}
+
+// The rule of zmi_split_core, per piece: a piece in front of a cut is CLEAN if its decode stopped for want of input exactly at its
+// last byte, on a block boundary, with all its output complete; the last piece must end the deflate data.  len[g] = the piece's
+// output (0 for a piece that failed); the first failure in stream order wins in *bad (piece << 40 | reported index << 8 | kind);
+// the last piece leaves the end of the deflate data in *tail.
+__global__ void __launch_bounds__(256) zmi_si_verify_kernel(const uint64_t* __restrict__ cuts, uint32_t n_cuts, uint32_t first, uint32_t cnt,
+                                                            const uint32_t* __restrict__ in_n, const uint32_t* __restrict__ olen,
+                                                            const int32_t* __restrict__ st, const int32_t* __restrict__ det,
+                                                            const uint32_t* __restrict__ res, uint32_t cap, uint32_t* __restrict__ len,
+                                                            unsigned long long* bad, uint64_t* tail) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= cnt) return;
+    const uint32_t g = first + i;
+    const bool last = g + 1u == n_cuts;
+    uint32_t kind = 0, idx = g;
+    if (in_n[i] == 0u) { kind = SI_D_CUT; idx = g + 1u < n_cuts ? g + 1u : g; }
+    else if (st[i] == ZMI_DATA_ERROR) kind = SI_D_DATA;
+    else if (st[i] == ZMI_BUF_ERROR && det[i] == 2) kind = SI_D_PIECE;
+    else if (olen[i] > cap) kind = SI_D_PIECE;
+    else if (st[i] != ZMI_OK && st[i] != ZMI_BUF_ERROR) kind = SI_D_DATA;
+    else if (last) {
+        if (st[i] != ZMI_OK || res[4u * i + 3u] == 0u) kind = SI_D_TRUNC;
+    } else {
+        const bool clean = st[i] == ZMI_BUF_ERROR && det[i] == 1 && res[4u * i] == in_n[i] && res[4u * i + 1u] == 0u &&
+                           res[4u * i + 2u] == olen[i] && res[4u * i + 3u] == 0u;
+        if (!clean) { kind = SI_D_CUT; idx = g + 1u; }
+    }
+    len[g] = kind ? 0u : olen[i];
+    if (kind) atomicMin(bad, (unsigned long long)(((uint64_t)g << 40) | ((uint64_t)idx << 8) | kind));
+    else if (last) *tail = cuts[g] + res[4u * i] + (res[4u * i + 1u] ? 1u : 0u);
+}
+
+// Thread 0: status / detail / lengths of the call.  Order: the header, the first failed piece, the room, the trailer (zlib: Adler-32
+// big-endian; gzip: CRC-32, then ISIZE = the low 32 bits of the length, little-endian).
+__global__ void __launch_bounds__(64) zmi_si_final_kernel(const uint8_t* __restrict__ in, uint64_t in_len, const uint32_t* __restrict__ hdr,
+                                                          const uint64_t* __restrict__ cut0, const unsigned long long* __restrict__ bad,
+                                                          const uint64_t* __restrict__ tail, const uint64_t* __restrict__ total,
+                                                          const uint32_t* __restrict__ adler, const uint32_t* __restrict__ crc, uint64_t out_cap,
+                                                          int32_t* status, int32_t* detail, uint64_t* out_len, uint64_t* in_used) {
+    if (threadIdx.x != 0) return;
+    const uint32_t kind = hdr[1];
+    int32_t st = (int32_t)hdr[2];
+    uint32_t det = hdr[3];
+    const uint64_t T = *total;
+    uint64_t used = hdr[0];
+    *out_len = T;
+    if (st == 0 && *cut0 != hdr[0]) { st = ZMI_DATA_ERROR; det = SI_D_CUT; }
+    if (st == 0 && *bad != ~0ull) {
+        const uint32_t k = (uint32_t)(*bad & 0xFFu), idx = (uint32_t)((*bad >> 8) & 0xFFFFFFFFull);
+        st = k == SI_D_TRUNC ? ZMI_BUF_ERROR : (k == SI_D_PIECE ? ZMI_BUF_ERROR : ZMI_DATA_ERROR);
+        det = (idx << 8) | k;
+    }
+    if (st == 0 && T > out_cap) { st = ZMI_BUF_ERROR; det = SI_D_OUT; }
+    if (st == 0) {
+        const uint64_t at = *tail;
+        used = at;
+        if (kind == 1u) {
+            if (at + 4u > in_len) { st = ZMI_BUF_ERROR; det = SI_D_TRUNC; }
+            else {
+                const uint32_t v = ((uint32_t)in[at] << 24) | ((uint32_t)in[at + 1u] << 16) | ((uint32_t)in[at + 2u] << 8) | in[at + 3u];
+                if (v != *adler) { st = ZMI_DATA_ERROR; det = SI_D_CHECK; }
+                used = at + 4u;
+            }
+        } else if (kind == 2u) {
+            if (at + 4u > in_len) { st = ZMI_BUF_ERROR; det = SI_D_TRUNC; }
+            else {
+                const uint32_t v = in[at] | ((uint32_t)in[at + 1u] << 8) | ((uint32_t)in[at + 2u] << 16) | ((uint32_t)in[at + 3u] << 24);
+                if (v != *crc) { st = ZMI_DATA_ERROR; det = SI_D_CHECK; }
+                else if (at + 8u > in_len) { st = ZMI_BUF_ERROR; det = SI_D_TRUNC; }
+                else {
+                    const uint32_t z = in[at + 4u] | ((uint32_t)in[at + 5u] << 8) | ((uint32_t)in[at + 6u] << 16) | ((uint32_t)in[at + 7u] << 24);
+                    if (z != (uint32_t)T) { st = ZMI_DATA_ERROR; det = SI_D_LENGTH; }
+                }
+                used = at + 8u;
+            }
+        }
+    }
+    *status = st;
+    *detail = (int32_t)det;
+    *in_used = used;
+}
+
+// ---- proposals of cuts: the byte behind every byte-aligned 00 00 FF FF (the empty stored block of a flush) ---------------------------
+// Pass 1, one workgroup per 4 KiB segment: the first marker that starts in it (~0u: none).  Pass 2, one wave: the greedy walk that
+// keeps proposals at least min_gap apart, segment table first, a segment's bytes only where its first marker lies in front of the
+// position the walk needs.
+#define SI_SEG 4096u
+static __device__ __forceinline__ bool si_marker(const uint8_t* in, uint64_t n, uint64_t m) {
+    return m + 4u < n && in[m] == 0u && in[m + 1u] == 0u && in[m + 2u] == 0xFFu && in[m + 3u] == 0xFFu;
+}
+__global__ void __launch_bounds__(256) zmi_si_seg_kernel(const uint8_t* __restrict__ in, uint64_t n, uint32_t* __restrict__ segfirst) {
+    __shared__ uint32_t best;
+    if (threadIdx.x == 0) best = ~0u;
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * SI_SEG;
+    for (uint32_t k = threadIdx.x * 16u; k < threadIdx.x * 16u + 16u; ++k)
+        if (si_marker(in, n, base + k)) { atomicMin(&best, k); break; }
+    __syncthreads();
+    if (threadIdx.x == 0) segfirst[blockIdx.x] = best;
+}
+__global__ void __launch_bounds__(64) zmi_si_walk_kernel(const uint8_t* __restrict__ in, uint64_t n, const uint32_t* __restrict__ hdr,
+                                                         const uint32_t* __restrict__ segfirst, uint64_t nseg, uint64_t min_gap,
+                                                         uint64_t* __restrict__ cuts, uint32_t cap, uint32_t* n_cuts) {
+    const uint32_t lane = zmi_lane();
+    const uint64_t h = hdr[0];
+    if (lane == 0 && cap) cuts[0] = h;
+    uint32_t cnt = cap ? 1u : 0u;
+    uint64_t last = h;
+    const uint64_t gap = min_gap ? min_gap : 1u;
+    while (cnt < cap) {
+        const uint64_t lo = last + gap > h + 4u ? last + gap - 4u : h;   // a marker at m proposes m + 4
+        uint64_t s = lo / SI_SEG, m = ~0ull;
+        while (s < nseg) {
+            const uint32_t f = segfirst[s];
+            if (f != ~0u) {
+                if (s * SI_SEG + f >= lo) { m = s * SI_SEG + f; break; }
+                // the segment's first marker lies in front of lo (only in lo's own segment): search its bytes from lo
+                const uint64_t end = (s + 1u) * SI_SEG;
+                for (uint64_t b = lo; b < end && m == ~0ull; b += 64u) {
+                    const uint64_t hit = __ballot(b + lane < end && si_marker(in, n, b + lane));
+                    if (hit) m = b + (uint64_t)__ffsll((unsigned long long)hit) - 1u;
+                }
+                if (m != ~0ull) break;
+            }
+            ++s;
+            while (s < nseg) {   // segments without a marker, 64 at a time
+                const uint64_t hit = __ballot(s + lane < nseg && segfirst[s + lane] != ~0u);
+                if (hit) { s += (uint64_t)__ffsll((unsigned long long)hit) - 1u; break; }
+                s += 64u;
+            }
+        }
+        if (m == ~0ull) break;
+        last = m + 4u;
+        if (lane == 0) cuts[cnt] = last;
+        ++cnt;
+    }
+    if (lane == 0) *n_cuts = cnt;
+}
+
+extern "C" int zmi_launch_si_header(const uint8_t* d_in, uint64_t n, uint32_t wrap, uint32_t* d_hdr, hipStream_t stream) {
+    ZMI_LAUNCH(zmi_si_header_kernel, dim3(1), dim3(64), 0, stream, d_in, n, wrap, d_hdr);
+    return 0;
+}
+extern "C" int zmi_launch_si_setup(const uint64_t* d_cuts, uint32_t n_cuts, uint64_t in_len, uint32_t first, uint32_t cnt, uint64_t stride,
+                                   uint32_t cap, uint64_t* d_in_off, uint32_t* d_in_n, uint64_t* d_out_off, uint32_t* d_ocap, uint32_t* d_hist,
+                                   hipStream_t stream) {
+    if (cnt == 0) return 0;
+    ZMI_LAUNCH(zmi_si_setup_kernel, dim3((cnt + 255u) / 256u), dim3(256), 0, stream, d_cuts, n_cuts, in_len, first, cnt, stride, cap, d_in_off,
+               d_in_n, d_out_off, d_ocap, d_hist);
+    return 0;
+}
+extern "C" int zmi_launch_si_verify(const uint64_t* d_cuts, uint32_t n_cuts, uint32_t first, uint32_t cnt, const uint32_t* d_in_n,
+                                    const uint32_t* d_olen, const int32_t* d_st, const int32_t* d_det, const uint32_t* d_res, uint32_t cap,
+                                    uint32_t* d_len, uint64_t* d_bad, uint64_t* d_tail, hipStream_t stream) {
+    if (cnt == 0) return 0;
+    ZMI_LAUNCH(zmi_si_verify_kernel, dim3((cnt + 255u) / 256u), dim3(256), 0, stream, d_cuts, n_cuts, first, cnt, d_in_n, d_olen, d_st, d_det,
+               d_res, cap, d_len, (unsigned long long*)d_bad, d_tail);
+    return 0;
+}
+extern "C" int zmi_launch_si_final(const uint8_t* d_in, uint64_t in_len, const uint32_t* d_hdr, const uint64_t* d_cut0, const uint64_t* d_bad,
+                                   const uint64_t* d_tail, const uint64_t* d_total, const uint32_t* d_adler, const uint32_t* d_crc, uint64_t out_cap,
+                                   int32_t* d_status, int32_t* d_detail, uint64_t* d_out_len, uint64_t* d_in_used, hipStream_t stream) {
+    ZMI_LAUNCH(zmi_si_final_kernel, dim3(1), dim3(64), 0, stream, d_in, in_len, d_hdr, d_cut0, (const unsigned long long*)d_bad, d_tail, d_total,
+               d_adler, d_crc, out_cap, d_status, d_detail, d_out_len, d_in_used);
+    return 0;
+}
+extern "C" int zmi_launch_si_find_cuts(const uint8_t* d_in, uint64_t n, const uint32_t* d_hdr, uint32_t* d_seg, uint64_t min_gap, uint64_t* d_cuts,
+                                       uint32_t cap, uint32_t* d_n_cuts, hipStream_t stream) {
+    const uint64_t nseg = (n + SI_SEG - 1u) / SI_SEG;
+    if (nseg) ZMI_LAUNCH(zmi_si_seg_kernel, dim3((uint32_t)nseg), dim3(256), 0, stream, d_in, n, d_seg);
+    ZMI_LAUNCH(zmi_si_walk_kernel, dim3(1), dim3(64), 0, stream, d_in, n, d_hdr, (const uint32_t*)d_seg, nseg, min_gap, d_cuts, cap, d_n_cuts);
+    return 0;
+}
+// what of piece i lies inside out_cap (the checksum pass reads only that)
+__global__ void __launch_bounds__(256) zmi_si_clamp_kernel(const uint32_t* __restrict__ len, const uint64_t* __restrict__ off, uint32_t n,
+                                                           uint64_t out_cap, uint32_t* __restrict__ clen) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t o = off[i];
+    clen[i] = o >= out_cap ? 0u : (out_cap - o < len[i] ? (uint32_t)(out_cap - o) : len[i]);
+}
+extern "C" int zmi_launch_si_clamp(const uint32_t* d_len, const uint64_t* d_off, uint32_t n, uint64_t out_cap, uint32_t* d_clen, hipStream_t stream) {
+    if (n == 0) return 0;
+    ZMI_LAUNCH(zmi_si_clamp_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_len, d_off, n, out_cap, d_clen);
+    return 0;
+}

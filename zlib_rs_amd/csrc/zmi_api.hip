@@ -104,6 +104,7 @@ struct zmi_ctx {
     hipEvent_t ev_fork{}, ev_join{};
     zmi_buf sd_meta, sd_slots;          // zmi_deflate_stream_dev: per-piece tables / one launch group's output slots
     zmi_buf comb;                       // zmi_checksum_combine_dev: the per-workgroup partial folds
+    zmi_buf si_meta, si_work, si_seg;   // zmi_inflate_stream_dev: per-piece tables / one launch group's regions; find_cuts' segment table
 };
 
 static int zmi_reserve(zmi_buf& b, size_t bytes) {
@@ -155,6 +156,9 @@ extern "C" int zmi_ctx_destroy(zmi_ctx* c) {
     if (c->sd_meta.p) (void)hipFree(c->sd_meta.p);
     if (c->sd_slots.p) (void)hipFree(c->sd_slots.p);
     if (c->comb.p) (void)hipFree(c->comb.p);
+    if (c->si_meta.p) (void)hipFree(c->si_meta.p);
+    if (c->si_work.p) (void)hipFree(c->si_work.p);
+    if (c->si_seg.p) (void)hipFree(c->si_seg.p);
     for (int k = 0; k < 2; ++k) if (c->st_pin[k].p) (void)hipHostFree(c->st_pin[k].p);
     if (c->st_pin_ev_live) { (void)hipEventDestroy(c->st_pin_ev[0]); (void)hipEventDestroy(c->st_pin_ev[1]); }
     if (c->hb_live) {
@@ -1965,5 +1969,147 @@ extern "C" int zmi_inflate_resume(zmi_ctx* c, const uint8_t* in, uint32_t in_len
         const int crc = zmi_d2h(c, out, (const uint8_t*)c->st_out.p + base, n, hs);
         if (crc) return crc;
     }
+    return ZMI_E_OK;
+}
+
+// ---- single-stream inflate (pigz-style): the inverse of zmi_deflate_stream_dev ------------------------------------------------------
+// Per launch group of pieces, all on `stream`, no host synchronisation: layout from the cuts -> decode (raw, 32 KiB of history on
+// trust) -> cut verification -> output offsets (scan from the device word the previous group ended at) -> symbolic resolve ->
+// window scan (carrying the window into the next group) -> substitute into d_out -> per-piece checks.  Then the combine of the
+// checks and the trailer.  Stages and their reasons: inflate.hip, "single-stream inflate"; DESIGN.md section 13.
+#define ZMI_SI_CH 1024u       // region granularity (SI_CH in inflate.hip)
+#define ZMI_SI_WIN 32768u
+#define ZMI_SI_B 64u          // pieces per block of the window scan
+#define ZMI_SI_SLACK 4096u
+extern "C" int zmi_inflate_stream_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, int wrap, const uint64_t* d_cuts, uint32_t n_cuts,
+                                      uint32_t piece_out_max, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used,
+                                      int32_t* d_status, int32_t* d_detail, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_AUTO) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip/auto");
+    if (n_cuts == 0 || !d_cuts) return zmi_fail(ZMI_E_ARG, "zmi_inflate_stream_dev: at least one cut (the end of the header)");
+    if (piece_out_max == 0 || piece_out_max > (1u << 30)) return zmi_fail(ZMI_E_ARG, "piece_out_max must be 1 .. 2^30");
+    if ((in_len && !d_in) || (out_cap && !d_out) || !d_out_len || !d_in_used || !d_status || !d_detail) return zmi_fail(ZMI_E_ARG, "null argument");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    const uint64_t stride = ((uint64_t)piece_out_max + ZMI_SI_CH - 1u) & ~(uint64_t)(ZMI_SI_CH - 1u);
+    // per piece: decode bytes + symbols + its window + bitmap and tables; per block of the scan: a map and a window
+    const uint64_t per = stride * 3u + ZMI_SI_WIN + stride / 8u + 128u + (3u * ZMI_SI_WIN) / ZMI_SI_B + 64u;
+    uint64_t group = c->scratch_limit / per;
+    if (const char* gv = zmi_tune("ZMI_STREAM_GROUP")) if (atoll(gv) > 0) group = (uint64_t)atoll(gv);
+    if (group == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one piece");
+    if (group > n_cuts) group = n_cuts;
+    const uint32_t G = (uint32_t)group, nblk = (G + ZMI_SI_B - 1u) / ZMI_SI_B;
+    const size_t n = n_cuts;
+    // per-call tables: off u64[n + 1] | bad u64 | tail u64 | len u32[n] | clen u32[n] | adler u32[n] | crc u32[n] | hdr u32[4] |
+    // combined checks u32[2] | carried window
+    const size_t m_off = 0, m_bad = 8 * (n + 1), m_tail = m_bad + 8, m_len = m_tail + 8, m_clen = m_len + 4 * n, m_adler = m_clen + 4 * n,
+                 m_crc = m_adler + 4 * n, m_hdr = m_crc + 4 * n, m_chk = m_hdr + 16, m_carry = (m_chk + 8 + 15) & ~(size_t)15,
+                 meta_bytes = m_carry + ZMI_SI_WIN;
+    // launch group: in_off u64 | out_off u64 | in_n | ocap | hist | olen | st | used | det (u32[G] each) | res u32[4G] | agg u16[nblk * 32 Ki] |
+    // wstart | win | sym | dec
+    const size_t g = G;
+    const size_t w_ioff = 0, w_ooff = 8 * g, w_in = 16 * g, w_cap = w_in + 4 * g, w_hist = w_cap + 4 * g, w_olen = w_hist + 4 * g, w_st = w_olen + 4 * g,
+                 w_used = w_st + 4 * g, w_det = w_used + 4 * g, w_res = w_det + 4 * g, w_agg = (w_res + 16 * g + 255) & ~(size_t)255,
+                 w_wst = w_agg + (size_t)nblk * ZMI_SI_WIN * 2u, w_win = w_wst + (size_t)nblk * ZMI_SI_WIN, w_sym = w_win + g * ZMI_SI_WIN,
+                 w_dec = w_sym + g * stride * 2u + ZMI_SI_SLACK, work_bytes = w_dec + g * stride + ZMI_SI_SLACK;
+    int rc = zmi_reserve(c->si_meta, meta_bytes);
+    if (!rc) rc = zmi_reserve(c->si_work, work_bytes);
+    if (rc) return rc;
+    uint8_t* M = (uint8_t*)c->si_meta.p;
+    uint8_t* W = (uint8_t*)c->si_work.p;
+    uint64_t* d_off = (uint64_t*)(M + m_off);
+    uint64_t* d_bad = (uint64_t*)(M + m_bad);
+    uint64_t* d_tail = (uint64_t*)(M + m_tail);
+    uint32_t* d_len = (uint32_t*)(M + m_len);
+    uint32_t* d_clen = (uint32_t*)(M + m_clen);
+    uint32_t* d_adler = (uint32_t*)(M + m_adler);
+    uint32_t* d_crc = (uint32_t*)(M + m_crc);
+    uint32_t* d_hdr = (uint32_t*)(M + m_hdr);
+    uint32_t* d_chk = (uint32_t*)(M + m_chk);
+    uint8_t* d_carry = M + m_carry;
+    uint16_t* d_sym = (uint16_t*)(W + w_sym);
+    uint8_t* d_dec = W + w_dec;
+    ZMI_HIP(hipMemsetAsync(d_off, 0, 8, stream));
+    ZMI_HIP(hipMemsetAsync(d_bad, 0xFF, 8, stream));
+    ZMI_HIP(hipMemsetAsync(d_tail, 0, 8, stream));
+    ZMI_HIP(hipMemsetAsync(d_chk, 0, 8, stream));
+    ZMI_HIP(hipMemsetAsync(d_carry, 0, ZMI_SI_WIN, stream));
+    {
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_si_header((const uint8_t*)d_in, in_len, (uint32_t)wrap, d_hdr, stream);
+    }
+    // the decode's bitmap covers one group's regions
+    const uint64_t saved_limit = c->inflate_out_limit;
+    c->inflate_out_limit = group * stride + (1ull << 16);
+    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; } } restore_limit{c, saved_limit};
+    const uint32_t kind = wrap == ZMI_WRAP_ZLIB ? 1u : (wrap == ZMI_WRAP_GZIP ? 2u : (wrap == ZMI_WRAP_AUTO ? 3u : 0u));
+    for (uint64_t first = 0; first < n; first += group) {
+        const uint32_t cnt = (uint32_t)(n - first < group ? n - first : group);
+        const uint32_t f = (uint32_t)first;
+        {
+            zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+            zmi_launch_si_setup(d_cuts, n_cuts, in_len, f, cnt, stride, piece_out_max, (uint64_t*)(W + w_ioff), (uint32_t*)(W + w_in),
+                                (uint64_t*)(W + w_ooff), (uint32_t*)(W + w_cap), (uint32_t*)(W + w_hist), stream);
+        }
+        rc = zmi_inflate_impl(c, d_in, (const uint64_t*)(W + w_ioff), (const uint32_t*)(W + w_in), cnt, ZMI_WRAP_RAW, d_dec, (const uint64_t*)(W + w_ooff),
+                              (const uint32_t*)(W + w_cap), (const uint32_t*)(W + w_hist), (uint32_t*)(W + w_olen), (int32_t*)(W + w_st),
+                              (uint32_t*)(W + w_used), (int32_t*)(W + w_det), nullptr, (uint32_t*)(W + w_res), stream_, true);
+        if (rc) return rc;
+        {
+            zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+            zmi_launch_si_verify(d_cuts, n_cuts, f, cnt, (const uint32_t*)(W + w_in), (const uint32_t*)(W + w_olen), (const int32_t*)(W + w_st),
+                                 (const int32_t*)(W + w_det), (const uint32_t*)(W + w_res), piece_out_max, d_len, d_bad, d_tail, stream);
+        }
+        {
+            zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+            zmi_launch_scan_sizes_base(d_len + f, cnt, d_off + f, d_off + f, stream);
+        }
+        {
+            zmi_scope_timer tm(c, ZMI_K_RESOLVE, stream);
+            zmi_launch_si_resolve(d_dec, stride, d_len + f, piece_out_max, cnt, (const uint64_t*)c->inf_bm.p, (const uint64_t*)c->inf_tmp.p, d_sym, stream);
+        }
+        {
+            zmi_scope_timer tm(c, ZMI_K_PARSE, stream);   // (the window scan; an inflate call runs no cost parse)
+            zmi_launch_si_window_scan(d_sym, stride, d_len + f, cnt, ZMI_SI_B, (uint16_t*)(W + w_agg), d_carry, W + w_wst, W + w_win, stream);
+        }
+        {
+            zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+            zmi_launch_si_subst(d_sym, stride, d_len + f, d_off + f, W + w_win, cnt, piece_out_max, f, (uint8_t*)d_out, out_cap, d_bad, stream);
+            zmi_launch_si_clamp(d_len + f, d_off + f, cnt, out_cap, d_clen + f, stream);
+        }
+        if (kind) {
+            zmi_scope_timer tm(c, ZMI_K_CHECKSUM, stream);
+            zmi_launch_checksum((const uint8_t*)d_out, d_off + f, d_clen + f, cnt, kind, d_adler + f, d_crc + f, stream);
+        }
+        ZMI_HIP(hipGetLastError());
+    }
+    if (kind == 1u || kind == 3u) { rc = zmi_checksum_combine_dev(c, ZMI_WRAP_ZLIB, d_adler, d_clen, 1u, n_cuts, d_chk, nullptr, stream_); if (rc) return rc; }
+    if (kind == 2u || kind == 3u) { rc = zmi_checksum_combine_dev(c, ZMI_WRAP_GZIP, d_crc, d_clen, 1u, n_cuts, d_chk + 1, nullptr, stream_); if (rc) return rc; }
+    {
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_si_final((const uint8_t*)d_in, in_len, d_hdr, d_cuts, d_bad, d_tail, d_off + n, d_chk, d_chk + 1, out_cap, d_status, d_detail,
+                            d_out_len, d_in_used, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+extern "C" int zmi_stream_find_cuts_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, int wrap, uint64_t min_gap, uint64_t* d_cuts, uint32_t cap,
+                                        uint32_t* d_n_cuts, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_AUTO) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip/auto");
+    if ((in_len && !d_in) || (cap && !d_cuts) || !d_n_cuts) return zmi_fail(ZMI_E_ARG, "null argument");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    const uint64_t nseg = (in_len + 4095u) / 4096u;
+    int rc = zmi_reserve(c->si_seg, 16u + (size_t)nseg * 4u);
+    if (rc) return rc;
+    uint32_t* d_hdr = (uint32_t*)c->si_seg.p;
+    {
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_si_header((const uint8_t*)d_in, in_len, (uint32_t)wrap, d_hdr, stream);
+        zmi_launch_si_find_cuts((const uint8_t*)d_in, in_len, d_hdr, d_hdr + 4, min_gap, d_cuts, cap, d_n_cuts, stream);
+    }
+    ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;
 }

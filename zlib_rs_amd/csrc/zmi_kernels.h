@@ -112,4 +112,27 @@ int zmi_launch_resolve_jump_segments(uint8_t* d_fin, const uint64_t* d_soff, uin
 int zmi_launch_inflate_resolve(uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_len, uint32_t n_streams,
                                const uint64_t* d_bitmap, const uint64_t* d_bm_off, const uint32_t* d_out_hist,
                                const uint32_t* d_order, hipStream_t stream);
+// single-stream inflate (inflate.hip): header, piece layout from the cuts, cut verification, symbolic resolve, window scan,
+// substitute, trailer; proposals of cuts
+int zmi_launch_si_header(const uint8_t* d_in, uint64_t n, uint32_t wrap, uint32_t* d_hdr, hipStream_t stream);
+int zmi_launch_si_setup(const uint64_t* d_cuts, uint32_t n_cuts, uint64_t in_len, uint32_t first, uint32_t cnt, uint64_t stride,
+                        uint32_t cap, uint64_t* d_in_off, uint32_t* d_in_n, uint64_t* d_out_off, uint32_t* d_ocap, uint32_t* d_hist,
+                        hipStream_t stream);
+int zmi_launch_si_verify(const uint64_t* d_cuts, uint32_t n_cuts, uint32_t first, uint32_t cnt, const uint32_t* d_in_n,
+                         const uint32_t* d_olen, const int32_t* d_st, const int32_t* d_det, const uint32_t* d_res, uint32_t cap,
+                         uint32_t* d_len, uint64_t* d_bad, uint64_t* d_tail, hipStream_t stream);
+int zmi_launch_si_resolve(const uint8_t* d_dec, uint64_t stride, const uint32_t* d_out_len, uint32_t cap, uint32_t n,
+                          const uint64_t* d_bitmap, const uint64_t* d_bm_off, uint16_t* d_sym, hipStream_t stream);
+uint32_t zmi_si_scan_blocks(uint32_t n, uint32_t B);
+int zmi_launch_si_window_scan(const uint16_t* d_sym, uint64_t stride, const uint32_t* d_len, uint32_t n, uint32_t B, uint16_t* d_agg,
+                              uint8_t* d_carry, uint8_t* d_wstart, uint8_t* d_win, hipStream_t stream);
+int zmi_launch_si_subst(const uint16_t* d_sym, uint64_t stride, const uint32_t* d_len, const uint64_t* d_off, const uint8_t* d_win,
+                        uint32_t n, uint32_t piece_cap, uint32_t first, uint8_t* d_out, uint64_t out_cap, uint64_t* d_bad,
+                        hipStream_t stream);
+int zmi_launch_si_final(const uint8_t* d_in, uint64_t in_len, const uint32_t* d_hdr, const uint64_t* d_cut0, const uint64_t* d_bad,
+                        const uint64_t* d_tail, const uint64_t* d_total, const uint32_t* d_adler, const uint32_t* d_crc, uint64_t out_cap,
+                        int32_t* d_status, int32_t* d_detail, uint64_t* d_out_len, uint64_t* d_in_used, hipStream_t stream);
+int zmi_launch_si_clamp(const uint32_t* d_len, const uint64_t* d_off, uint32_t n, uint64_t out_cap, uint32_t* d_clen, hipStream_t stream);
+int zmi_launch_si_find_cuts(const uint8_t* d_in, uint64_t n, const uint32_t* d_hdr, uint32_t* d_seg, uint64_t min_gap, uint64_t* d_cuts,
+                            uint32_t cap, uint32_t* d_n_cuts, hipStream_t stream);
 }

@@ -14,6 +14,8 @@ from . import _lib
 
 WRAP_RAW, WRAP_ZLIB, WRAP_GZIP, WRAP_AUTO = 0, 1, 2, 3
 GEN_SEED = 0x5A4C4942
+# zmi_inflate_stream_dev detail kinds (include/zmi355.h ZMI_SI_*)
+SI_CUT, SI_PIECE, SI_OUT = 3, 4, 9
 
 
 def _stream_ptr():
@@ -174,6 +176,54 @@ class Engine:
         if status != 0:
             raise RuntimeError("zmi_deflate_stream_dev: status %d (stream of %d bytes, room for %d)" % (status, length, out.numel()))
         return (out[:length], idx) if index else out[:length]
+
+    def find_cuts(self, data, wrap=WRAP_AUTO, min_gap=1 << 16, cap=None):
+        """Proposed piece starts of a stream with flush points (the end of the header, then the byte behind every byte-aligned
+        00 00 FF FF, at least min_gap bytes apart): an int64 device tensor.  One synchronisation, for the count."""
+        n = int(data.numel())
+        if cap is None:
+            cap = max(2, n // max(1, int(min_gap)) + 2)
+        cuts = torch.zeros(cap, dtype=torch.int64, device=self.device)
+        cnt = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.check(self.L.zmi_stream_find_cuts_dev(self._ctx, data.data_ptr() if n else None, n, int(wrap), int(min_gap), cuts.data_ptr(),
+                                                   int(cap), cnt.data_ptr(), _stream_ptr()), "zmi_stream_find_cuts_dev")
+        return cuts[:int(cnt.item())]
+
+    def inflate_stream(self, data, wrap=WRAP_AUTO, index=None, piece_out_max=1 << 20, out=None, out_cap=None):
+        """One raw / zlib / gzip stream with flush points (deflate_stream's output, pigz) -> (uint8 view of the output, in_used).
+        index: the piece starts (deflate_stream's index without its last entry, or find_cuts'); None runs find_cuts.  A cut that does
+        not verify is dropped and the call runs again; a piece above piece_out_max doubles it; an output above the room of `out`
+        (default: out_cap bytes, or 4x the input + 1 MiB) is decoded again into a buffer of the size the device reported.  Data
+        errors raise with the status."""
+        n = int(data.numel())
+        cuts = self.find_cuts(data, wrap) if index is None else index.to(torch.int64)
+        pom = int(piece_out_max)
+        if out is None:
+            out = torch.empty(int(out_cap) if out_cap is not None else 4 * n + (1 << 20), dtype=torch.uint8, device=self.device)
+        meta = torch.zeros(3, dtype=torch.int64, device=self.device)   # out_len | in_used | status, detail (int32)
+        tries = int(cuts.numel()) + 64
+        for _ in range(tries):
+            meta.zero_()
+            _lib.check(self.L.zmi_inflate_stream_dev(self._ctx, data.data_ptr() if n else None, n, int(wrap), cuts.data_ptr(),
+                                                     int(cuts.numel()), pom, out.data_ptr(), int(out.numel()), meta.data_ptr(),
+                                                     meta.data_ptr() + 8, meta.data_ptr() + 16, meta.data_ptr() + 20, _stream_ptr()),
+                       "zmi_inflate_stream_dev")
+            olen, used, sd = meta.tolist()
+            st = sd & 0xFFFFFFFF
+            st = st - (1 << 32) if st >= 1 << 31 else st
+            det = (sd >> 32) & 0xFFFFFFFF
+            kind, at = det & 0xFF, det >> 8
+            if st == 0:
+                return out[:olen], used
+            if kind == SI_CUT and 0 < at < cuts.numel():
+                cuts = torch.cat([cuts[:at], cuts[at + 1:]])
+            elif kind == SI_PIECE and pom < (1 << 30):
+                pom = min(pom * 2, 1 << 30)
+            elif kind == SI_OUT:
+                out = torch.empty(olen, dtype=torch.uint8, device=self.device)
+            else:
+                raise RuntimeError("zmi_inflate_stream_dev: status %d detail %d (kind %d, index %d)" % (st, det, kind, at))
+        raise RuntimeError("zmi_inflate_stream_dev: no result after %d attempts" % tries)
 
     def deflate_pieces(self, data, offsets, lengths, max_len, level=6, strategy=0, wrap=WRAP_GZIP, independent=True, final=True):
         """One rank's pieces of a single stream: (slots [n, stride] uint8, sizes int32 [n], checks int32 [n], status int32 [n])."""

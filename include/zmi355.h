@@ -328,6 +328,34 @@ int zmi_inflate_stream_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, int 
 int zmi_stream_find_cuts_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, int wrap, uint64_t min_gap, uint64_t* d_cuts, uint32_t cap,
                              uint32_t* d_n_cuts, void* stream);
 
+/* ---- single-stream inflate of streams WITHOUT flush points (what gzip, zlib and zlib-rs write at their default settings) ----------
+ * zmi_stream_find_blocks_dev   the shape of zmi_stream_find_cuts_dev, but the entries are BIT offsets into d_in: d_cuts[0] = 8 x the
+ *                              end of the header; every further entry is the first of the three header bits of a DYNAMIC block, found
+ *                              by trying every bit position (csrc/blockscan.hip: a plausible header, then code lengths that decode
+ *                              exactly).  Greedy and exact: entry k + 1 is the smallest position found >= d_cuts[k] + 8 x max(min_gap, 1);
+ *                              ascending, at most cap entries, *d_n_cuts = entries written, the same entries on every run.  Any in_len
+ *                              (the stream is scanned in windows of 64 MiB, positions are 64-bit), asynchronous on `stream`, no host
+ *                              synchronisation.  Scratch of the context: about 9 / 16 of min(in_len, 64 MiB).  Overflow: 2 KiB of input
+ *                              in which more than one bit position in 64 looks like a header (ordinary data: one in ~250) proposes
+ *                              nothing; a window with more than one block per 64 bytes keeps its first ones.  Never an unvalidated entry.
+ *                              NOT found: fixed and stored blocks -- three header bits prove nothing; they ride along in the piece of the
+ *                              dynamic block in front of them.  So a stream of only such blocks (level-1 output of some encoders, level
+ *                              0) is ONE piece, bounded by piece_out_max <= 2^30 bytes of output.  A proposal may be false (a stored
+ *                              block that holds a deflate stream): the verification below catches it.
+ * zmi_inflate_stream_bits_dev  zmi_inflate_stream_dev with d_cuts in BITS: piece g starts at bit d_cuts[g] & 7 of byte d_cuts[g] >> 3 and
+ *                              reads up to the byte that holds the next cut.  d_cuts[0] must be 8 x the end of the header.  A cut counts
+ *                              if the decode in front of it stopped for want of input in a block that starts exactly at that bit; the few
+ *                              bits it saw behind the cut produce nothing that is kept.  Status, ZMI_SI_* details, indices, *d_out_len,
+ *                              *d_in_used, out_cap and the independence of the scratch limit are those of zmi_inflate_stream_dev; with
+ *                              cuts 8 x c[k] it writes the same four words and the same bytes as zmi_inflate_stream_dev with c[k].
+ *                              Proposals of both kinds may be mixed (8 x find_cuts' entries merged with find_blocks').
+ *                              One member per call; *d_in_used points at the next. */
+int zmi_stream_find_blocks_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, int wrap, uint64_t min_gap, uint64_t* d_cuts, uint32_t cap,
+                               uint32_t* d_n_cuts, void* stream);
+int zmi_inflate_stream_bits_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, int wrap, const uint64_t* d_cuts, uint32_t n_cuts,
+                                uint32_t piece_out_max, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used,
+                                int32_t* d_status, int32_t* d_detail, void* stream);
+
 /* ---- host-buffer convenience wrappers: copy in, run the batch on the GPU, copy back ---- */
 int zmi_deflate_batch(zmi_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_shards,
                       int level, int strategy, int wrap, uint8_t* out, uint64_t out_stride, uint32_t* out_len,

@@ -114,15 +114,11 @@ static __device__ bool bs_validate(const uint8_t* __restrict__ in, uint32_t n, u
     return true;
 }
 
-// Stage 1: thread g looks at the 64 bit positions [64 g, 64 g + 64) of in[0 .. n); positions below first_bit are skipped.
-// pre[] receives the positions that pass (any order), *pre_count their number (may exceed pre_cap: the list is then incomplete
-// and the caller falls back to the serial decode).  Stage 2 runs as a launch of its own, one lane per survivor: inside this
-// loop a survivor's ~300-symbol walk would hold the other 63 lanes of its wave (measured: 3.4 ms of a 6.6 MB stream's scan).
-__global__ void __launch_bounds__(BS_T) zmi_block_scan_kernel(const uint8_t* __restrict__ in, uint32_t n, uint64_t first_bit,
-                                                               uint32_t* __restrict__ pre, uint32_t pre_cap, uint32_t* __restrict__ pre_count) {
-    const uint64_t g = (uint64_t)blockIdx.x * BS_T + threadIdx.x;
+// Stage 1 for thread g: the 64 bit positions [64 g, 64 g + 64) of in[0 .. n); positions below first_bit or at / behind end_bit
+// are skipped.  Bit i of the result: position 64 g + i passed.
+static __device__ __forceinline__ uint64_t bs_stage1(const uint8_t* __restrict__ in, uint32_t n, uint64_t g, uint64_t first_bit, uint64_t end_bit) {
     const uint64_t p0 = g * 64u;
-    const bool live = p0 < 8ull * n;   // (no early return: the wave hands its survivors in together, below)
+    const bool live = p0 < 8ull * n;   // (no early return: the caller's wave hands its survivors in together)
     // 24 bytes behind the thread's first position: 64 positions + 74 header bits
     const uint32_t b0 = live ? (uint32_t)(p0 >> 3) : 0u;
     uint64_t q[3];
@@ -141,7 +137,7 @@ __global__ void __launch_bounds__(BS_T) zmi_block_scan_kernel(const uint8_t* __r
     uint64_t mine = 0ull;   // bit i: position p0 + i passed
     for (uint32_t i = 0; i < 64u; ++i) {
         const uint64_t pos = p0 + i;
-        if (!live || pos < first_bit || pos + 17u + 12u > 8ull * n) continue;
+        if (!live || pos < first_bit || pos >= end_bit || pos + 17u + 12u > 8ull * n) continue;
         // 128 bits starting at position i of the 192 loaded
         const uint64_t lo = i ? (q[0] >> i) | (q[1] << (64u - i)) : q[0];
         const uint64_t hi = i ? (q[1] >> i) | (q[2] << (64u - i)) : q[1];
@@ -160,6 +156,18 @@ __global__ void __launch_bounds__(BS_T) zmi_block_scan_kernel(const uint8_t* __r
         if (kraft != 128u) continue;
         mine |= 1ull << i;
     }
+    return mine;
+}
+
+// Stage 1: thread g looks at the 64 bit positions [64 g, 64 g + 64) of in[0 .. n); positions below first_bit are skipped.
+// pre[] receives the positions that pass (any order), *pre_count their number (may exceed pre_cap: the list is then incomplete
+// and the caller falls back to the serial decode).  Stage 2 runs as a launch of its own, one lane per survivor: inside this
+// loop a survivor's ~300-symbol walk would hold the other 63 lanes of its wave (measured: 3.4 ms of a 6.6 MB stream's scan).
+__global__ void __launch_bounds__(BS_T) zmi_block_scan_kernel(const uint8_t* __restrict__ in, uint32_t n, uint64_t first_bit,
+                                                               uint32_t* __restrict__ pre, uint32_t pre_cap, uint32_t* __restrict__ pre_count) {
+    const uint64_t g = (uint64_t)blockIdx.x * BS_T + threadIdx.x;
+    const uint64_t p0 = g * 64u;
+    uint64_t mine = bs_stage1(in, n, g, first_bit, ~0ull);
     // One atomic per WAVE (4096 positions, ~8 survivors), not per survivor: some 100 000 atomic adds on this one word, one after the
     // other at the L2, were most of what this kernel took (0.56 ms for a 6.6 MB stream).
     const uint32_t c = (uint32_t)__popcll((unsigned long long)mine);
@@ -202,5 +210,136 @@ extern "C" int zmi_launch_block_scan(const uint8_t* d_in, uint32_t n, uint64_t f
                d_count + 3);
     ZMI_LAUNCH(zmi_block_validate_kernel, dim3((pre_cap + BS_T - 1u) / BS_T), dim3(BS_T), 0, stream, d_in, n, (const uint32_t*)d_pre, pre_cap,
                (const uint32_t*)(d_count + 3), d_list, cap, d_count);
+    return 0;
+}
+
+// ==== the scan for zmi_stream_find_blocks_dev: any length, proposals in stream order, nothing left to the order of atomics =========
+// The stream is taken in WINDOWS of up to 2^28 bytes (64 MiB in the product): a window's kernels see the window and BS_LOOK bytes
+// behind it (a dynamic header is at most 17 + 57 + 316 * 14 bits = 563 bytes long, so what they accept does not depend on where
+// the windows lie), work with 32-bit positions relative to the window, and the walk adds the window's first bit.  Per window:
+//   scan      one workgroup per 2 KiB (16 384 positions): the stage-1 survivors of the workgroup, ascending, in its own slot of
+//             BS_SLOT entries (a prefix sum over the threads' counts gives every survivor its place);
+//   validate  one lane per slot entry (stage 2, bs_validate): the entries that pass, ascending, back into the slot;
+//   offsets   the prefix sum of the slots' counts (zmi_launch_scan_sizes, pack.hip);
+//   gather    the slots back to back: the window's validated positions as one ascending list;
+//   walk      one wave: the greedy choice, 64 entries of the list a step, continuing from the last entry of d_cuts.
+// OVERFLOW: a workgroup with more than BS_SLOT stage-1 survivors (one position in 64; ordinary compressed data leaves one in
+// ~250) proposes nothing for its 2 KiB; a window with more than vcap validated positions keeps the first vcap of them.
+#define BS_SLOT 256u
+#define BS_LOOK 4096u
+static_assert(BS_SLOT == BS_T, "validate: one lane per slot entry");
+
+__global__ void __launch_bounds__(BS_T) zmi_block_scan_ord_kernel(const uint8_t* __restrict__ in, uint32_t n, uint64_t base_bit, uint32_t own_bits,
+                                                                   const uint32_t* __restrict__ hdr, uint32_t* __restrict__ slots,
+                                                                   uint32_t* __restrict__ cnt) {
+    __shared__ uint32_t wsum[BS_T / 64u];
+    // the first block needs no finding: the scan starts behind its three header bits
+    const uint64_t first_abs = 8ull * hdr[0] + 3u;
+    const uint64_t first_bit = first_abs > base_bit ? first_abs - base_bit : 0ull;
+    const uint64_t g = (uint64_t)blockIdx.x * BS_T + threadIdx.x;
+    uint64_t mine = bs_stage1(in, n, g, first_bit, own_bits);
+    const uint32_t c = (uint32_t)__popcll((unsigned long long)mine);
+    const uint32_t incl = zmi_wave_incl_scan(c);
+    if (zmi_lane() == 63u) wsum[zmi_wave()] = incl;
+    __syncthreads();
+    uint32_t k = incl - c, total = 0u;
+    for (uint32_t w = 0; w < BS_T / 64u; ++w) {
+        if (w < zmi_wave()) k += wsum[w];
+        total += wsum[w];
+    }
+    uint32_t* slot = slots + (uint64_t)blockIdx.x * BS_SLOT;
+    while (mine) {
+        const uint32_t i = (uint32_t)__ffsll((unsigned long long)mine) - 1u;
+        mine &= mine - 1ull;
+        if (k < BS_SLOT) slot[k] = (uint32_t)(g * 64u + i);
+        ++k;
+    }
+    if (threadIdx.x == 0u) cnt[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(BS_T) zmi_block_validate_ord_kernel(const uint8_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ slots,
+                                                                       const uint32_t* __restrict__ cnt, uint32_t* __restrict__ vcnt) {
+    __shared__ uint32_t wsum[BS_T / 64u];
+    const uint32_t t = threadIdx.x;
+    uint32_t* slot = slots + (uint64_t)blockIdx.x * BS_SLOT;
+    const uint32_t have = cnt[blockIdx.x];
+    const bool mine = have <= BS_SLOT && t < have;   // (a slot that overflowed proposes nothing)
+    const uint32_t pos = mine ? slot[t] : 0u;
+    const bool ok = mine && bs_validate(in, n, pos);
+    const uint64_t m = __ballot(ok);
+    if (zmi_lane() == 0u) wsum[zmi_wave()] = (uint32_t)__popcll((unsigned long long)m);
+    __syncthreads();   // (every entry has been read: the slot may be overwritten)
+    uint32_t k = zmi_mbcnt(m), total = 0u;
+    for (uint32_t w = 0; w < BS_T / 64u; ++w) {
+        if (w < zmi_wave()) k += wsum[w];
+        total += wsum[w];
+    }
+    if (ok) slot[k] = pos;
+    if (t == 0u) vcnt[blockIdx.x] = total;
+}
+
+__global__ void __launch_bounds__(BS_T) zmi_block_gather_kernel(const uint32_t* __restrict__ slots, const uint32_t* __restrict__ vcnt,
+                                                                 const uint64_t* __restrict__ voff, uint32_t* __restrict__ vlist, uint32_t vcap) {
+    const uint32_t t = threadIdx.x;
+    if (t >= vcnt[blockIdx.x]) return;
+    const uint64_t k = voff[blockIdx.x] + t;
+    if (k < vcap) vlist[k] = slots[(uint64_t)blockIdx.x * BS_SLOT + t];
+}
+
+// One wave.  first != 0: cuts[0] = 8 * the end of the header starts the list; otherwise the walk continues behind cuts[*n_cuts - 1].
+// Entry k + 1 = the smallest validated position >= cuts[k] + gap_bits.
+__global__ void __launch_bounds__(64) zmi_block_walk_kernel(const uint32_t* __restrict__ vlist, const uint64_t* __restrict__ voff, uint32_t nblocks,
+                                                            uint32_t vcap, uint64_t base_bit, uint64_t gap_bits, uint32_t first,
+                                                            const uint32_t* __restrict__ hdr, uint64_t* cuts, uint32_t cap, uint32_t* n_cuts) {
+    const uint32_t lane = zmi_lane();
+    uint32_t cnt;
+    uint64_t last;
+    if (first) {
+        last = 8ull * hdr[0];
+        cnt = cap ? 1u : 0u;
+        if (lane == 0u && cap) cuts[0] = last;
+    } else {
+        cnt = *n_cuts;
+        last = cnt ? cuts[cnt - 1u] : 0ull;
+    }
+    uint64_t total = nblocks ? voff[nblocks] : 0ull;
+    if (total > vcap) total = vcap;
+    uint64_t need = last + gap_bits;
+    for (uint64_t i0 = 0; i0 < total && cnt != 0u && cnt < cap; i0 += 64u) {
+        const bool have = i0 + lane < total;
+        const uint64_t v = have ? base_bit + vlist[i0 + lane] : 0ull;
+        for (;;) {
+            const uint64_t hit = __ballot(have && v >= need);
+            if (!hit) break;
+            const uint32_t l = (uint32_t)__ffsll((unsigned long long)hit) - 1u;
+            const uint64_t p = (uint64_t)zmi_readlane((uint32_t)v, l) | ((uint64_t)zmi_readlane((uint32_t)(v >> 32), l) << 32);
+            if (lane == 0u) cuts[cnt] = p;
+            need = p + gap_bits;
+            if (++cnt >= cap) break;
+        }
+    }
+    if (lane == 0u) *n_cuts = cnt;
+}
+
+// One window: d_win = the window's first byte, n_vis bytes visible from there (the window and up to BS_LOOK bytes behind it),
+// own_bits positions proposed from (8 * the window's bytes), base_bit = the window's first bit in the stream.  Scratch: d_slots
+// u32[nblocks * BS_SLOT], d_cnt / d_vcnt u32[nblocks], d_voff u64[nblocks + 1], d_vlist u32[vcap]; nblocks = zmi_block_scan_groups(own_bits).
+extern "C" uint32_t zmi_block_scan_groups(uint32_t own_bits) { return (own_bits + BS_T * 64u - 1u) / (BS_T * 64u); }
+extern "C" uint32_t zmi_block_scan_slot(void) { return BS_SLOT; }
+extern "C" uint32_t zmi_block_scan_look(void) { return BS_LOOK; }
+extern "C" int zmi_launch_block_scan_window(const uint8_t* d_win, uint32_t n_vis, uint64_t base_bit, uint32_t own_bits, const uint32_t* d_hdr,
+                                            uint32_t* d_slots, uint32_t* d_cnt, uint32_t* d_vcnt, uint64_t* d_voff, uint32_t* d_vlist, uint32_t vcap,
+                                            uint64_t gap_bits, uint32_t first, uint64_t* d_cuts, uint32_t cap, uint32_t* d_n_cuts,
+                                            hipStream_t stream) {
+    const uint32_t nblocks = zmi_block_scan_groups(own_bits);
+    if (nblocks) {
+        ZMI_LAUNCH(zmi_block_scan_ord_kernel, dim3(nblocks), dim3(BS_T), 0, stream, d_win, n_vis, base_bit, own_bits, d_hdr, d_slots, d_cnt);
+        ZMI_LAUNCH(zmi_block_validate_ord_kernel, dim3(nblocks), dim3(BS_T), 0, stream, d_win, n_vis, d_slots, (const uint32_t*)d_cnt, d_vcnt);
+        zmi_launch_scan_sizes((const uint32_t*)d_vcnt, nblocks, d_voff, stream);
+        ZMI_LAUNCH(zmi_block_gather_kernel, dim3(nblocks), dim3(BS_T), 0, stream, (const uint32_t*)d_slots, (const uint32_t*)d_vcnt,
+                   (const uint64_t*)d_voff, d_vlist, vcap);
+    }
+    ZMI_LAUNCH(zmi_block_walk_kernel, dim3(1), dim3(64), 0, stream, (const uint32_t*)d_vlist, (const uint64_t*)d_voff, nblocks, vcap, base_bit,
+               gap_bits, first, d_hdr, d_cuts, cap, d_n_cuts);
     return 0;
 }

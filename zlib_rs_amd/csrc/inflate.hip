@@ -2427,10 +2427,67 @@ __global__ void __launch_bounds__(256) zmi_si_verify_kernel(const uint64_t* __re
     else if (last) *tail = cuts[g] + res[4u * i] + (res[4u * i + 1u] ? 1u : 0u);
 }
 
+// ---- the same two steps for cuts at BIT positions (zmi_inflate_stream_bits_dev; proposals of the block scan, blockscan.hip) ---------
+// Piece g starts at bit cuts[g] & 7 of byte cuts[g] >> 3 and sees the input up to the byte that holds the next cut, which both
+// neighbours read.  Only the start bit reaches in_bit[]: its upper bits would ask the decode for block stops.
+__global__ void __launch_bounds__(256) zmi_si_setup_bits_kernel(const uint64_t* __restrict__ cuts, uint32_t n_cuts, uint64_t in_len, uint32_t first,
+                                                                uint32_t cnt, uint64_t stride, uint32_t cap, uint64_t* __restrict__ in_off,
+                                                                uint32_t* __restrict__ in_n, uint64_t* __restrict__ out_off,
+                                                                uint32_t* __restrict__ ocap, uint32_t* __restrict__ hist,
+                                                                uint32_t* __restrict__ in_bit) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= cnt) return;
+    const uint32_t g = first + i;
+    const uint64_t end = 8ull * in_len;
+    const uint64_t a = cuts[g], b = g + 1u < n_cuts ? cuts[g + 1u] : end;
+    const uint64_t ab = a >> 3, bb = (b >> 3) + ((b & 7u) ? 1u : 0u);
+    const bool fits = b > a && b <= end && bb - ab <= 0xFFFFFF00ull;
+    in_off[i] = ab <= in_len ? ab : in_len;
+    in_n[i] = fits ? (uint32_t)(bb - ab) : 0u;
+    in_bit[i] = fits ? (uint32_t)(a & 7u) : 0u;
+    out_off[i] = (uint64_t)i * stride;
+    ocap[i] = cap;
+    hist[i] = g == 0u ? 0u : SI_HIST;
+}
+
+// The rule zmi_split_core applies to a cut inside a byte: the piece in front of it is CLEAN if its decode stopped for want of input
+// with its checkpoint (the start of the block it stopped in) exactly at the cut.  It has seen at most seven bits of the next block;
+// whatever it made of them lies behind the checkpoint: the piece's length is the checkpoint's output count.
+__global__ void __launch_bounds__(256) zmi_si_verify_bits_kernel(const uint64_t* __restrict__ cuts, uint32_t n_cuts, uint32_t first, uint32_t cnt,
+                                                                 const uint32_t* __restrict__ in_n, const uint32_t* __restrict__ olen,
+                                                                 const int32_t* __restrict__ st, const int32_t* __restrict__ det,
+                                                                 const uint32_t* __restrict__ res, uint32_t cap, uint32_t* __restrict__ len,
+                                                                 unsigned long long* bad, uint64_t* tail) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= cnt) return;
+    const uint32_t g = first + i;
+    const bool last = g + 1u == n_cuts;
+    uint32_t kind = 0, idx = g, L = olen[i];
+    if (in_n[i] == 0u) { kind = SI_D_CUT; idx = g + 1u < n_cuts ? g + 1u : g; }
+    else if (st[i] == ZMI_DATA_ERROR) kind = SI_D_DATA;
+    else if (st[i] == ZMI_BUF_ERROR && det[i] == 2) kind = SI_D_PIECE;
+    else if (olen[i] > cap) kind = SI_D_PIECE;
+    else if (st[i] != ZMI_OK && st[i] != ZMI_BUF_ERROR) kind = SI_D_DATA;
+    else if (last) {
+        if (st[i] != ZMI_OK || res[4u * i + 3u] == 0u) kind = SI_D_TRUNC;
+    } else {
+        const uint64_t cut_byte = (cuts[g + 1u] >> 3) - (cuts[g] >> 3);
+        const uint32_t cut_bit = (uint32_t)(cuts[g + 1u] & 7u);
+        const bool clean = st[i] == ZMI_BUF_ERROR && det[i] == 1 && res[4u * i] == cut_byte && res[4u * i + 1u] == cut_bit &&
+                           res[4u * i + 2u] <= olen[i] && (cut_bit != 0u || res[4u * i + 2u] == olen[i]) && res[4u * i + 3u] == 0u;
+        if (!clean) { kind = SI_D_CUT; idx = g + 1u; }
+        L = res[4u * i + 2u];
+    }
+    len[g] = kind ? 0u : L;
+    if (kind) atomicMin(bad, (unsigned long long)(((uint64_t)g << 40) | ((uint64_t)idx << 8) | kind));
+    else if (last) *tail = (cuts[g] >> 3) + res[4u * i] + (res[4u * i + 1u] ? 1u : 0u);
+}
+
 // Thread 0: status / detail / lengths of the call.  Order: the header, the first failed piece, the room, the trailer (zlib: Adler-32
 // big-endian; gzip: CRC-32, then ISIZE = the low 32 bits of the length, little-endian).
 __global__ void __launch_bounds__(64) zmi_si_final_kernel(const uint8_t* __restrict__ in, uint64_t in_len, const uint32_t* __restrict__ hdr,
-                                                          const uint64_t* __restrict__ cut0, const unsigned long long* __restrict__ bad,
+                                                          const uint64_t* __restrict__ cut0, uint32_t cut_shift,
+                                                          const unsigned long long* __restrict__ bad,
                                                           const uint64_t* __restrict__ tail, const uint64_t* __restrict__ total,
                                                           const uint32_t* __restrict__ adler, const uint32_t* __restrict__ crc, uint64_t out_cap,
                                                           int32_t* status, int32_t* detail, uint64_t* out_len, uint64_t* in_used) {
@@ -2441,7 +2498,7 @@ __global__ void __launch_bounds__(64) zmi_si_final_kernel(const uint8_t* __restr
     const uint64_t T = *total;
     uint64_t used = hdr[0];
     *out_len = T;
-    if (st == 0 && *cut0 != hdr[0]) { st = ZMI_DATA_ERROR; det = SI_D_CUT; }
+    if (st == 0 && *cut0 != (uint64_t)hdr[0] << cut_shift) { st = ZMI_DATA_ERROR; det = SI_D_CUT; }
     if (st == 0 && *bad != ~0ull) {
         const uint32_t k = (uint32_t)(*bad & 0xFFu), idx = (uint32_t)((*bad >> 8) & 0xFFFFFFFFull);
         st = k == SI_D_TRUNC ? ZMI_BUF_ERROR : (k == SI_D_PIECE ? ZMI_BUF_ERROR : ZMI_DATA_ERROR);
@@ -2554,11 +2611,28 @@ extern "C" int zmi_launch_si_verify(const uint64_t* d_cuts, uint32_t n_cuts, uin
                d_res, cap, d_len, (unsigned long long*)d_bad, d_tail);
     return 0;
 }
-extern "C" int zmi_launch_si_final(const uint8_t* d_in, uint64_t in_len, const uint32_t* d_hdr, const uint64_t* d_cut0, const uint64_t* d_bad,
-                                   const uint64_t* d_tail, const uint64_t* d_total, const uint32_t* d_adler, const uint32_t* d_crc, uint64_t out_cap,
-                                   int32_t* d_status, int32_t* d_detail, uint64_t* d_out_len, uint64_t* d_in_used, hipStream_t stream) {
-    ZMI_LAUNCH(zmi_si_final_kernel, dim3(1), dim3(64), 0, stream, d_in, in_len, d_hdr, d_cut0, (const unsigned long long*)d_bad, d_tail, d_total,
-               d_adler, d_crc, out_cap, d_status, d_detail, d_out_len, d_in_used);
+extern "C" int zmi_launch_si_setup_bits(const uint64_t* d_cuts, uint32_t n_cuts, uint64_t in_len, uint32_t first, uint32_t cnt, uint64_t stride,
+                                        uint32_t cap, uint64_t* d_in_off, uint32_t* d_in_n, uint64_t* d_out_off, uint32_t* d_ocap, uint32_t* d_hist,
+                                        uint32_t* d_in_bit, hipStream_t stream) {
+    if (cnt == 0) return 0;
+    ZMI_LAUNCH(zmi_si_setup_bits_kernel, dim3((cnt + 255u) / 256u), dim3(256), 0, stream, d_cuts, n_cuts, in_len, first, cnt, stride, cap, d_in_off,
+               d_in_n, d_out_off, d_ocap, d_hist, d_in_bit);
+    return 0;
+}
+extern "C" int zmi_launch_si_verify_bits(const uint64_t* d_cuts, uint32_t n_cuts, uint32_t first, uint32_t cnt, const uint32_t* d_in_n,
+                                         const uint32_t* d_olen, const int32_t* d_st, const int32_t* d_det, const uint32_t* d_res, uint32_t cap,
+                                         uint32_t* d_len, uint64_t* d_bad, uint64_t* d_tail, hipStream_t stream) {
+    if (cnt == 0) return 0;
+    ZMI_LAUNCH(zmi_si_verify_bits_kernel, dim3((cnt + 255u) / 256u), dim3(256), 0, stream, d_cuts, n_cuts, first, cnt, d_in_n, d_olen, d_st, d_det,
+               d_res, cap, d_len, (unsigned long long*)d_bad, d_tail);
+    return 0;
+}
+extern "C" int zmi_launch_si_final(const uint8_t* d_in, uint64_t in_len, const uint32_t* d_hdr, const uint64_t* d_cut0, uint32_t cut_shift,
+                                   const uint64_t* d_bad, const uint64_t* d_tail, const uint64_t* d_total, const uint32_t* d_adler,
+                                   const uint32_t* d_crc, uint64_t out_cap, int32_t* d_status, int32_t* d_detail, uint64_t* d_out_len,
+                                   uint64_t* d_in_used, hipStream_t stream) {
+    ZMI_LAUNCH(zmi_si_final_kernel, dim3(1), dim3(64), 0, stream, d_in, in_len, d_hdr, d_cut0, cut_shift, (const unsigned long long*)d_bad, d_tail,
+               d_total, d_adler, d_crc, out_cap, d_status, d_detail, d_out_len, d_in_used);
     return 0;
 }
 extern "C" int zmi_launch_si_find_cuts(const uint8_t* d_in, uint64_t n, const uint32_t* d_hdr, uint32_t* d_seg, uint64_t min_gap, uint64_t* d_cuts,

@@ -105,6 +105,7 @@ struct zmi_ctx {
     zmi_buf sd_meta, sd_slots;          // zmi_deflate_stream_dev: per-piece tables / one launch group's output slots
     zmi_buf comb;                       // zmi_checksum_combine_dev: the per-workgroup partial folds
     zmi_buf si_meta, si_work, si_seg;   // zmi_inflate_stream_dev: per-piece tables / one launch group's regions; find_cuts' segment table
+    zmi_buf si_scan;                    // zmi_stream_find_blocks_dev: one window's survivor slots and validated list
 };
 
 static int zmi_reserve(zmi_buf& b, size_t bytes) {
@@ -159,6 +160,7 @@ extern "C" int zmi_ctx_destroy(zmi_ctx* c) {
     if (c->si_meta.p) (void)hipFree(c->si_meta.p);
     if (c->si_work.p) (void)hipFree(c->si_work.p);
     if (c->si_seg.p) (void)hipFree(c->si_seg.p);
+    if (c->si_scan.p) (void)hipFree(c->si_scan.p);
     for (int k = 0; k < 2; ++k) if (c->st_pin[k].p) (void)hipHostFree(c->st_pin[k].p);
     if (c->st_pin_ev_live) { (void)hipEventDestroy(c->st_pin_ev[0]); (void)hipEventDestroy(c->st_pin_ev[1]); }
     if (c->hb_live) {
@@ -1981,14 +1983,19 @@ extern "C" int zmi_inflate_resume(zmi_ctx* c, const uint8_t* in, uint32_t in_len
 #define ZMI_SI_WIN 32768u
 #define ZMI_SI_B 64u          // pieces per block of the window scan
 #define ZMI_SI_SLACK 4096u
-extern "C" int zmi_inflate_stream_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, int wrap, const uint64_t* d_cuts, uint32_t n_cuts,
-                                      uint32_t piece_out_max, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used,
-                                      int32_t* d_status, int32_t* d_detail, void* stream_) {
+// bits: the cuts are bit offsets (zmi_inflate_stream_bits_dev) -- the pieces' start bits go to the decode, the setup and verify steps
+// are the bit forms; everything else is one code path
+static int zmi_inflate_stream_body(zmi_ctx* c, const void* d_in, uint64_t in_len, int wrap, const uint64_t* d_cuts, uint32_t n_cuts,
+                                   uint32_t piece_out_max, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used,
+                                   int32_t* d_status, int32_t* d_detail, void* stream_, bool bits) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_AUTO) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip/auto");
-    if (n_cuts == 0 || !d_cuts) return zmi_fail(ZMI_E_ARG, "zmi_inflate_stream_dev: at least one cut (the end of the header)");
+    if (n_cuts == 0 || !d_cuts)
+        return zmi_fail(ZMI_E_ARG, bits ? "zmi_inflate_stream_bits_dev: at least one cut (the end of the header)"
+                                        : "zmi_inflate_stream_dev: at least one cut (the end of the header)");
     if (piece_out_max == 0 || piece_out_max > (1u << 30)) return zmi_fail(ZMI_E_ARG, "piece_out_max must be 1 .. 2^30");
     if ((in_len && !d_in) || (out_cap && !d_out) || !d_out_len || !d_in_used || !d_status || !d_detail) return zmi_fail(ZMI_E_ARG, "null argument");
+    if (bits && in_len >= (1ull << 60)) return zmi_fail(ZMI_E_ARG, "in_len must be below 2^60 (bit offsets are 64-bit)");
     hipStream_t stream = (hipStream_t)stream_;
     ZMI_ON_DEVICE(c);
     const uint64_t stride = ((uint64_t)piece_out_max + ZMI_SI_CH - 1u) & ~(uint64_t)(ZMI_SI_CH - 1u);
@@ -2005,11 +2012,11 @@ extern "C" int zmi_inflate_stream_dev(zmi_ctx* c, const void* d_in, uint64_t in_
     const size_t m_off = 0, m_bad = 8 * (n + 1), m_tail = m_bad + 8, m_len = m_tail + 8, m_clen = m_len + 4 * n, m_adler = m_clen + 4 * n,
                  m_crc = m_adler + 4 * n, m_hdr = m_crc + 4 * n, m_chk = m_hdr + 16, m_carry = (m_chk + 8 + 15) & ~(size_t)15,
                  meta_bytes = m_carry + ZMI_SI_WIN;
-    // launch group: in_off u64 | out_off u64 | in_n | ocap | hist | olen | st | used | det (u32[G] each) | res u32[4G] | agg u16[nblk * 32 Ki] |
-    // wstart | win | sym | dec
+    // launch group: in_off u64 | out_off u64 | in_n | ocap | hist | olen | st | used | det | start bit (u32[G] each) | res u32[4G] |
+    // agg u16[nblk * 32 Ki] | wstart | win | sym | dec
     const size_t g = G;
     const size_t w_ioff = 0, w_ooff = 8 * g, w_in = 16 * g, w_cap = w_in + 4 * g, w_hist = w_cap + 4 * g, w_olen = w_hist + 4 * g, w_st = w_olen + 4 * g,
-                 w_used = w_st + 4 * g, w_det = w_used + 4 * g, w_res = w_det + 4 * g, w_agg = (w_res + 16 * g + 255) & ~(size_t)255,
+                 w_used = w_st + 4 * g, w_det = w_used + 4 * g, w_bit = w_det + 4 * g, w_res = w_bit + 4 * g, w_agg = (w_res + 16 * g + 255) & ~(size_t)255,
                  w_wst = w_agg + (size_t)nblk * ZMI_SI_WIN * 2u, w_win = w_wst + (size_t)nblk * ZMI_SI_WIN, w_sym = w_win + g * ZMI_SI_WIN,
                  w_dec = w_sym + g * stride * 2u + ZMI_SI_SLACK, work_bytes = w_dec + g * stride + ZMI_SI_SLACK;
     int rc = zmi_reserve(c->si_meta, meta_bytes);
@@ -2048,17 +2055,23 @@ extern "C" int zmi_inflate_stream_dev(zmi_ctx* c, const void* d_in, uint64_t in_
         const uint32_t f = (uint32_t)first;
         {
             zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
-            zmi_launch_si_setup(d_cuts, n_cuts, in_len, f, cnt, stride, piece_out_max, (uint64_t*)(W + w_ioff), (uint32_t*)(W + w_in),
-                                (uint64_t*)(W + w_ooff), (uint32_t*)(W + w_cap), (uint32_t*)(W + w_hist), stream);
+            if (bits)
+                zmi_launch_si_setup_bits(d_cuts, n_cuts, in_len, f, cnt, stride, piece_out_max, (uint64_t*)(W + w_ioff), (uint32_t*)(W + w_in),
+                                         (uint64_t*)(W + w_ooff), (uint32_t*)(W + w_cap), (uint32_t*)(W + w_hist), (uint32_t*)(W + w_bit), stream);
+            else
+                zmi_launch_si_setup(d_cuts, n_cuts, in_len, f, cnt, stride, piece_out_max, (uint64_t*)(W + w_ioff), (uint32_t*)(W + w_in),
+                                    (uint64_t*)(W + w_ooff), (uint32_t*)(W + w_cap), (uint32_t*)(W + w_hist), stream);
         }
         rc = zmi_inflate_impl(c, d_in, (const uint64_t*)(W + w_ioff), (const uint32_t*)(W + w_in), cnt, ZMI_WRAP_RAW, d_dec, (const uint64_t*)(W + w_ooff),
                               (const uint32_t*)(W + w_cap), (const uint32_t*)(W + w_hist), (uint32_t*)(W + w_olen), (int32_t*)(W + w_st),
-                              (uint32_t*)(W + w_used), (int32_t*)(W + w_det), nullptr, (uint32_t*)(W + w_res), stream_, true);
+                              (uint32_t*)(W + w_used), (int32_t*)(W + w_det), bits ? (const uint32_t*)(W + w_bit) : nullptr, (uint32_t*)(W + w_res),
+                              stream_, true);
         if (rc) return rc;
         {
             zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
-            zmi_launch_si_verify(d_cuts, n_cuts, f, cnt, (const uint32_t*)(W + w_in), (const uint32_t*)(W + w_olen), (const int32_t*)(W + w_st),
-                                 (const int32_t*)(W + w_det), (const uint32_t*)(W + w_res), piece_out_max, d_len, d_bad, d_tail, stream);
+            (bits ? zmi_launch_si_verify_bits : zmi_launch_si_verify)(d_cuts, n_cuts, f, cnt, (const uint32_t*)(W + w_in), (const uint32_t*)(W + w_olen),
+                                                                      (const int32_t*)(W + w_st), (const int32_t*)(W + w_det),
+                                                                      (const uint32_t*)(W + w_res), piece_out_max, d_len, d_bad, d_tail, stream);
         }
         {
             zmi_scope_timer tm(c, ZMI_K_PACK, stream);
@@ -2087,11 +2100,23 @@ extern "C" int zmi_inflate_stream_dev(zmi_ctx* c, const void* d_in, uint64_t in_
     if (kind == 2u || kind == 3u) { rc = zmi_checksum_combine_dev(c, ZMI_WRAP_GZIP, d_crc, d_clen, 1u, n_cuts, d_chk + 1, nullptr, stream_); if (rc) return rc; }
     {
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
-        zmi_launch_si_final((const uint8_t*)d_in, in_len, d_hdr, d_cuts, d_bad, d_tail, d_off + n, d_chk, d_chk + 1, out_cap, d_status, d_detail,
-                            d_out_len, d_in_used, stream);
+        zmi_launch_si_final((const uint8_t*)d_in, in_len, d_hdr, d_cuts, bits ? 3u : 0u, d_bad, d_tail, d_off + n, d_chk, d_chk + 1, out_cap, d_status,
+                            d_detail, d_out_len, d_in_used, stream);
     }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;
+}
+extern "C" int zmi_inflate_stream_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, int wrap, const uint64_t* d_cuts, uint32_t n_cuts,
+                                      uint32_t piece_out_max, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used,
+                                      int32_t* d_status, int32_t* d_detail, void* stream_) {
+    return zmi_inflate_stream_body(c, d_in, in_len, wrap, d_cuts, n_cuts, piece_out_max, d_out, out_cap, d_out_len, d_in_used, d_status, d_detail,
+                                   stream_, false);
+}
+extern "C" int zmi_inflate_stream_bits_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, int wrap, const uint64_t* d_cuts, uint32_t n_cuts,
+                                           uint32_t piece_out_max, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used,
+                                           int32_t* d_status, int32_t* d_detail, void* stream_) {
+    return zmi_inflate_stream_body(c, d_in, in_len, wrap, d_cuts, n_cuts, piece_out_max, d_out, out_cap, d_out_len, d_in_used, d_status, d_detail,
+                                   stream_, true);
 }
 
 extern "C" int zmi_stream_find_cuts_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, int wrap, uint64_t min_gap, uint64_t* d_cuts, uint32_t cap,
@@ -2110,6 +2135,46 @@ extern "C" int zmi_stream_find_cuts_dev(zmi_ctx* c, const void* d_in, uint64_t i
         zmi_launch_si_header((const uint8_t*)d_in, in_len, (uint32_t)wrap, d_hdr, stream);
         zmi_launch_si_find_cuts((const uint8_t*)d_in, in_len, d_hdr, d_hdr + 4, min_gap, d_cuts, cap, d_n_cuts, stream);
     }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+// Proposals of cuts for a stream WITHOUT flush points: the bit positions of its dynamic block headers (blockscan.hip), thinned
+// greedily to at least min_gap bytes apart, ascending, on the device.  The stream is scanned in windows of 64 MiB, one after the
+// other on `stream`; the walk of a window continues the list of the window in front of it.  Scratch (c->si_scan): about 9 / 16 of
+// min(in_len, 64 MiB) -- 1 KiB of survivor slots per 2 KiB of a window, 4 B of list per 64 B -- whatever in_len is.
+extern "C" int zmi_stream_find_blocks_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, int wrap, uint64_t min_gap, uint64_t* d_cuts, uint32_t cap,
+                                          uint32_t* d_n_cuts, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_AUTO) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip/auto");
+    if ((in_len && !d_in) || (cap && !d_cuts) || !d_n_cuts) return zmi_fail(ZMI_E_ARG, "null argument");
+    if (in_len >= (1ull << 60) || min_gap >= (1ull << 60)) return zmi_fail(ZMI_E_ARG, "in_len and min_gap must be below 2^60 (bit offsets are 64-bit)");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    uint64_t window = 64ull << 20;   // (positions inside a window are 32-bit: at most 2^28 bytes)
+    if (const char* wv = zmi_tune("ZMI_BLOCKS_WINDOW")) if (atoll(wv) >= 64 && atoll(wv) <= (1ll << 28)) window = (uint64_t)atoll(wv);
+    const uint64_t widest = in_len < window ? in_len : window;
+    const size_t nb = zmi_block_scan_groups((uint32_t)(8u * widest)), slot = zmi_block_scan_slot();
+    const uint32_t vcap = (uint32_t)(widest / 64u) + 1024u;
+    // hdr u32[4] | voff u64[nb + 1] | cnt u32[nb] | vcnt u32[nb] | vlist u32[vcap] | slots u32[nb * slot]
+    const size_t s_hdr = 0, s_voff = 16, s_cnt = s_voff + 8 * (nb + 1), s_vcnt = s_cnt + 4 * nb, s_vlist = s_vcnt + 4 * nb,
+                 s_slots = s_vlist + 4 * (size_t)vcap, bytes = s_slots + 4 * nb * slot;
+    int rc = zmi_reserve(c->si_scan, bytes);
+    if (rc) return rc;
+    uint8_t* S = (uint8_t*)c->si_scan.p;
+    uint32_t* d_hdr = (uint32_t*)(S + s_hdr);
+    const uint64_t gap_bits = 8ull * (min_gap ? min_gap : 1u);
+    zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+    zmi_launch_si_header((const uint8_t*)d_in, in_len, (uint32_t)wrap, d_hdr, stream);
+    uint64_t base = 0;
+    do {
+        const uint64_t own = in_len - base < window ? in_len - base : window;
+        const uint64_t vis = in_len - base < window + zmi_block_scan_look() ? in_len - base : window + zmi_block_scan_look();
+        zmi_launch_block_scan_window((const uint8_t*)d_in + base, (uint32_t)vis, 8ull * base, (uint32_t)(8u * own), d_hdr, (uint32_t*)(S + s_slots),
+                                     (uint32_t*)(S + s_cnt), (uint32_t*)(S + s_vcnt), (uint64_t*)(S + s_voff), (uint32_t*)(S + s_vlist), vcap,
+                                     gap_bits, base == 0 ? 1u : 0u, d_cuts, cap, d_n_cuts, stream);
+        base += own;
+    } while (base < in_len);
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;
 }

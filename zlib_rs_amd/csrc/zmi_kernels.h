@@ -129,10 +129,28 @@ int zmi_launch_si_window_scan(const uint16_t* d_sym, uint64_t stride, const uint
 int zmi_launch_si_subst(const uint16_t* d_sym, uint64_t stride, const uint32_t* d_len, const uint64_t* d_off, const uint8_t* d_win,
                         uint32_t n, uint32_t piece_cap, uint32_t first, uint8_t* d_out, uint64_t out_cap, uint64_t* d_bad,
                         hipStream_t stream);
-int zmi_launch_si_final(const uint8_t* d_in, uint64_t in_len, const uint32_t* d_hdr, const uint64_t* d_cut0, const uint64_t* d_bad,
-                        const uint64_t* d_tail, const uint64_t* d_total, const uint32_t* d_adler, const uint32_t* d_crc, uint64_t out_cap,
-                        int32_t* d_status, int32_t* d_detail, uint64_t* d_out_len, uint64_t* d_in_used, hipStream_t stream);
+// cut_shift: 0 for cuts in bytes, 3 for cuts in bits (*d_cut0 must be the end of the header in that unit)
+int zmi_launch_si_final(const uint8_t* d_in, uint64_t in_len, const uint32_t* d_hdr, const uint64_t* d_cut0, uint32_t cut_shift,
+                        const uint64_t* d_bad, const uint64_t* d_tail, const uint64_t* d_total, const uint32_t* d_adler, const uint32_t* d_crc,
+                        uint64_t out_cap, int32_t* d_status, int32_t* d_detail, uint64_t* d_out_len, uint64_t* d_in_used, hipStream_t stream);
+// the same two steps for cuts at BIT positions (zmi_inflate_stream_bits_dev): d_in_bit[i] = the bit of its first byte piece i starts at
+int zmi_launch_si_setup_bits(const uint64_t* d_cuts, uint32_t n_cuts, uint64_t in_len, uint32_t first, uint32_t cnt, uint64_t stride,
+                             uint32_t cap, uint64_t* d_in_off, uint32_t* d_in_n, uint64_t* d_out_off, uint32_t* d_ocap, uint32_t* d_hist,
+                             uint32_t* d_in_bit, hipStream_t stream);
+int zmi_launch_si_verify_bits(const uint64_t* d_cuts, uint32_t n_cuts, uint32_t first, uint32_t cnt, const uint32_t* d_in_n,
+                              const uint32_t* d_olen, const int32_t* d_st, const int32_t* d_det, const uint32_t* d_res, uint32_t cap,
+                              uint32_t* d_len, uint64_t* d_bad, uint64_t* d_tail, hipStream_t stream);
 int zmi_launch_si_clamp(const uint32_t* d_len, const uint64_t* d_off, uint32_t n, uint64_t out_cap, uint32_t* d_clen, hipStream_t stream);
 int zmi_launch_si_find_cuts(const uint8_t* d_in, uint64_t n, const uint32_t* d_hdr, uint32_t* d_seg, uint64_t min_gap, uint64_t* d_cuts,
                             uint32_t cap, uint32_t* d_n_cuts, hipStream_t stream);
+// the block scan (blockscan.hip): the host-buffer form of zmi_inflate_blocks, and one window of the ordered form of
+// zmi_stream_find_blocks_dev
+int zmi_launch_block_scan(const uint8_t* d_in, uint32_t n, uint64_t first_bit, uint32_t* d_pre, uint32_t pre_cap, uint32_t* d_list,
+                          uint32_t cap, uint32_t* d_count, hipStream_t stream);
+uint32_t zmi_block_scan_groups(uint32_t own_bits);
+uint32_t zmi_block_scan_slot(void);
+uint32_t zmi_block_scan_look(void);
+int zmi_launch_block_scan_window(const uint8_t* d_win, uint32_t n_vis, uint64_t base_bit, uint32_t own_bits, const uint32_t* d_hdr,
+                                 uint32_t* d_slots, uint32_t* d_cnt, uint32_t* d_vcnt, uint64_t* d_voff, uint32_t* d_vlist, uint32_t vcap,
+                                 uint64_t gap_bits, uint32_t first, uint64_t* d_cuts, uint32_t cap, uint32_t* d_n_cuts, hipStream_t stream);
 }

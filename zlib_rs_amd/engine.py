@@ -189,14 +189,43 @@ class Engine:
                                                    int(cap), cnt.data_ptr(), _stream_ptr()), "zmi_stream_find_cuts_dev")
         return cuts[:int(cnt.item())]
 
+    def find_blocks(self, data, wrap=WRAP_AUTO, min_gap=1 << 16, cap=None):
+        """Proposed piece starts of a stream WITHOUT flush points (what gzip, zlib and zlib-rs write), as BIT offsets: 8 x the end of
+        the header, then the first header bit of dynamic blocks found by the block scan, at least min_gap bytes apart: an int64 device
+        tensor.  One synchronisation, for the count."""
+        n = int(data.numel())
+        if cap is None:
+            cap = max(2, n // max(1, int(min_gap)) + 2)
+        cuts = torch.zeros(cap, dtype=torch.int64, device=self.device)
+        cnt = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _lib.check(self.L.zmi_stream_find_blocks_dev(self._ctx, data.data_ptr() if n else None, n, int(wrap), int(min_gap), cuts.data_ptr(),
+                                                     int(cap), cnt.data_ptr(), _stream_ptr()), "zmi_stream_find_blocks_dev")
+        return cuts[:int(cnt.item())]
+
+    def inflate_plain_stream(self, data, wrap=WRAP_AUTO, bit_index=None, min_gap=1 << 16, piece_out_max=None, out=None, out_cap=None):
+        """One raw / zlib / gzip member, with or without flush points -> (uint8 view of the output, in_used).  bit_index: the piece
+        starts as bit offsets (find_blocks'); None runs find_blocks(min_gap).  piece_out_max defaults to 16 x min_gap, at least
+        1 MiB, at most 2^30: a piece is at least min_gap compressed bytes plus the rest of its last block, and text seldom
+        shrinks below one tenth.  The loop is inflate_stream's: a cut that does not verify is dropped and the call runs again; a
+        piece above piece_out_max doubles it (up to 2^30); an output above the room of `out` (default: out_cap bytes, or 4x the
+        input + 1 MiB) is decoded again into a buffer of the size the device reported.  Data errors raise with the status."""
+        cuts = self.find_blocks(data, wrap, min_gap) if bit_index is None else bit_index.to(torch.int64)
+        if piece_out_max is None:
+            piece_out_max = min(1 << 30, max(1 << 20, 16 * int(min_gap)))
+        return self._inflate_stream_loop(self.L.zmi_inflate_stream_bits_dev, "zmi_inflate_stream_bits_dev", data, wrap, cuts, piece_out_max, out,
+                                         out_cap)
+
     def inflate_stream(self, data, wrap=WRAP_AUTO, index=None, piece_out_max=1 << 20, out=None, out_cap=None):
         """One raw / zlib / gzip stream with flush points (deflate_stream's output, pigz) -> (uint8 view of the output, in_used).
         index: the piece starts (deflate_stream's index without its last entry, or find_cuts'); None runs find_cuts.  A cut that does
         not verify is dropped and the call runs again; a piece above piece_out_max doubles it; an output above the room of `out`
         (default: out_cap bytes, or 4x the input + 1 MiB) is decoded again into a buffer of the size the device reported.  Data
         errors raise with the status."""
-        n = int(data.numel())
         cuts = self.find_cuts(data, wrap) if index is None else index.to(torch.int64)
+        return self._inflate_stream_loop(self.L.zmi_inflate_stream_dev, "zmi_inflate_stream_dev", data, wrap, cuts, piece_out_max, out, out_cap)
+
+    def _inflate_stream_loop(self, fn, name, data, wrap, cuts, piece_out_max, out, out_cap):
+        n = int(data.numel())
         pom = int(piece_out_max)
         if out is None:
             out = torch.empty(int(out_cap) if out_cap is not None else 4 * n + (1 << 20), dtype=torch.uint8, device=self.device)
@@ -204,16 +233,15 @@ class Engine:
         tries = int(cuts.numel()) + 64
         for _ in range(tries):
             meta.zero_()
-            _lib.check(self.L.zmi_inflate_stream_dev(self._ctx, data.data_ptr() if n else None, n, int(wrap), cuts.data_ptr(),
-                                                     int(cuts.numel()), pom, out.data_ptr(), int(out.numel()), meta.data_ptr(),
-                                                     meta.data_ptr() + 8, meta.data_ptr() + 16, meta.data_ptr() + 20, _stream_ptr()),
-                       "zmi_inflate_stream_dev")
+            _lib.check(fn(self._ctx, data.data_ptr() if n else None, n, int(wrap), cuts.data_ptr(), int(cuts.numel()), pom, out.data_ptr(),
+                          int(out.numel()), meta.data_ptr(), meta.data_ptr() + 8, meta.data_ptr() + 16, meta.data_ptr() + 20, _stream_ptr()), name)
             olen, used, sd = meta.tolist()
             st = sd & 0xFFFFFFFF
             st = st - (1 << 32) if st >= 1 << 31 else st
             det = (sd >> 32) & 0xFFFFFFFF
             kind, at = det & 0xFF, det >> 8
             if st == 0:
+                self.last_piece_out_max = pom   # (what the call needed in the end: the probe tools report it)
                 return out[:olen], used
             if kind == SI_CUT and 0 < at < cuts.numel():
                 cuts = torch.cat([cuts[:at], cuts[at + 1:]])
@@ -222,8 +250,8 @@ class Engine:
             elif kind == SI_OUT:
                 out = torch.empty(olen, dtype=torch.uint8, device=self.device)
             else:
-                raise RuntimeError("zmi_inflate_stream_dev: status %d detail %d (kind %d, index %d)" % (st, det, kind, at))
-        raise RuntimeError("zmi_inflate_stream_dev: no result after %d attempts" % tries)
+                raise RuntimeError("%s: status %d detail %d (kind %d, index %d)" % (name, st, det, kind, at))
+        raise RuntimeError("%s: no result after %d attempts" % (name, tries))
 
     def deflate_pieces(self, data, offsets, lengths, max_len, level=6, strategy=0, wrap=WRAP_GZIP, independent=True, final=True):
         """One rank's pieces of a single stream: (slots [n, stride] uint8, sizes int32 [n], checks int32 [n], status int32 [n])."""

@@ -278,13 +278,15 @@ class Engine:
                    "zmi_checksum_combine_dev")
         return c, t
 
-    def stream_frame(self, out, payload_len, check, raw_len, wrap=WRAP_GZIP, level=6, strategy=0):
+    def stream_frame(self, out, payload_len, check, raw_len, wrap=WRAP_GZIP, level=6, strategy=0, out_cap=None):
         """header and trailer around the payload_len (int64 device word) bytes of deflate data at out[header:]; returns the int64
-        [2] device words length | status"""
+        [2] device words length | status.  out_cap: the room the stream may take (default: all of `out`; an empty view of a tensor
+        has no address to pass, so a capacity of 0 is given this way)"""
         meta = torch.zeros(2, dtype=torch.int64, device=self.device)
         _lib.check(self.L.zmi_stream_frame_dev(self._ctx, int(wrap), int(level), int(strategy), payload_len.data_ptr(),
                                                check.data_ptr() if check is not None else None,
-                                               raw_len.data_ptr() if raw_len is not None else None, out.data_ptr(), int(out.numel()),
+                                               raw_len.data_ptr() if raw_len is not None else None, out.data_ptr(),
+                                               int(out.numel() if out_cap is None else min(out_cap, out.numel())),
                                                meta.data_ptr(), meta.data_ptr() + 8, _stream_ptr()), "zmi_stream_frame_dev")
         return meta
 
@@ -304,10 +306,12 @@ class Engine:
         return out_len, status
 
     # ---- checksums ----
-    def checksums(self, data, offsets, lengths, adler=True, crc=True):
+    def checksums(self, data, offsets, lengths, adler=True, crc=True, out_adler=None, out_crc=None):
+        """(adler int32 [n], crc int32 [n]); the array of a checksum that was not asked for is left as it is (zeros when
+        allocated here)"""
         n = int(lengths.numel())
-        a = torch.zeros(n, dtype=torch.int32, device=self.device)
-        c = torch.zeros(n, dtype=torch.int32, device=self.device)
+        a = torch.zeros(n, dtype=torch.int32, device=self.device) if out_adler is None else out_adler
+        c = torch.zeros(n, dtype=torch.int32, device=self.device) if out_crc is None else out_crc
         kind = (1 if adler else 0) | (2 if crc else 0)
         _lib.check(self.L.zmi_checksum_batch_dev(self._ctx, data.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, kind,
                                                  a.data_ptr(), c.data_ptr(), _stream_ptr()), "zmi_checksum_batch_dev")

@@ -141,6 +141,40 @@ int zmi_inflate_batch_dict_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d
                                uint32_t n_streams, int wrap, void* d_out, const uint64_t* d_out_off,
                                const uint32_t* d_out_cap, const uint32_t* d_out_hist, uint32_t* d_out_len,
                                int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, void* stream);
+/* ---- one shared preset dictionary for a whole batch (small records: pages, log lines, messages, rows) ----
+ * Per shard exactly deflateInit2_(level, Z_DEFLATED, -15 | 15, 8, strategy) + deflateSetDictionary(dict) + deflate(Z_FINISH)
+ * (zlib-rs/src/deflate.rs:499-564, header :1572-1601), per stream inflateInit2_ + inflateSetDictionary(dict) +
+ * inflate(Z_FINISH) (zlib-rs/src/inflate.rs:2492-2536, :1036-1062), with ONE copy of the dictionary in device memory for
+ * every shard of the call.
+ *   wrap     ZMI_WRAP_RAW or ZMI_WRAP_ZLIB; gzip and auto return ZMI_E_ARG (a gzip member has no dictionary field).
+ *   d_dict   any device address at any alignment, any dict_len.  Deflate matches into the tail the search can reach:
+ *            32768 - 5 * 1024 = 27 648 bytes, rounded down to a multiple of 16 (a dictionary shorter than 16 bytes is
+ *            announced but not matched into) -- the cap a chained segment's carry-over has; the shorter reach is this
+ *            engine's existing max_dist deviation (farthest back-reference 27 632), not a new one.  Inflate uses the
+ *            last 32 768 bytes.  d_dict NULL or dict_len 0: the call is zmi_deflate_batch_dev / zmi_inflate_batch_dev_ex,
+ *            byte for byte.
+ *   DICTID   Adler-32 of all dict_len bytes, computed on the device by the checksum kernel; the encoder and the check
+ *            of the decoder read it from a device word.  Neither call synchronises with the host.
+ * Deflate: out_stride a multiple of 16, >= zmi_deflate_dict_bound(max_len, wrap).  With the zlib wrapper FDICT is set,
+ * FCHECK follows it and the DICTID stands big-endian behind the two header bytes -- at every level and strategy, also
+ * level 0 / Z_HUFFMAN_ONLY / Z_RLE, where the dictionary is announced and not (Z_RLE: hardly) used, as in zlib; the Adler-32
+ * trailer covers the shard only.  A shard's bytes depend on (dictionary, shard bytes, level, strategy, wrap) alone -- not on
+ * n_shards, its index, the alignment of d_in_off or d_dict, the scratch limit or the launch grouping.
+ * Inflate: the output regions need no room in front of them.  A zlib stream with FDICT whose DICTID is not the
+ * dictionary's reports Z_DATA_ERROR (-3) and no output, as inflateSetDictionary refuses it; a stream without FDICT and any
+ * raw stream decodes with the dictionary available and reports 0; a distance that reaches in front of the first
+ * dictionary byte is Z_DATA_ERROR; d_in_used and d_detail as in zmi_inflate_batch_dev_ex.  Back-references are always
+ * resolved by the one-wave-per-stream pass (never by pointer jumping): the call's case is many small streams. */
+/* zmi_deflate_bound + the 4 DICTID bytes of the zlib wrapper, rounded up to 16 */
+uint64_t zmi_deflate_dict_bound(uint64_t n, int wrap);
+int zmi_deflate_batch_shared_dict_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                      uint32_t n_shards, uint32_t max_len, int level, int strategy, int wrap,
+                                      const void* d_dict, uint32_t dict_len, void* d_out, uint64_t out_stride,
+                                      uint32_t* d_out_len, int32_t* d_status, void* stream);
+int zmi_inflate_batch_shared_dict_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                      uint32_t n_streams, int wrap, const void* d_dict, uint32_t dict_len, void* d_out,
+                                      const uint64_t* d_out_off, const uint32_t* d_out_cap, uint32_t* d_out_len,
+                                      int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, void* stream);
 /* Resumable decode of raw deflate streams -- the device half of a streaming inflate() that is fed partial input
  * (the reference keeps Mode / BitReader / Window for this, zlib-rs/src/inflate.rs:288-320; here the state is a
  * block-boundary checkpoint).  Stream i starts at bit d_in_bit[i] (0..7, array may be NULL) of its first byte, with

@@ -27,6 +27,11 @@ def lib():
     L.zmi_deflate_bound.argtypes = [u64, i32]
     L.zmi_deflate_batch_dev.argtypes = [vp, vp, vp, vp, u32, u32, i32, i32, i32, vp, u64, vp, vp, vp]
     L.zmi_inflate_batch_dev.argtypes = [vp, vp, vp, vp, u32, i32, vp, vp, vp, vp, vp, vp]
+    # one shared preset dictionary for a whole batch (csrc/lz77.hip, inflate.hip, zmi_api.hip)
+    L.zmi_deflate_dict_bound.restype = u64
+    L.zmi_deflate_dict_bound.argtypes = [u64, i32]
+    L.zmi_deflate_batch_shared_dict_dev.argtypes = [vp, vp, vp, vp, u32, u32, i32, i32, i32, vp, u32, vp, u64, vp, vp, vp]
+    L.zmi_inflate_batch_shared_dict_dev.argtypes = [vp, vp, vp, vp, u32, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.zmi_checksum_batch_dev.argtypes = [vp, vp, vp, vp, u32, i32, vp, vp, vp]
     L.zmi_gen_shards_dev.argtypes = [vp, vp, u64, u32, u32, u32, vp]
     L.zmi_gen_shards_strided_dev.argtypes = [vp, vp, u64, u32, u32, u32, u32, vp]

@@ -866,10 +866,16 @@ __global__ void __launch_bounds__(64) ENC_OCC zmi_encode_kernel_t(const uint8_t*
         if (!is_first) {
         } else if (prm.wrap == 1u) {
             uint32_t lf = prm.level < 2u ? 0u : (prm.level < 6u ? 1u : (prm.level == 6u ? 2u : 3u));
-            uint32_t h = (0x78u << 8) | (lf << 6);
+            // with a preset dictionary FDICT is set and the DICTID follows, big-endian, whether or not the level or strategy can
+            // use the dictionary (zlib-rs/src/deflate.rs:1572-1601); the value is a device word, computed by the checksum kernel
+            uint32_t h = (0x78u << 8) | (lf << 6) | (prm.dictid ? 0x20u : 0u);
             h += 31u - (h % 31u);
             enc_put0(S, rel, h >> 8, 8u);
             enc_put0(S, rel, h & 0xFFu, 8u);
+            if (prm.dictid) {
+                const uint32_t a = *prm.dictid;
+                enc_put0(S, rel, (a >> 24) | ((a >> 8) & 0xFF00u) | ((a << 8) & 0xFF0000u) | (a << 24), 32u);
+            }
         } else if (prm.wrap == 2u) {
             uint32_t xfl = prm.level == 9u ? 2u : (prm.level < 2u ? 4u : 0u);
             enc_put0(S, rel, 0x00088B1Fu, 32u);

@@ -1649,8 +1649,22 @@ static __device__ __forceinline__ uint4 res_fetch(const uint8_t* dst, uint32_t n
 // `pre` holds block [loaded, loaded + RES_BLK) when `have` is set: the load of the next block is always in
 // flight while the holes of the current one are filled
 // `keep` = lowest output byte the batch being staged for may still read from the ring (its first hole - RES_NEAR)
+// SD (shared preset dictionary, zmi_inflate_batch_shared_dict_dev): positions below `shift` are not bytes in front of the output
+// region but the dictionary image (img[0, shift): zeros, then the dictionary's tail, 16-byte aligned; shift a multiple of RES_BLK,
+// so no 16-byte chunk straddles the seam); dst is then fetched with lo = shift -- nothing in front of the region is read
+template <bool SD>
+static __device__ __forceinline__ uint4 res_fetch_sd(const uint8_t* dst, uint32_t n_out, uint32_t at, bool aligned16, uint32_t lo,
+                                                     const uint8_t* img, uint32_t shift) {
+    if (SD) {
+        const uint32_t so = at + 16u * zmi_lane();
+        if (so < shift) return *(const uint4*)(img + so);
+    }
+    return res_fetch(dst, n_out, at, aligned16, lo);
+}
+template <bool SD>
 static __device__ __forceinline__ void res_stage(uint8_t* ring, const uint8_t* dst, uint32_t n_out, uint32_t& loaded, uint32_t upto,
-                                                 bool aligned16, uint4& pre, bool& have, uint32_t& rb, uint32_t lo, uint32_t keep) {
+                                                 bool aligned16, uint4& pre, bool& have, uint32_t& rb, uint32_t lo, uint32_t keep,
+                                                 const uint8_t* img, uint32_t shift) {
     const uint32_t lane = zmi_lane();
     zmi_wave_order();   // ring reads issued so far (write-back of final lines) stay in front of the stores below
     if (upto > loaded + RES_RING - 2048u) {   // a long stretch without holes: only the near window matters
@@ -1660,11 +1674,11 @@ static __device__ __forceinline__ void res_stage(uint8_t* ring, const uint8_t* d
         have = false;
     }
     while (loaded < upto) {
-        if (!have) pre = res_fetch(dst, n_out, loaded, aligned16, lo);
+        if (!have) pre = res_fetch_sd<SD>(dst, n_out, loaded, aligned16, lo, img, shift);
         rb = (loaded / RES_RING) * RES_RING;
         *(uint4*)(ring + (loaded - rb) + 16u * lane) = pre;   // RES_RING is a multiple of RES_BLK: a block never wraps
         loaded += RES_BLK;
-        pre = res_fetch(dst, n_out, loaded, aligned16, lo);
+        pre = res_fetch_sd<SD>(dst, n_out, loaded, aligned16, lo, img, shift);
         have = true;
     }
     rb = (loaded / RES_RING) * RES_RING;
@@ -1746,12 +1760,24 @@ struct ResChunk {
     uint16_t list[22u * RES_CW]; // hole positions relative to the chunk (a hole is >= 3 bytes: <= 22 per word)
 };
 
+// the shared-dictionary arguments of the kernel below, when it has them
+static __device__ __forceinline__ const uint8_t* res_sd_img() { return nullptr; }
+static __device__ __forceinline__ const uint8_t* res_sd_img(const uint8_t* img, uint32_t) { return img; }
+static __device__ __forceinline__ uint32_t res_sd_hist() { return 0u; }
+static __device__ __forceinline__ uint32_t res_sd_hist(const uint8_t*, uint32_t hist) { return hist; }
+
+// SDA: nothing -- the kernel as it always was -- or (const uint8_t* img, uint32_t hist): every stream of the launch behind the same
+// `hist` bytes of dictionary, read from the image (res_fetch_sd) instead of from in front of its output region.  An instantiation
+// of its own; out_hist is not read then.
+template <typename... SDA>
 __global__ void __launch_bounds__(64) zmi_inflate_resolve_kernel(uint8_t* out, const uint64_t* __restrict__ out_off,
                                                                  const uint32_t* __restrict__ out_len,
                                                                  const uint64_t* __restrict__ bitmap,
                                                                  const uint64_t* __restrict__ bm_off,
                                                                  const uint32_t* __restrict__ out_hist,
-                                                                 const uint32_t* __restrict__ order) {
+                                                                 const uint32_t* __restrict__ order, SDA... sd_args) {
+    constexpr bool SD = sizeof...(SDA) != 0;
+    const uint8_t* const img = res_sd_img(sd_args...);
     ZMI_DYN_SMEM(smem);
     uint8_t* ring = smem;
     ResChunk* C = (ResChunk*)(smem + RES_RING);
@@ -1767,8 +1793,8 @@ __global__ void __launch_bounds__(64) zmi_inflate_resolve_kernel(uint8_t* out, c
     // With a preset dictionary of `hist` bytes in front of the output, every position in this kernel is shifted by
     // `shift` (hist rounded up to the staging block, so that lines stay aligned): the dictionary occupies
     // [lo, shift), the output [shift, n_out); nothing below `shift` is ever written back.
-    const uint32_t hist = out_hist ? out_hist[s] : 0u;
-    const uint32_t shift = (hist + RES_BLK - 1u) & ~(RES_BLK - 1u), lo = shift - hist;
+    const uint32_t hist = SD ? res_sd_hist(sd_args...) : (out_hist ? out_hist[s] : 0u);
+    const uint32_t shift = (hist + RES_BLK - 1u) & ~(RES_BLK - 1u), lo = SD ? shift : shift - hist;
     const uint32_t n_out = n_real + shift;
     uint8_t* dst = out + out_off[s] - shift;
     const bool aligned16 = ((uintptr_t)dst & 15u) == 0u, aligned4 = ((uintptr_t)dst & 3u) == 0u;
@@ -1817,7 +1843,7 @@ __global__ void __launch_bounds__(64) zmi_inflate_resolve_kernel(uint8_t* out, c
                 if (fin > wb) wb = fin;
             }
             const uint32_t keep = p_first > RES_NEAR ? p_first - RES_NEAR : 0u;
-            if (p_last + 3u > loaded) res_stage(ring, dst, n_out, loaded, p_last + 3u, aligned16, pre, have, rb, lo, keep);
+            if (p_last + 3u > loaded) res_stage<SD>(ring, dst, n_out, loaded, p_last + 3u, aligned16, pre, have, rb, lo, keep, img, shift);
             uint32_t rec = 0;
             if (active) {
                 const uint32_t a = res_ri(p, rb);
@@ -1826,7 +1852,7 @@ __global__ void __launch_bounds__(64) zmi_inflate_resolve_kernel(uint8_t* out, c
             }
             const uint32_t mlen = (rec >> 15) + 3u, md = (rec & 0x7FFFu) + 1u;
             const uint32_t last_end = p_last + zmi_readlane(mlen, nb - 1u);
-            if (last_end > loaded) res_stage(ring, dst, n_out, loaded, last_end, aligned16, pre, have, rb, lo, keep);
+            if (last_end > loaded) res_stage<SD>(ring, dst, n_out, loaded, last_end, aligned16, pre, have, rb, lo, keep, img, shift);
             const uint32_t s0 = p - md;
             const uint32_t e = s0 + (mlen < md ? mlen : md);   // end of the bytes this hole reads
             uint32_t need = 0;                                  // holes of this batch that must be finished first
@@ -1851,7 +1877,33 @@ __global__ void __launch_bounds__(64) zmi_inflate_resolve_kernel(uint8_t* out, c
                 for (uint32_t base = 0; __ballot(base < lim); base += RES_SHORT) {
                     uint32_t w[4] = {0u, 0u, 0u, 0u};
                     const uint32_t left = base < lim ? lim - base : 0u;
-                    if (left) {
+                    if (SD && left && s0 + base < shift) {
+                        // the source starts in the dictionary: the image is read-only (plain loads, 32 zero bytes behind it); a
+                        // source that runs across the seam takes the rest from this stream's own first output bytes, final in HBM
+                        const uint32_t at = s0 + base;
+                        if (at + 16u <= shift) {
+                            const uint32_t* q = (const uint32_t*)(img + (at & ~3u));
+                            const uint32_t sh = at & 3u;
+                            const uint32_t q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4];
+                            w[0] = __builtin_amdgcn_alignbyte(q1, q0, sh);
+                            w[1] = __builtin_amdgcn_alignbyte(q2, q1, sh);
+                            w[2] = __builtin_amdgcn_alignbyte(q3, q2, sh);
+                            w[3] = __builtin_amdgcn_alignbyte(q4, q3, sh);
+                        } else {
+                            uint64_t lo8 = 0, hi8 = 0;
+                            const uint32_t m = left < RES_SHORT ? left : RES_SHORT;
+                            for (uint32_t j = 0; j < m; ++j) {
+                                uint32_t b;
+                                if (at + j < shift) b = img[at + j];
+                                else {
+                                    const uintptr_t A = (uintptr_t)(dst + at + j);
+                                    b = (res_ld_final((const uint32_t*)(A & ~(uintptr_t)3)) >> (8u * (uint32_t)(A & 3u))) & 0xFFu;
+                                }
+                                if (j < 8u) lo8 |= (uint64_t)b << (8u * j); else hi8 |= (uint64_t)b << (8u * (j - 8u));
+                            }
+                            w[0] = (uint32_t)lo8; w[1] = (uint32_t)(lo8 >> 32); w[2] = (uint32_t)hi8; w[3] = (uint32_t)(hi8 >> 32);
+                        }
+                    } else if (left) {
                         const uintptr_t P = (uintptr_t)(dst + s0 + base);
                         const uint32_t* q = (const uint32_t*)(P & ~(uintptr_t)3);
                         const uint32_t sh = (uint32_t)(P & 3u), span = sh + (left < RES_SHORT ? left : RES_SHORT);
@@ -2009,12 +2061,72 @@ extern "C" int zmi_launch_inflate_resolve(uint8_t* d_out, const uint64_t* d_out_
 #ifndef ZMI_EMU
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)zmi_inflate_resolve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(RES_RING + sizeof(ResChunk)));
+        hipError_t e = hipFuncSetAttribute((const void*)zmi_inflate_resolve_kernel<>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(RES_RING + sizeof(ResChunk)));
         if (e != hipSuccess) return (int)e;
         attr_set = true;
     }
 #endif
-    ZMI_LAUNCH(zmi_inflate_resolve_kernel, dim3(n_streams), dim3(64), RES_RING + sizeof(ResChunk), stream, d_out, d_out_off, d_out_len, d_bitmap, d_bm_off, d_out_hist, d_order);
+    ZMI_LAUNCH(zmi_inflate_resolve_kernel<>, dim3(n_streams), dim3(64), RES_RING + sizeof(ResChunk), stream, d_out, d_out_off, d_out_len, d_bitmap, d_bm_off, d_out_hist, d_order);
+    return 0;
+}
+
+// The same pass with one shared dictionary: d_img = zmi_launch_dict_image's image whose first `shift` = hist rounded up to RES_BLK
+// bytes end with the dictionary's last `hist` (<= 32768) bytes, 32 zero bytes behind them.  Always this pass, never the pointer
+// jumping of resolve_jump.hip: the call's case is many small streams.
+extern "C" int zmi_launch_inflate_resolve_shared(uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_len, uint32_t n_streams,
+                                                 const uint64_t* d_bitmap, const uint64_t* d_bm_off, const uint32_t* d_order,
+                                                 const uint8_t* d_img, uint32_t hist, hipStream_t stream) {
+    if (n_streams == 0) return 0;
+    if (hist == 0u || hist > 32768u || ((uintptr_t)d_img & 15u)) return 1;
+#ifndef ZMI_EMU
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute((const void*)zmi_inflate_resolve_kernel<const uint8_t*, uint32_t>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)(RES_RING + sizeof(ResChunk)));
+        if (e != hipSuccess) return (int)e;
+        attr_set = true;
+    }
+#endif
+    ZMI_LAUNCH((zmi_inflate_resolve_kernel<const uint8_t*, uint32_t>), dim3(n_streams), dim3(64), RES_RING + sizeof(ResChunk), stream, d_out,
+               d_out_off, d_out_len, d_bitmap, d_bm_off, (const uint32_t*)nullptr, d_order, d_img, hist);
+    return 0;
+}
+
+// every stream of a shared-dictionary launch has the same history in front of it: the decode kernel's out_hist table
+__global__ void __launch_bounds__(256) zmi_inflate_shared_hist_kernel(uint32_t* __restrict__ hist_out, uint32_t n, uint32_t hist) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < n) hist_out[s] = hist;
+}
+extern "C" int zmi_launch_inflate_shared_hist(uint32_t* d_hist, uint32_t n_streams, uint32_t hist, hipStream_t stream) {
+    if (n_streams == 0) return 0;
+    ZMI_LAUNCH(zmi_inflate_shared_hist_kernel, dim3((n_streams + 255u) / 256u), dim3(256), 0, stream, d_hist, n_streams, hist);
+    return 0;
+}
+
+// after the verify kernel, zlib wrapper: a stream whose header is valid and carries FDICT names its dictionary by DICTID; if that is
+// not the Adler-32 of the call's dictionary (*dictid, a device word) the stream is refused as inflateSetDictionary refuses it
+// (Z_DATA_ERROR, zlib-rs/src/inflate.rs:2492-2536), whatever the decode made of it: no output is reported
+__global__ void __launch_bounds__(256) zmi_inflate_dictid_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+                                                                 const uint32_t* __restrict__ in_len, uint32_t n,
+                                                                 const uint32_t* __restrict__ dictid, int32_t* __restrict__ status,
+                                                                 int32_t* __restrict__ detail, uint32_t* __restrict__ out_len) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n || in_len[s] < 6u) return;
+    const uint8_t* p = in + in_off[s];
+    const uint32_t cmf = p[0], flg = p[1];
+    if ((cmf & 0x0Fu) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || !(flg & 0x20u)) return;
+    const uint32_t id = ((uint32_t)p[2] << 24) | ((uint32_t)p[3] << 16) | ((uint32_t)p[4] << 8) | (uint32_t)p[5];
+    if (id == *dictid) return;
+    status[s] = ZMI_DATA_ERROR;
+    out_len[s] = 0u;
+    if (detail) detail[s] = 0;
+}
+extern "C" int zmi_launch_inflate_dictid(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_streams,
+                                         const uint32_t* d_dictid, int32_t* d_status, int32_t* d_detail, uint32_t* d_out_len,
+                                         hipStream_t stream) {
+    if (n_streams == 0) return 0;
+    ZMI_LAUNCH(zmi_inflate_dictid_kernel, dim3((n_streams + 255u) / 256u), dim3(256), 0, stream, d_in, d_in_off, d_in_len, n_streams,
+               d_dictid, d_status, d_detail, d_out_len);
     return 0;
 }
 

@@ -250,11 +250,35 @@ static __device__ __forceinline__ void lz_build_tile(const uint8_t* win, uint16_
     else lz_build_tile_t<H6, false>(win, prev, head, head4, c4, tile, n, max_dist, ctl, producers);
 }
 
-template <bool H6>
+// one 16-byte chunk of the shard's virtual positions [c, c + 16), c a multiple of 16.  DICT (zmi_deflate_batch_shared_dict_dev): the
+// `hist` positions in front of the shard are not the bytes in front of it in `data` but the normalised image of the call's one
+// preset dictionary (zmi_dict_image_kernel: 16-byte aligned, hist a multiple of 16 -- no chunk straddles the seam and the image
+// is always read on the aligned path, whatever the caller's d_dict was)
+template <bool DICT>
+static __device__ __forceinline__ zmi_b16 lz_ld_chunk(const uint8_t* src, const uint8_t* dict, uint32_t hist, uint32_t c, uint32_t n,
+                                                      bool aligned) {
+    if (DICT && c < hist) return zmi_ld16(dict + c, 16u, true);
+    return zmi_ld16(src + c, c < n ? n - c : 0u, aligned);
+}
+
+// the shared-dictionary arguments of the kernel below, when it has them
+static __device__ __forceinline__ const uint8_t* lz_dict_ptr() { return nullptr; }
+static __device__ __forceinline__ const uint8_t* lz_dict_ptr(const uint8_t* dict, uint32_t) { return dict; }
+static __device__ __forceinline__ uint32_t lz_dict_hist() { return 0u; }
+static __device__ __forceinline__ uint32_t lz_dict_hist(const uint8_t*, uint32_t hist) { return hist; }
+
+// D: nothing -- the kernel as it always was -- or (const uint8_t* dict, uint32_t hist): every shard of the launch behind the same
+// `hist` bytes of history, dict[0, hist), 16-byte aligned, hist a multiple of 16.  That form is an instantiation of its own (the
+// kernel sits at the register limit of a 1024-thread workgroup: profiles/shared_dict_resource_usage.txt holds the listings, the
+// plain instantiations' unchanged).
+template <bool H6, typename... D>
 __global__ void __launch_bounds__(1024) zmi_lz77_kernel_t(const uint8_t* __restrict__ data, const uint64_t* __restrict__ off,
                                                         const uint32_t* __restrict__ len, uint32_t first_shard,
                                                         uint32_t* __restrict__ match, uint64_t match_stride,
-                                                        zmi_lz_params prm) {
+                                                        zmi_lz_params prm, D... dict_args) {
+    constexpr bool DICT = sizeof...(D) != 0;
+    const uint8_t* const dict = lz_dict_ptr(dict_args...);
+    const uint32_t dict_hist = lz_dict_hist(dict_args...);
 #ifdef ZMI_EMU
     ZMI_DYN_SMEM(smem);
 #else
@@ -276,7 +300,8 @@ __global__ void __launch_bounds__(1024) zmi_lz77_kernel_t(const uint8_t* __restr
     // positions at the start of the shard; they are hashed (producer) but not searched, so every position index
     // in this kernel is "virtual" = hist + position in the segment, and results are stored at index - hist
     uint32_t hist = 0;
-    if (prm.carry) {
+    if (DICT) hist = dict_hist;   // the same dictionary tail in front of every shard (a multiple of 16, sized by the launcher)
+    else if (prm.carry) {
         const uint64_t before = off[s] - off[0] + prm.dict_len;   // history bytes of this stream in front of the segment
         // whole tiles of history: max_dist rounded up (a small window -- windowBits 9..12 -- would otherwise see no history
         // or dictionary at all; positions farther back than max_dist are hashed but never reached), at most the 27 KiB
@@ -307,12 +332,12 @@ __global__ void __launch_bounds__(1024) zmi_lz77_kernel_t(const uint8_t* __restr
         // the top of the following one, so its latency hides behind the throttle wait and the hash inserts.
         if (wave == 0) {
             for (uint32_t c = lane * 16u; c < LZ_T + 16u; c += 1024u) {
-                zmi_b16 v0 = zmi_ld16(src + c, c < n ? n - c : 0u, aligned);
+                zmi_b16 v0 = lz_ld_chunk<DICT>(src, dict, hist, c, n, aligned);
                 lz_store_chunk(win, c, v0);
             }
         }
         uint32_t cpos = (wave + 1u) * LZ_T + 16u + lane * 16u;   // chunk that this wave's first round must make resident
-        zmi_b16 cur = zmi_ld16(src + cpos, cpos < n ? n - cpos : 0u, aligned);
+        zmi_b16 cur = lz_ld_chunk<DICT>(src, dict, hist, cpos, n, aligned);
         uint32_t cached_min = 0u;
         // How far the producers may run ahead of the oldest search: the window ring allows 32 KiB - max_dist, but the ring of
         // probe answers (c4: LZ_C4RING positions) must not be overwritten before it is read either -- with a short max_dist
@@ -322,7 +347,7 @@ __global__ void __launch_bounds__(1024) zmi_lz77_kernel_t(const uint8_t* __restr
         const uint32_t hold = prm.max_dist > LZ_MAX_DIST ? prm.max_dist : LZ_MAX_DIST;
         for (uint32_t k = wave; k < ntiles; k += P) {
             const uint32_t npos = cpos + P * LZ_T;
-            zmi_b16 nxt = zmi_ld16(src + npos, npos < n ? n - npos : 0u, aligned);  // for this wave's next tile
+            zmi_b16 nxt = lz_ld_chunk<DICT>(src, dict, hist, npos, n, aligned);  // for this wave's next tile
             const uint32_t E = (k + 2u) * LZ_T + 16u;  // bytes [0, E) must be resident after this round
             // ring throttle: byte E-1 lands on the slot of byte E-1-32768, which the oldest in-flight
             // search (position q) may still read while q - max_dist <= E-1-32768
@@ -530,6 +555,42 @@ __global__ void __launch_bounds__(1024) zmi_lz77_kernel_t(const uint8_t* __restr
     if (lane == 0) lz_st_rel(&ctl->wmin[wave], 0xFFFFFFFFu);
 }
 
+// The normalised image of a preset dictionary (one launch per call, a few KiB): img[0, lead) = 0, img[lead, lead + take) = the
+// last `take` bytes of dict[0, dict_len), `pad` zero bytes behind them; img is 16-byte aligned and lead + take + pad is a
+// multiple of 16, d_dict may lie anywhere.  Thread 0 also writes the one-entry layout (offset 0, length dict_len) the checksum
+// kernel needs for the DICTID (Adler-32 of the whole dictionary, deflate.rs:1572-1601), so that no host value travels.
+__global__ void __launch_bounds__(256) zmi_dict_image_kernel(const uint8_t* __restrict__ dict, uint32_t dict_len, uint8_t* __restrict__ img,
+                                                             uint32_t lead, uint32_t take, uint32_t pad, uint64_t* __restrict__ lay_off,
+                                                             uint32_t* __restrict__ lay_len) {
+    const uint32_t c = (blockIdx.x * 256u + threadIdx.x) * 16u;
+    if (c == 0u && lay_off) { lay_off[0] = 0ull; lay_len[0] = dict_len; }
+    if (c >= lead + take + pad) return;
+    const uint8_t* tail = dict + (dict_len - take);
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t j = 0; j < 16u; ++j) {
+        const uint32_t i = c + j;
+        if (i >= lead && i < lead + take) w[j >> 2] |= (uint32_t)tail[i - lead] << (8u * (j & 3u));
+    }
+    uint4 q;
+    q.x = w[0]; q.y = w[1]; q.z = w[2]; q.w = w[3];
+    *(uint4*)(img + c) = q;
+}
+extern "C" int zmi_launch_dict_image(const uint8_t* d_dict, uint32_t dict_len, uint8_t* d_img, uint32_t lead, uint32_t take, uint32_t pad,
+                                     uint64_t* d_lay_off, uint32_t* d_lay_len, hipStream_t stream) {
+    if (take > dict_len || ((lead + take + pad) & 15u)) return 1;
+    const uint32_t chunks = (lead + take + pad) / 16u;
+    ZMI_LAUNCH(zmi_dict_image_kernel, dim3(chunks / 256u + 1u), dim3(256), 0, stream, d_dict, dict_len, d_img, lead, take, pad, d_lay_off,
+               d_lay_len);
+    return 0;
+}
+// bytes of dictionary tail the match search of zmi_launch_lz77_dict can use at all (the image to build): what prm.carry gives a
+// segment of a chained stream, LZ_WSIZE - 5 * LZ_T, rounded down to the 16-byte load path
+extern "C" uint32_t zmi_lz77_dict_image_len(uint32_t dict_len) {
+    const uint32_t cap = LZ_WSIZE - 5u * LZ_T;
+    return (dict_len < cap ? dict_len : cap) & ~15u;
+}
+
 extern "C" int zmi_launch_lz77(const uint8_t* d_data, const uint64_t* d_off, const uint32_t* d_len, uint32_t first_shard,
                                uint32_t n_shards, uint32_t* d_match, uint64_t match_stride, zmi_lz_params prm,
                                hipStream_t stream) {
@@ -547,6 +608,33 @@ extern "C" int zmi_launch_lz77(const uint8_t* d_data, const uint64_t* d_off, con
 #endif
 #define LZ_GO(H) ZMI_LAUNCH((zmi_lz77_kernel_t<H>), dim3(n_shards), dim3(1024), LZ_DYN, stream, d_data, d_off, d_len, first_shard, \
                             d_match, match_stride, prm)
+    if (prm.hash6) LZ_GO(true); else LZ_GO(false);
+#undef LZ_GO
+    return 0;
+}
+
+// The same search with d_img[0, img_len) -- zmi_lz77_dict_image_len bytes, zmi_launch_dict_image's lead = 0 form -- as history in
+// front of EVERY shard (the shards are independent streams: prm.carry must be 0).  The history a shard gets is the image's tail
+// of max_dist rounded up to whole tiles, as prm.carry sizes it: Z_RLE hashes 1 KiB of it, Z_HUFFMAN_ONLY none.
+extern "C" int zmi_launch_lz77_dict(const uint8_t* d_data, const uint64_t* d_off, const uint32_t* d_len, uint32_t first_shard,
+                                    uint32_t n_shards, uint32_t* d_match, uint64_t match_stride, zmi_lz_params prm,
+                                    const uint8_t* d_img, uint32_t img_len, hipStream_t stream) {
+    if (n_shards == 0) return 0;
+    if (prm.carry || (img_len & 15u) || img_len > LZ_WSIZE - 5u * LZ_T || ((uintptr_t)d_img & 15u)) return 1;
+    if (prm.max_dist > LZ_MAX_DIST) prm.max_dist = LZ_MAX_DIST;
+    uint32_t reach = (prm.max_dist + LZ_T - 1u) & ~(LZ_T - 1u);
+    if (reach > LZ_WSIZE - 5u * LZ_T) reach = LZ_WSIZE - 5u * LZ_T;
+    const uint32_t hist = img_len < reach ? img_len : reach;
+    if (hist == 0u) return zmi_launch_lz77(d_data, d_off, d_len, first_shard, n_shards, d_match, match_stride, prm, stream);
+    if (prm.claim != 128u && prm.claim != 192u && prm.claim != 256u) prm.claim = 64u;
+#ifdef ZMI_EMU
+    const uint32_t LZ_DYN = LZ_SMEM;
+#else
+    const uint32_t LZ_DYN = 0u;
+#endif
+    const uint8_t* tail = d_img + (img_len - hist);
+#define LZ_GO(H) ZMI_LAUNCH((zmi_lz77_kernel_t<H, const uint8_t*, uint32_t>), dim3(n_shards), dim3(1024), LZ_DYN, stream, d_data, d_off, d_len, first_shard, \
+                            d_match, match_stride, prm, tail, hist)
     if (prm.hash6) LZ_GO(true); else LZ_GO(false);
 #undef LZ_GO
     return 0;

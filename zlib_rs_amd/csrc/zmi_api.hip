@@ -22,6 +22,13 @@ extern "C" int zmi_launch_inflate_verify(const uint8_t* d_in, const uint64_t* d_
                                          const uint32_t* d_crc, int32_t* d_status, int32_t* d_detail, hipStream_t stream);
 
 static thread_local std::string g_err;
+extern "C" int zmi_launch_inflate_shared_hist(uint32_t* d_hist, uint32_t n_streams, uint32_t hist, hipStream_t stream);
+extern "C" int zmi_launch_inflate_resolve_shared(uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_len, uint32_t n_streams,
+                                                 const uint64_t* d_bitmap, const uint64_t* d_bm_off, const uint32_t* d_order,
+                                                 const uint8_t* d_img, uint32_t hist, hipStream_t stream);
+extern "C" int zmi_launch_inflate_dictid(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_streams,
+                                         const uint32_t* d_dictid, int32_t* d_status, int32_t* d_detail, uint32_t* d_out_len,
+                                         hipStream_t stream);
 static int zmi_fail(int code, const char* what, hipError_t e = hipSuccess) {
     char buf[256];
     if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
@@ -106,6 +113,7 @@ struct zmi_ctx {
     zmi_buf comb;                       // zmi_checksum_combine_dev: the per-workgroup partial folds
     zmi_buf si_meta, si_work, si_seg;   // zmi_inflate_stream_dev: per-piece tables / one launch group's regions; find_cuts' segment table
     zmi_buf si_scan;                    // zmi_stream_find_blocks_dev: one window's survivor slots and validated list
+    zmi_buf dict;                       // the shared-dictionary batch calls: layout words and DICTID | deflate image | inflate image (zmi_sd_*)
 };
 
 static int zmi_reserve(zmi_buf& b, size_t bytes) {
@@ -161,6 +169,7 @@ extern "C" int zmi_ctx_destroy(zmi_ctx* c) {
     if (c->si_work.p) (void)hipFree(c->si_work.p);
     if (c->si_seg.p) (void)hipFree(c->si_seg.p);
     if (c->si_scan.p) (void)hipFree(c->si_scan.p);
+    if (c->dict.p) (void)hipFree(c->dict.p);
     for (int k = 0; k < 2; ++k) if (c->st_pin[k].p) (void)hipHostFree(c->st_pin[k].p);
     if (c->st_pin_ev_live) { (void)hipEventDestroy(c->st_pin_ev[0]); (void)hipEventDestroy(c->st_pin_ev[1]); }
     if (c->hb_live) {
@@ -269,6 +278,48 @@ extern "C" uint64_t zmi_deflate_bound(uint64_t n, int wrap) {
     return (b + 15) & ~15ull;
 }
 
+extern "C" uint64_t zmi_deflate_dict_bound(uint64_t n, int wrap) {
+    // ... and the DICTID behind the zlib header (deflate.rs:1572-1601)
+    uint64_t w = wrap == ZMI_WRAP_ZLIB ? 10u : (wrap == ZMI_WRAP_GZIP ? 18u : 0u);
+    uint64_t b = n + (n == 0) + (n < 9) + ((n + 7) >> 3) + 3 + w;
+    return (b + 15) & ~15ull;
+}
+
+// One preset dictionary for every shard / stream of a batch call (zmi_deflate_batch_shared_dict_dev,
+// zmi_inflate_batch_shared_dict_dev): what the kernels read lives in the context's `dict` scratch, built on the caller's stream by
+// zmi_launch_dict_image and the checksum kernel -- no value of it passes through the host.
+#define ZMI_SD_LAY_OFF 0u        // u64: 0            } the one-entry layout the checksum kernel reads the dictionary through
+#define ZMI_SD_LAY_LEN 8u        // u32: dict_len     }
+#define ZMI_SD_DICTID 12u        // u32: Adler-32 of all dict_len bytes
+#define ZMI_SD_DEF_IMG 64u       // deflate: the tail the match search can reach, <= 27 648 bytes (zmi_lz77_dict_image_len)
+#define ZMI_SD_INF_IMG 32832u    // inflate: the last <= 32 768 bytes, ending at a multiple of 1 KiB, zeros in front and 32 behind
+#define ZMI_SD_BYTES (ZMI_SD_INF_IMG + 32768u + 64u)
+struct zmi_sd_deflate {
+    const uint8_t* img;       // null / 0: no history (a dictionary shorter than 16 bytes, Z_HUFFMAN_ONLY)
+    uint32_t img_len;
+    const uint32_t* dictid;   // device word (zlib wrapper only)
+};
+struct zmi_sd_inflate {
+    const uint8_t* img;
+    uint32_t hist;            // min(dict_len, 32768)
+    const uint32_t* dictid;
+};
+static int zmi_sd_prepare(zmi_ctx* c, const void* d_dict, uint32_t dict_len, bool inflate, bool want_id, hipStream_t stream,
+                          uint32_t lead, uint32_t take, uint32_t pad) {
+    int rc = zmi_reserve(c->dict, ZMI_SD_BYTES);
+    if (rc) return rc;
+    uint8_t* base = (uint8_t*)c->dict.p;
+    int lrc = zmi_launch_dict_image((const uint8_t*)d_dict, dict_len, base + (inflate ? ZMI_SD_INF_IMG : ZMI_SD_DEF_IMG), lead, take, pad,
+                                    (uint64_t*)(base + ZMI_SD_LAY_OFF), (uint32_t*)(base + ZMI_SD_LAY_LEN), stream);
+    if (lrc) return zmi_fail(ZMI_E_ARG, "dictionary image layout");
+    if (want_id) {
+        zmi_scope_timer tm(c, ZMI_K_CHECKSUM, stream);
+        zmi_launch_checksum((const uint8_t*)d_dict, (const uint64_t*)(base + ZMI_SD_LAY_OFF), (const uint32_t*)(base + ZMI_SD_LAY_LEN), 1u, 1u,
+                            (uint32_t*)(base + ZMI_SD_DICTID), nullptr, stream);
+    }
+    return 0;
+}
+
 // search / parse effort per level: the MI355X analogue of CONFIGURATION_TABLE
 // (zlib-rs/src/deflate/algorithm/mod.rs:69-82).  Every position is searched in parallel, so the
 // chain budget is what the slowest lane of a wave spends; see DESIGN.md for the measured trade-off.
@@ -372,13 +423,44 @@ extern "C" int zmi_pack_slab_dev(zmi_ctx* c, const void* d_slots, uint64_t slot_
 static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
                             uint32_t max_len, int level, int strategy, int wrap, uint32_t chain_mode, uint32_t dict_len,
                             uint32_t window_bits, void* d_out, uint64_t out_stride, uint32_t* d_out_len, int32_t* d_status,
-                            void* stream_, int carry = -1, uint64_t launch_n = 0);
+                            void* stream_, int carry = -1, uint64_t launch_n = 0, const zmi_sd_deflate* sd = nullptr);
 
 extern "C" int zmi_deflate_batch_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
                                      uint32_t n, uint32_t max_len, int level, int strategy, int wrap, void* d_out,
                                      uint64_t out_stride, uint32_t* d_out_len, int32_t* d_status, void* stream_) {
     return zmi_deflate_impl(c, d_in, d_in_off, d_in_len, n, max_len, level, strategy, wrap, 0u, 0u, 15u, d_out, out_stride,
                             d_out_len, d_status, stream_);
+}
+
+// Every shard as deflateInit2_ + deflateSetDictionary(dict) + deflate(Z_FINISH) (zlib-rs/src/deflate.rs:499-564), one dictionary
+// for the whole call; see include/zmi355.h.  chain_mode 0: a shard's bytes depend on the dictionary, its own bytes, level, strategy
+// and wrap alone.
+extern "C" int zmi_deflate_batch_shared_dict_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                                 uint32_t n, uint32_t max_len, int level, int strategy, int wrap, const void* d_dict,
+                                                 uint32_t dict_len, void* d_out, uint64_t out_stride, uint32_t* d_out_len,
+                                                 int32_t* d_status, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (wrap != ZMI_WRAP_RAW && wrap != ZMI_WRAP_ZLIB) return zmi_fail(ZMI_E_ARG, "a preset dictionary needs wrap raw or zlib (a gzip member has no dictionary field)");
+    if (!d_dict || dict_len == 0u)
+        return zmi_deflate_impl(c, d_in, d_in_off, d_in_len, n, max_len, level, strategy, wrap, 0u, 0u, 15u, d_out, out_stride, d_out_len,
+                                d_status, stream_);
+    if (level < -1 || level > 9) return zmi_fail(ZMI_E_ARG, "level must be -1..9");
+    if (strategy < 0 || strategy > 4) return zmi_fail(ZMI_E_ARG, "strategy must be 0..4");
+    if (out_stride % 16u || out_stride < zmi_deflate_dict_bound(max_len, wrap))
+        return zmi_fail(ZMI_E_ARG, "out_stride must be a multiple of 16 and >= zmi_deflate_dict_bound(max_len)");
+    if (n == 0) return ZMI_E_OK;
+    zmi_sd_deflate sd;
+    {
+        ZMI_ON_DEVICE(c);
+        const uint32_t img_len = zmi_lz77_dict_image_len(dict_len);
+        int rc = zmi_sd_prepare(c, d_dict, dict_len, false, wrap == ZMI_WRAP_ZLIB, (hipStream_t)stream_, 0u, img_len, 16u);
+        if (rc) return rc;
+        sd.img = (const uint8_t*)c->dict.p + ZMI_SD_DEF_IMG;
+        sd.img_len = img_len;
+        sd.dictid = (const uint32_t*)((const uint8_t*)c->dict.p + ZMI_SD_DICTID);
+    }
+    return zmi_deflate_impl(c, d_in, d_in_off, d_in_len, n, max_len, level, strategy, wrap, 0u, 0u, 15u, d_out, out_stride, d_out_len,
+                            d_status, stream_, -1, 0, &sd);
 }
 
 // The shards are consecutive segments of ONE raw deflate stream, contiguous in d_in (d_in_off[i+1] = d_in_off[i] +
@@ -418,14 +500,15 @@ extern "C" int zmi_deflate_chain_window_dev(zmi_ctx* c, const void* d_in, const 
 static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
                             uint32_t max_len, int level, int strategy, int wrap, uint32_t chain_mode, uint32_t dict_len,
                             uint32_t window_bits, void* d_out, uint64_t out_stride, uint32_t* d_out_len, int32_t* d_status,
-                            void* stream_, int carry, uint64_t launch_n) {
+                            void* stream_, int carry, uint64_t launch_n, const zmi_sd_deflate* sd) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (level == -1) level = 6;
     if (level < 0 || level > 9) return zmi_fail(ZMI_E_ARG, "level must be -1..9");
     if (strategy < 0 || strategy > 4) return zmi_fail(ZMI_E_ARG, "strategy must be 0..4");
     if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_GZIP) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip");
-    if (out_stride % 16u || out_stride < zmi_deflate_bound(max_len, wrap))
-        return zmi_fail(ZMI_E_ARG, "out_stride must be a multiple of 16 and >= zmi_deflate_bound(max_len)");
+    if (out_stride % 16u || out_stride < (sd ? zmi_deflate_dict_bound(max_len, wrap) : zmi_deflate_bound(max_len, wrap)))
+        return zmi_fail(ZMI_E_ARG, sd ? "out_stride must be a multiple of 16 and >= zmi_deflate_dict_bound(max_len)"
+                                      : "out_stride must be a multiple of 16 and >= zmi_deflate_bound(max_len)");
     if (out_stride > 0xFFFFFFF0ull) return zmi_fail(ZMI_E_ARG, "shards larger than 3.5 GiB are not supported");
     if (n == 0) return ZMI_E_OK;
     hipStream_t stream = (hipStream_t)stream_;
@@ -487,6 +570,7 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     ep.strategy = (uint32_t)strategy;
     ep.chain_mode = chain_mode;
     ep.last_shard = n - 1u;
+    ep.dictid = (sd && wrap == ZMI_WRAP_ZLIB) ? sd->dictid : nullptr;
     if (level == 0) ep.strategy = 100u;           // stored blocks only (deflate_stored)
     ep.cost_parse = (level >= 3 && strategy != 2) ? 1u : 0u;
     if (const char* cp = zmi_tune("ZMI_COST_PARSE")) ep.cost_parse = atoi(cp) ? 1u : 0u;
@@ -572,7 +656,7 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
         // worst case: every block stored (5 header bytes + byte alignment); a block holds at least one sub-block of
         // block_tokens tokens (>= as many input bytes), stored sub-blocks are cut at 32 KiB
         const uint64_t min_block = ep.block_tokens < 32768u ? ep.block_tokens : 32768u;
-        uint64_t worst = psize + 6u * (psize / min_block + 3u) + 32u;
+        uint64_t worst = psize + 6u * (psize / min_block + 3u) + 32u + (sd ? 4u : 0u);   // (the DICTID in the first piece)
         if (region >= worst) break;
         --pieces;
     }
@@ -582,8 +666,11 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
         uint32_t cnt = (uint32_t)((n - first < group) ? (n - first) : group);
         {
             zmi_scope_timer tm(c, ZMI_K_LZ77, stream);
-            int lrc = zmi_launch_lz77((const uint8_t*)d_in, d_in_off, d_in_len, (uint32_t)first, cnt, (uint32_t*)c->match.p,
-                                      per_shard / 4u, lp, stream);
+            int lrc = (sd && sd->img_len)
+                          ? zmi_launch_lz77_dict((const uint8_t*)d_in, d_in_off, d_in_len, (uint32_t)first, cnt, (uint32_t*)c->match.p,
+                                                 per_shard / 4u, lp, sd->img, sd->img_len, stream)
+                          : zmi_launch_lz77((const uint8_t*)d_in, d_in_off, d_in_len, (uint32_t)first, cnt, (uint32_t*)c->match.p,
+                                            per_shard / 4u, lp, stream);
             if (lrc) return zmi_fail(ZMI_E_HIP, "lz77 launch setup", (hipError_t)lrc);
         }
         if (ep.cost_parse) {
@@ -792,13 +879,13 @@ static int zmi_inflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
                             uint32_t n, int wrap, void* d_out, const uint64_t* d_out_off,
                             const uint32_t* d_out_cap, const uint32_t* d_out_hist, uint32_t* d_out_len,
                             int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, const uint32_t* d_in_bit,
-                            uint32_t* d_resume, void* stream_, bool decode_only = false) {
+                            uint32_t* d_resume, void* stream_, bool decode_only = false, const zmi_sd_inflate* sd = nullptr) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_AUTO) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip/auto");
     if (n == 0) return ZMI_E_OK;
     hipStream_t stream = (hipStream_t)stream_;
     ZMI_ON_DEVICE(c);
-    int rc = zmi_reserve(c->inf_tmp, (size_t)n * 28u);
+    int rc = zmi_reserve(c->inf_tmp, (size_t)n * 32u);
     if (rc) return rc;
     uint64_t* d_bm_off = (uint64_t*)c->inf_tmp.p;
     uint32_t* d_used = (uint32_t*)(d_bm_off + n);
@@ -807,6 +894,11 @@ static int zmi_inflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     uint32_t* d_crc = d_adler + n;
     uint32_t* d_order = d_crc + n;   // workgroup -> stream: largest compressed size first (zmi_inflate_order_kernel)
     if (d_in_used) d_used = d_in_used;
+    if (sd) {   // the decode pass reads no history: all it needs is every stream's `hist` for its distance check and the FDICT branch
+        uint32_t* d_hist = d_order + n;
+        zmi_launch_inflate_shared_hist(d_hist, n, sd->hist, stream);
+        d_out_hist = d_hist;
+    }
     // bitmap scratch: 1 bit per byte of output capacity (+2 words per stream).  The capacities live on the
     // device, so the size comes from the context's limit; streams beyond it report Z_MEM_ERROR.
     const uint64_t out_limit = c->inflate_out_limit ? c->inflate_out_limit : c->scratch_limit;
@@ -839,6 +931,7 @@ static int zmi_inflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
                 (c->inf_limit_exact || out_limit <= (uint64_t)n * (64ull << 20) + (1ull << 20));
     if (!decode_only) {
     if (const char* jv = zmi_tune("ZMI_INF_JUMP")) jump = atoi(jv) != 0 && out_limit <= (1ull << 30);
+    if (sd) jump = false;   // the shared dictionary is read by the one-wave-per-stream pass only (its case is many small streams)
     if (jump && zmi_reserve(c->inf_ptr, (size_t)bm_words * 256u + 512u) != 0) jump = false;   // (no room: the serial pass needs none)
     {
         zmi_scope_timer tm(c, ZMI_K_RESOLVE, stream);
@@ -848,6 +941,9 @@ static int zmi_inflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
             for (uint64_t span = 3u; rounds < 34u && span < out_limit; span *= 3u) ++rounds;
             lrc = zmi_launch_resolve_jump((uint8_t*)d_out, d_out_off, d_out_len, n, (const uint64_t*)c->inf_bm.p, d_bm_off, (int32_t*)c->inf_ptr.p,
                                           bm_words * 64ull, rounds, (uint32_t*)((uint8_t*)c->inf_ptr.p + (size_t)bm_words * 256u), stream);
+        } else if (sd) {
+            lrc = zmi_launch_inflate_resolve_shared((uint8_t*)d_out, d_out_off, d_out_len, n, (const uint64_t*)c->inf_bm.p, d_bm_off, d_order,
+                                                    sd->img, sd->hist, stream);
         } else {
             lrc = zmi_launch_inflate_resolve((uint8_t*)d_out, d_out_off, d_out_len, n, (const uint64_t*)c->inf_bm.p, d_bm_off, d_out_hist, d_order, stream);
         }
@@ -863,9 +959,38 @@ static int zmi_inflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
         zmi_launch_inflate_verify((const uint8_t*)d_in, d_in_off, d_in_len, n, (uint32_t)wrap, d_check, d_adler, d_crc, d_status,
                                   d_detail, stream);
+        // inflateSetDictionary refuses a dictionary whose Adler-32 is not the stream's DICTID (inflate.rs:2492-2536)
+        if (sd && wrap == ZMI_WRAP_ZLIB)
+            zmi_launch_inflate_dictid((const uint8_t*)d_in, d_in_off, d_in_len, n, sd->dictid, d_status, d_detail, d_out_len, stream);
     }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;
+}
+
+// Every stream as inflateInit2_ + inflateSetDictionary(dict) + inflate(Z_FINISH), one dictionary for the whole call; see
+// include/zmi355.h.
+extern "C" int zmi_inflate_batch_shared_dict_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                                 uint32_t n, int wrap, const void* d_dict, uint32_t dict_len, void* d_out,
+                                                 const uint64_t* d_out_off, const uint32_t* d_out_cap, uint32_t* d_out_len,
+                                                 int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (wrap != ZMI_WRAP_RAW && wrap != ZMI_WRAP_ZLIB) return zmi_fail(ZMI_E_ARG, "a preset dictionary needs wrap raw or zlib (a gzip member has no dictionary field)");
+    if (!d_dict || dict_len == 0u || n == 0u)
+        return zmi_inflate_impl(c, d_in, d_in_off, d_in_len, n, wrap, d_out, d_out_off, d_out_cap, nullptr, d_out_len, d_status, d_in_used,
+                                d_detail, nullptr, nullptr, stream_);
+    zmi_sd_inflate sd;
+    {
+        ZMI_ON_DEVICE(c);
+        const uint32_t hist = dict_len < 32768u ? dict_len : 32768u;
+        const uint32_t shift = (hist + 1023u) & ~1023u;   // the resolve pass's staging block (RES_BLK, inflate.hip)
+        int rc = zmi_sd_prepare(c, d_dict, dict_len, true, wrap == ZMI_WRAP_ZLIB, (hipStream_t)stream_, shift - hist, hist, 32u);
+        if (rc) return rc;
+        sd.img = (const uint8_t*)c->dict.p + ZMI_SD_INF_IMG;
+        sd.hist = hist;
+        sd.dictid = (const uint32_t*)((const uint8_t*)c->dict.p + ZMI_SD_DICTID);
+    }
+    return zmi_inflate_impl(c, d_in, d_in_off, d_in_len, n, wrap, d_out, d_out_off, d_out_cap, nullptr, d_out_len, d_status, d_in_used,
+                            d_detail, nullptr, nullptr, stream_, false, &sd);
 }
 
 extern "C" int zmi_inflate_batch_dict_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,

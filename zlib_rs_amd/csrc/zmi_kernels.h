@@ -49,6 +49,8 @@ struct zmi_enc_params {
     uint32_t last_shard;
     uint32_t cost_parse;  // 1: tokens are chosen by a backward cost parse over the matches (levels 3-9, csrc/parse.hip);
                           // 0: by the lazy rule (levels 1, 2 -- greedy -- and Z_HUFFMAN_ONLY / level 0, which have no matches)
+    const uint32_t* dictid; // wrap 1 only, null = none: device word holding the Adler-32 of a preset dictionary; the zlib header
+                          // then carries FDICT and this DICTID (zmi_deflate_batch_shared_dict_dev)
 };
 
 // per-shard result codes written by the kernels (zlib numbering, zlib-rs/src/c_api.rs:140-148)
@@ -87,6 +89,15 @@ int zmi_launch_checksum(const uint8_t* d_data, const uint64_t* d_off, const uint
                         uint32_t kind, uint32_t* d_adler, uint32_t* d_crc, hipStream_t stream);
 int zmi_launch_lz77(const uint8_t* d_data, const uint64_t* d_off, const uint32_t* d_len, uint32_t first_shard,
                     uint32_t n_shards, uint32_t* d_match, uint64_t match_stride, zmi_lz_params prm, hipStream_t stream);
+// the match search with one preset dictionary in front of every shard (lz77.hip): d_img = zmi_launch_dict_image's image of
+// zmi_lz77_dict_image_len(dict_len) bytes (lead 0).  zmi_launch_dict_image: d_img[0, lead) = 0, then the last `take` bytes of the
+// dictionary, then `pad` zero bytes; d_lay_off / d_lay_len (may be null) receive the one-entry layout (0, dict_len)
+int zmi_launch_dict_image(const uint8_t* d_dict, uint32_t dict_len, uint8_t* d_img, uint32_t lead, uint32_t take, uint32_t pad,
+                          uint64_t* d_lay_off, uint32_t* d_lay_len, hipStream_t stream);
+uint32_t zmi_lz77_dict_image_len(uint32_t dict_len);
+int zmi_launch_lz77_dict(const uint8_t* d_data, const uint64_t* d_off, const uint32_t* d_len, uint32_t first_shard,
+                         uint32_t n_shards, uint32_t* d_match, uint64_t match_stride, zmi_lz_params prm, const uint8_t* d_img,
+                         uint32_t img_len, hipStream_t stream);
 int zmi_launch_encode(const uint8_t* d_data, const uint64_t* d_off, const uint32_t* d_len, uint32_t first_shard,
                       uint32_t n_shards, uint32_t* d_match, uint64_t match_stride, const uint32_t* d_adler,
                       const uint32_t* d_crc, uint8_t* d_out, uint64_t out_stride, uint32_t out_cap, uint32_t* d_out_len,

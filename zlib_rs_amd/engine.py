@@ -39,8 +39,9 @@ class Engine:
             self.L.zmi_ctx_destroy(self._ctx)
             self._ctx = None
 
-    def deflate_bound(self, n, wrap=WRAP_ZLIB):
-        return int(self.L.zmi_deflate_bound(int(n), int(wrap)))
+    def deflate_bound(self, n, wrap=WRAP_ZLIB, zdict=False):
+        """zdict: the bound of deflate_batch(..., zdict=...), which has the DICTID in its zlib header"""
+        return int((self.L.zmi_deflate_dict_bound if zdict else self.L.zmi_deflate_bound)(int(n), int(wrap)))
 
     # ---- synthetic benchmark shards (csrc/shardgen.h) ----
     def gen_shards(self, n_shards, shard_bytes=1 << 20, first_shard=0, seed=GEN_SEED, out=None, shard_step=1):
@@ -134,17 +135,27 @@ class Engine:
 
     # ---- deflate ----
     def deflate_batch(self, data, offsets, lengths, max_len, level=6, strategy=0, wrap=WRAP_ZLIB, out=None, out_len=None,
-                      status=None):
+                      status=None, zdict=None):
         """data: uint8 device tensor; offsets (uint64 as int64) / lengths (uint32 as int32) device tensors.
+        zdict: a uint8 device tensor, the one preset dictionary of every shard (deflateSetDictionary; wrap raw or zlib).
         Returns (out [n, stride] uint8, out_len [n] int32, status [n] int32)."""
         n = int(lengths.numel())
-        stride = self.deflate_bound(max_len, wrap)
+        stride = self.deflate_bound(max_len, wrap, zdict is not None)
         if out is None:
             out = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
         if out_len is None:
             out_len = torch.empty(n, dtype=torch.int32, device=self.device)
         if status is None:
             status = torch.empty(n, dtype=torch.int32, device=self.device)
+        if zdict is not None:
+            _check_zdict(zdict, self.device)
+            _lib.check(self.L.zmi_deflate_batch_shared_dict_dev(self._ctx, data.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n,
+                                                                int(max_len), int(level), int(strategy), int(wrap),
+                                                                zdict.data_ptr() if zdict.numel() else None, int(zdict.numel()),
+                                                                out.data_ptr(), out.stride(0) if out.dim() == 2 else stride,
+                                                                out_len.data_ptr(), status.data_ptr(), _stream_ptr()),
+                       "zmi_deflate_batch_shared_dict_dev")
+            return out, out_len, status
         _lib.check(self.L.zmi_deflate_batch_dev(self._ctx, data.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n,
                                                 int(max_len), int(level), int(strategy), int(wrap), out.data_ptr(),
                                                 out.stride(0) if out.dim() == 2 else stride, out_len.data_ptr(),
@@ -291,7 +302,10 @@ class Engine:
         return meta
 
     # ---- inflate ----
-    def inflate_batch(self, data, offsets, lengths, out, out_offsets, out_caps, wrap=WRAP_ZLIB, out_len=None, status=None):
+    def inflate_batch(self, data, offsets, lengths, out, out_offsets, out_caps, wrap=WRAP_ZLIB, out_len=None, status=None, zdict=None,
+                      in_used=None, detail=None):
+        """zdict: a uint8 device tensor, the one preset dictionary of every stream (inflateSetDictionary; wrap raw or zlib); in_used /
+        detail (int32 [n], with zdict only) receive the consumed input bytes and why a stream stopped"""
         n = int(lengths.numel())
         if out_len is None:
             out_len = torch.empty(n, dtype=torch.int32, device=self.device)
@@ -299,6 +313,16 @@ class Engine:
             status = torch.empty(n, dtype=torch.int32, device=self.device)
         # inflate keeps 1 bit of scratch per byte of output capacity; the capacities are device data, `out` bounds them
         _lib.check(self.L.zmi_ctx_set_inflate_out_limit(self._ctx, int(out.numel()) + (1 << 20)), "zmi_ctx_set_inflate_out_limit")
+        if zdict is not None:
+            _check_zdict(zdict, self.device)
+            _lib.check(self.L.zmi_inflate_batch_shared_dict_dev(self._ctx, data.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n,
+                                                                int(wrap), zdict.data_ptr() if zdict.numel() else None, int(zdict.numel()),
+                                                                out.data_ptr(), out_offsets.data_ptr(), out_caps.data_ptr(),
+                                                                out_len.data_ptr(), status.data_ptr(),
+                                                                in_used.data_ptr() if in_used is not None else None,
+                                                                detail.data_ptr() if detail is not None else None, _stream_ptr()),
+                       "zmi_inflate_batch_shared_dict_dev")
+            return out_len, status
         _lib.check(self.L.zmi_inflate_batch_dev(self._ctx, data.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n,
                                                 int(wrap), out.data_ptr(), out_offsets.data_ptr(), out_caps.data_ptr(),
                                                 out_len.data_ptr(), status.data_ptr(), _stream_ptr()),
@@ -316,6 +340,11 @@ class Engine:
         _lib.check(self.L.zmi_checksum_batch_dev(self._ctx, data.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, kind,
                                                  a.data_ptr(), c.data_ptr(), _stream_ptr()), "zmi_checksum_batch_dev")
         return a, c
+
+
+def _check_zdict(zdict, device):
+    if zdict.dtype != torch.uint8 or zdict.device != device or not zdict.is_contiguous():
+        raise ValueError("zdict must be a contiguous uint8 tensor on %s" % (device,))
 
 
 def _len_status(meta):

@@ -390,6 +390,73 @@ int zmi_inflate_stream_bits_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len,
                                 uint32_t piece_out_max, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used,
                                 int32_t* d_status, int32_t* d_detail, void* stream);
 
+/* ---- multi-member gzip files: what zmi_pack_slab_dev and the exchange calls write with the gzip wrapper, bgzip / BGZF, `cat a.gz b.gz`,
+ * pigz -i -- read by the reference one member after the other (libz-rs-sys/src/gz.rs:1464-1506).  Two calls, both asynchronous on
+ * `stream`, neither synchronises with the host, every result is a device word.
+ *
+ * zmi_gzip_find_members_dev  proposals of member starts.  d_starts[0] = 0 whenever in_len > 0; every further entry is a byte offset p
+ *                            with in[p .. p + 3) = 1f 8b 08, (FLG & 0xE0) == 0 and at least 18 bytes from p to the end.  Ascending and
+ *                            exact: every such position, the first `cap` of them if there are more; *d_n_starts = entries written
+ *                            (reading it is the caller's one synchronisation); the same entries on every run.  Any address, any
+ *                            in_len below 2^45.  A proposal may be false: compressed bytes pass the filter about once in 2^27
+ *                            positions (2^-24 for the three bytes, 1/8 for the flag bits), and a stored block may hold a whole gzip file.
+ *                            Scratch of the context: 12 bytes per 16 KiB of input.
+ * zmi_inflate_members_dev    decodes and verifies.  d_starts[0 .. n_starts): proposals, d_starts[0] = 0, strictly ascending, all below
+ *                            in_len (find_members' list as it stands, or the caller's).  Proposal k owns the input up to the next
+ *                            proposal (the last one to in_len); its output size is the ISIZE word that ends that range, its offset the
+ *                            sum of the sizes in front: all members decode in one group of launches straight into d_out, through the
+ *                            batch decoder (header incl. FEXTRA / FNAME / FCOMMENT / FHCRC, CRC-32 and ISIZE checked).
+ *                            Verified are the members of the unbroken chain from offset 0: status 0, ended exactly on the next
+ *                            proposal, produced exactly the planned size; the last one may end before in_len (*d_in_used tells).
+ *                            After the first pass ZMI_MM_REPAIR_PASSES repair passes run, enqueued unconditionally, working from
+ *                            device words (nothing to do: launches of empty streams): a member that wanted more input or room,
+ *                            whose ISIZE is more than deflate can reach or whose planned region crosses out_cap drops the
+ *                            proposal behind it, one that ended early exactly on a dropped proposal brings it back, offsets
+ *                            are planned again and everything from the first member that failed is decoded again.  Then the first
+ *                            member that still does not verify is decoded alone with all the input behind its start (at most
+ *                            2^32 - 1 bytes) and all the room left: on a valid file every call verifies at least one member.
+ *                            A valid file completes in ONE call if no two false proposals lie in the same member or in adjacent
+ *                            members AND out_cap has room for what the first pass plans (a false proposal adds the size its
+ *                            garbage ISIZE names, when deflate could reach it: with a tight out_cap a member pushed across
+ *                            out_cap costs a repair pass of its own); any other valid file in a finite number of ZMI_MM_AGAIN
+ *                            continuations.
+ *   *d_status   0: every member to the end of the list verified.  Z_DATA_ERROR (-3): the first member that does not verify is corrupt;
+ *               Z_BUF_ERROR (-5): truncated input, a member of 4 GiB or more, the output does not fit out_cap, or ZMI_MM_AGAIN;
+ *               ZMI_MM_BIG also names a member whose output is above the scratch limit (only when out_cap exceeds that limit);
+ *               ZMI_E_ARG (-103): d_starts[0] != 0, a list that does not ascend or reaches in_len -- the list
+ *               lives on the device, so this one arrives in the status word, not as the return value.
+ *               Never status 0 with wrong bytes; nothing at or behind d_out + out_cap is written.
+ *   *d_detail   the case in its low 8 bits, the index (into d_starts) of the offending proposal above them.
+ *               ZMI_MM_AGAIN: the passes ran out on a file that may be valid; continue at d_in + *d_in_used with the proposals
+ *               behind that offset (minus it, 0 in front) -- Engine.inflate_members does.  ZMI_MM_OUT: *d_out_len holds the total
+ *               the first pass planned, exact when no proposal was false.
+ *   In every other case *d_members = verified members, *d_in_used = the end of the last of them, *d_out_len = their output, and the
+ *   bytes d_out[0 .. *d_out_len) are right.  d_member_off (NULL or n_starts + 1 entries): the output offset of every verified member,
+ *   then the total -- the random-access index of the file.
+ *   Launch groups: the decode keeps one bit of scratch per byte of out_cap; an out_cap above the scratch limit
+ *   (zmi_ctx_set_scratch_limit -- not the inflate-out limit, which batch callers size for their own calls) is decoded in
+ *   out_cap / (limit / 2) + 1 launch groups per pass, a group holding the members planned into one window of limit / 2 bytes.
+ *   Bytes and words do not depend on the limit.  A member above half the limit that shares its window with members in front does
+ *   not fit its group's bitmap in the first pass; the next pass decodes from it on, where it leads its group and fits: each such
+ *   member costs a repair pass, and beyond them the last resort (one member alone, up to the whole limit) and ZMI_MM_AGAIN.
+ *   Event timing (zmi_ctx_get_timing): 5 = plan and group setup, 3 / 6 / 0 = decode, resolve, CRC-32, 4 = verify (the batch's and the
+ *   chain's, with the repair kernels), 7 = the offset scans.
+ *   in_len 0: status 0, no members, whatever n_starts is.  Scratch of the context: 88 bytes per proposal. */
+#define ZMI_MM_REPAIR_PASSES 2
+#define ZMI_MM_HEADER 1  /* bad member header (Z_DATA_ERROR) */
+#define ZMI_MM_TRUNC 2   /* the input ends inside the member (Z_BUF_ERROR) */
+#define ZMI_MM_DATA 3    /* a corrupt block (Z_DATA_ERROR) */
+#define ZMI_MM_CHECK 4   /* wrong CRC-32 (Z_DATA_ERROR) */
+#define ZMI_MM_LENGTH 5  /* wrong ISIZE (Z_DATA_ERROR) */
+#define ZMI_MM_OUT 6     /* the output does not fit out_cap (Z_BUF_ERROR) */
+#define ZMI_MM_BIG 7     /* a member of 4 GiB or more, compressed or raw, or with more output than the scratch limit (Z_BUF_ERROR) */
+#define ZMI_MM_AGAIN 8   /* repair passes exhausted: continue at *d_in_used (Z_BUF_ERROR) */
+int zmi_gzip_find_members_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, uint64_t* d_starts, uint32_t cap, uint32_t* d_n_starts,
+                              void* stream);
+int zmi_inflate_members_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, const uint64_t* d_starts, uint32_t n_starts, void* d_out,
+                            uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used, uint32_t* d_members, uint64_t* d_member_off,
+                            int32_t* d_status, int32_t* d_detail, void* stream);
+
 /* ---- host-buffer convenience wrappers: copy in, run the batch on the GPU, copy back ---- */
 int zmi_deflate_batch(zmi_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_shards,
                       int level, int strategy, int wrap, uint8_t* out, uint64_t out_stride, uint32_t* out_len,

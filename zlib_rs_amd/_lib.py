@@ -57,6 +57,9 @@ def lib():
     # ... of streams without flush points: cuts at bit positions, proposed by the block scan (csrc/blockscan.hip)
     L.zmi_stream_find_blocks_dev.argtypes = [vp, vp, u64, i32, u64, vp, u32, vp, vp]
     L.zmi_inflate_stream_bits_dev.argtypes = [vp, vp, u64, i32, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp]
+    # multi-member gzip files: proposals of member starts, then every member decoded in place and verified
+    L.zmi_gzip_find_members_dev.argtypes = [vp, vp, u64, vp, u32, vp, vp]
+    L.zmi_inflate_members_dev.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp]
     # the multi-GPU stitch (csrc/exchange.hip); RCCL itself is loaded by the library on first use
     L.zmi_comm_unique_id.argtypes = [vp]
     L.zmi_comm_create.argtypes = [C.POINTER(vp), vp, i32, i32, vp]

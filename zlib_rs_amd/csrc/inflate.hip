@@ -2767,3 +2767,285 @@ extern "C" int zmi_launch_si_clamp(const uint32_t* d_len, const uint64_t* d_off,
     ZMI_LAUNCH(zmi_si_clamp_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_len, d_off, n, out_cap, d_clen);
     return 0;
 }
+
+// ---- multi-member gzip files (zmi_inflate_members_dev): plan, verify, repair --------------------------------------------------------
+// A list of proposed member starts (zmi_gzip_find_members_dev, or the caller's) becomes a batch for the decoder above: proposal k
+// owns the input up to the next LIVE proposal, its output size is the ISIZE word in the last four bytes of that range, its output
+// offset the exclusive sum of those sizes -- every member decodes straight into its final place.  A proposal may be false (the
+// magic inside a stored block), so nothing counts until it is verified: status 0 (header, CRC-32 and ISIZE checked by the batch
+// verify), ended exactly on the next live start, produced exactly the planned size; the accepted members are the unbroken chain
+// from offset 0.  Between the passes every member that failed repairs its own range -- one that wanted more input or room (or whose
+// ISIZE cannot be true: more than 1032 bytes per input byte, the most deflate can do) drops the live proposal behind it, one that
+// ended early exactly on a dropped proposal brings it back -- and the next pass decodes again from the first member that failed.
+// All of it works from device words; a pass with nothing left to do launches decodes of empty streams.  DESIGN.md section 16.
+#define MM_F_LIVE 1u
+#define MM_F_LAST 2u    // no live proposal behind it: owns the input to in_len and may end before it
+#define MM_F_BIG 4u     // owns 4 GiB or more
+#define MM_F_IMPL 8u    // cannot be a whole member: fewer than 18 bytes, or an ISIZE deflate cannot reach from that many bytes
+#define MM_W_BAD 0u     // words: the list is not ascending from 0 / reaches in_len
+#define MM_W_FIRST 1u   // first member that did not verify in the pass just run (n: none)
+#define MM_W_REDO 2u    // members from here on are decoded in this pass
+#define MM_W_LASTLIVE 3u  // 1 + the highest live proposal
+#define MM_W_LR 4u      // the last-resort decode ran
+#define MM_W_LRCLIP 5u  // ... with less room than out_cap leaves (4 GiB - 1 or the scratch limit)
+#define MM_W_TOTAL0 8u  // (and 9: one u64) the total the first pass planned -- what ZMI_MM_OUT reports, exact when no proposal was false
+#define MM_D_HEADER 1
+#define MM_D_TRUNC 2
+#define MM_D_DATA 3
+#define MM_D_CHECK 4
+#define MM_D_LENGTH 5
+#define MM_D_OUT 6
+#define MM_D_BIG 7
+#define MM_D_AGAIN 8
+#define MM_E_ARG (-103)
+
+struct MmTab {          // per proposal
+    const uint64_t* start;
+    uint32_t n;
+    uint32_t* live;
+    uint32_t* owned;
+    uint32_t* size;
+    uint32_t* flags;
+    int32_t* st;
+    int32_t* det;
+    uint32_t* used;
+    uint32_t* olen;
+    uint64_t* off;      // n + 1
+    uint32_t* w;        // MM_W_*
+};
+
+static __device__ __forceinline__ uint32_t mm_next_live(const MmTab& T, uint32_t k) {
+    uint32_t j = k + 1u;
+    while (j < T.n && !T.live[j]) ++j;
+    return j;
+}
+// is member k decoded in this pass (by one of its launch groups)?
+static __device__ __forceinline__ bool mm_attempt(const MmTab& T, uint32_t k, uint64_t out_cap) {
+    const uint32_t f = T.flags[k];
+    return (f & MM_F_LIVE) && !(f & (MM_F_BIG | MM_F_IMPL)) && k >= T.w[MM_W_REDO] && T.off[k] + T.size[k] <= out_cap;
+}
+static __device__ __forceinline__ bool mm_ok(const MmTab& T, uint32_t k, uint64_t out_cap) {
+    return mm_attempt(T, k, out_cap) && T.st[k] == ZMI_OK && T.olen[k] == T.size[k] && (T.used[k] == T.owned[k] || (T.flags[k] & MM_F_LAST));
+}
+
+__global__ void __launch_bounds__(256) zmi_mm_init_kernel(MmTab T, uint64_t in_len) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= T.n) return;
+    T.live[k] = 1u;
+    const uint64_t p = T.start[k];
+    if (p >= in_len || (k == 0u ? p != 0u : p <= T.start[k - 1u])) atomicOr(&T.w[MM_W_BAD], 1u);
+}
+
+__global__ void __launch_bounds__(256) zmi_mm_plan_kernel(MmTab T, const uint8_t* __restrict__ in, uint64_t in_len, uint32_t pass) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k == 0u) {   // (nobody reads these words between the repair of the pass before and the setup of this one)
+        if (pass) T.w[MM_W_REDO] = T.w[MM_W_FIRST];
+        T.w[MM_W_FIRST] = T.n;
+        T.w[MM_W_LASTLIVE] = 0u;
+    }
+    if (k >= T.n) return;
+    uint32_t f = 0, own = 0, sz = 0;
+    if (!T.w[MM_W_BAD] && T.live[k]) {
+        const uint32_t j = mm_next_live(T, k);
+        const uint64_t a = T.start[k], b = j < T.n ? T.start[j] : in_len, o = b - a;
+        f = MM_F_LIVE | (j < T.n ? 0u : MM_F_LAST);
+        if (o > 0xFFFFFFFFull) { f |= MM_F_BIG; own = 0xFFFFFFFFu; }
+        else {
+            own = (uint32_t)o;
+            if (own < 18u) f |= MM_F_IMPL;
+            else {
+                const uint8_t* e = in + b - 4u;
+                const uint32_t isz = (uint32_t)e[0] | ((uint32_t)e[1] << 8) | ((uint32_t)e[2] << 16) | ((uint32_t)e[3] << 24);
+                if ((uint64_t)isz > 1032ull * o + 1024ull) f |= MM_F_IMPL; else sz = isz;
+            }
+        }
+    }
+    T.flags[k] = f;
+    T.owned[k] = own;
+    T.size[k] = sz;
+}
+
+// one launch group: the members whose planned offset lies in [grp * half, + half) (half 0: all of them)
+__global__ void __launch_bounds__(256) zmi_mm_setup_kernel(MmTab T, uint64_t out_cap, uint64_t half, uint32_t grp, uint64_t* __restrict__ g_ioff,
+                                                           uint32_t* __restrict__ g_in, uint64_t* __restrict__ g_ooff, uint32_t* __restrict__ g_cap) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= T.n) return;
+    const bool on = mm_attempt(T, k, out_cap) && (half == 0u || T.off[k] / half == grp);
+    g_ioff[k] = on ? T.start[k] : 0ull;
+    g_in[k] = on ? T.owned[k] : 0u;
+    g_ooff[k] = on ? T.off[k] : 0ull;
+    g_cap[k] = on ? T.size[k] : 0u;
+}
+__global__ void __launch_bounds__(256) zmi_mm_collect_kernel(MmTab T, uint64_t out_cap, uint64_t half, uint32_t grp, const uint32_t* __restrict__ g_olen,
+                                                             const int32_t* __restrict__ g_st, const uint32_t* __restrict__ g_used,
+                                                             const int32_t* __restrict__ g_det) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= T.n) return;
+    if (!(mm_attempt(T, k, out_cap) && (half == 0u || T.off[k] / half == grp))) return;
+    T.olen[k] = g_olen[k]; T.st[k] = g_st[k]; T.used[k] = g_used[k]; T.det[k] = g_det[k];
+}
+
+__global__ void __launch_bounds__(256) zmi_mm_verify_kernel(MmTab T, uint64_t out_cap, uint32_t pass) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k == 0u && pass == 0u) *(uint64_t*)(T.w + MM_W_TOTAL0) = T.off[T.n];
+    if (k >= T.n || !(T.flags[k] & MM_F_LIVE)) return;
+    atomicMax(&T.w[MM_W_LASTLIVE], k + 1u);
+    if (k < T.w[MM_W_REDO]) return;   // verified by an earlier pass
+    if (!mm_ok(T, k, out_cap)) atomicMin(&T.w[MM_W_FIRST], k);
+}
+
+// Every failed member acts on the proposals of its own range alone (live[k + 1 .. next live]): no two threads touch the same entry.
+__global__ void __launch_bounds__(256) zmi_mm_repair_kernel(MmTab T, uint64_t out_cap) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= T.n || !(T.flags[k] & MM_F_LIVE) || k < T.w[MM_W_REDO] || mm_ok(T, k, out_cap)) return;
+    const bool tried = mm_attempt(T, k, out_cap);
+    const uint32_t j = mm_next_live(T, k);
+    // the member whose planned region crosses out_cap: its ISIZE may be the payload bytes in front of a false proposal (one that
+    // is too large but not impossible), and nothing behind it was decoded.  If the size is true the call ends with ZMI_MM_OUT anyway.
+    const bool crosses = !(T.flags[k] & (MM_F_BIG | MM_F_IMPL)) && T.off[k] <= out_cap && T.off[k] + T.size[k] > out_cap;
+    if ((T.flags[k] & MM_F_IMPL) || crosses || (tried && T.st[k] == ZMI_BUF_ERROR)) {
+        if (j < T.n) T.live[j] = 0u;                  // wanted more: the proposal behind it was false (or this one is)
+    } else if (tried && T.st[k] == ZMI_OK && T.used[k] < T.owned[k]) {
+        const uint64_t e = T.start[k] + T.used[k];    // ended early: exactly on a proposal that was dropped?
+        for (uint32_t d = k + 1u; d < j; ++d)
+            if (T.start[d] == e) { T.live[d] = 1u; break; }
+    }
+}
+
+// Last resort: the first member that still does not verify gets all the input behind its start and all the room that is left,
+// alone -- its start is the end of a verified member, so on a valid file it decodes, and the call makes progress.
+__global__ void __launch_bounds__(64) zmi_mm_lr_setup_kernel(MmTab T, uint64_t in_len, uint64_t out_cap, uint64_t room_max, uint64_t* l_ioff,
+                                                             uint32_t* l_in, uint64_t* l_ooff, uint32_t* l_cap) {
+    if (threadIdx.x != 0) return;
+    const uint32_t F = T.w[MM_W_FIRST];
+    l_ioff[0] = 0; l_in[0] = 0; l_ooff[0] = 0; l_cap[0] = 0;
+    T.w[MM_W_LR] = 0; T.w[MM_W_LRCLIP] = 0;
+    if (T.w[MM_W_BAD] || F >= T.n) return;
+    const uint64_t a = T.start[F], rem = in_len - a, base = T.off[F], room = out_cap - base;
+    uint64_t cap = room < 0xFFFFFFFFull ? room : 0xFFFFFFFFull;
+    if (cap > room_max) cap = room_max;
+    l_ioff[0] = a;
+    l_in[0] = rem < 0xFFFFFFFFull ? (uint32_t)rem : 0xFFFFFFFFu;
+    l_ooff[0] = base;
+    l_cap[0] = (uint32_t)cap;
+    T.w[MM_W_LR] = 1u;
+    T.w[MM_W_LRCLIP] = cap < room ? 1u : 0u;
+}
+
+// rank = exclusive count of live proposals (n + 1 entries); lr_*: the last-resort decode's words; chk: its trailer CRC-32 and the
+// CRC-32 of what it produced
+__global__ void __launch_bounds__(256) zmi_mm_final_kernel(MmTab T, const uint8_t* __restrict__ in, uint64_t in_len, uint64_t out_cap,
+                                                           const uint64_t* __restrict__ rank, const uint32_t* lr_olen, const int32_t* lr_st,
+                                                           const uint32_t* lr_used, const int32_t* lr_det, const uint32_t* chk_trailer,
+                                                           const uint32_t* chk_crc, uint64_t* out_len, uint64_t* in_used, uint32_t* members,
+                                                           uint64_t* member_off, int32_t* status, int32_t* detail) {
+    const uint32_t F = T.w[MM_W_BAD] ? 0u : T.w[MM_W_FIRST];
+    if (member_off)
+        for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < F; k += gridDim.x * 256u)
+            if (T.flags[k] & MM_F_LIVE) member_off[rank[k]] = T.off[k];
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    if (T.w[MM_W_BAD]) {
+        *status = MM_E_ARG; *detail = 0; *members = 0; *in_used = 0; *out_len = 0;
+        if (member_off) member_off[0] = 0;
+        return;
+    }
+    if (F >= T.n) {
+        const uint32_t ll = T.w[MM_W_LASTLIVE] - 1u;   // (proposal 0 is always live)
+        *status = ZMI_OK; *detail = 0; *members = (uint32_t)rank[T.n]; *in_used = T.start[ll] + T.used[ll]; *out_len = T.off[T.n];
+        if (member_off) member_off[rank[T.n]] = T.off[T.n];
+        return;
+    }
+    const uint32_t M = (uint32_t)rank[F];
+    const uint64_t a = T.start[F], base = T.off[F];
+    const int32_t st = lr_st[0], det = lr_det[0];
+    int32_t rs = ZMI_DATA_ERROR, kind = MM_D_DATA;
+    uint32_t idx = F, m = M;
+    uint64_t used = a, total = base;
+    if (st == ZMI_OK) {
+        m = M + 1u; used = a + lr_used[0]; total = base + lr_olen[0];
+        if (member_off) member_off[M] = base;
+        // anything left to try?  (the offsets of the proposals behind were planned from a range that was not this member's)
+        uint32_t lo = F + 1u, hi = T.n;
+        while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2u; if (T.start[mid] >= used) hi = mid; else lo = mid + 1u; }
+        if (lo < T.n) { rs = ZMI_BUF_ERROR; kind = MM_D_AGAIN; idx = lo; }
+        else { rs = ZMI_OK; kind = 0; idx = 0; }
+    } else if (st == ZMI_BUF_ERROR && det == 2) {
+        rs = ZMI_BUF_ERROR;
+        if (T.w[MM_W_LRCLIP]) kind = MM_D_BIG;
+        else {
+            const uint64_t planned = *(const uint64_t*)(T.w + MM_W_TOTAL0);
+            kind = MM_D_OUT;
+            total = planned > base + lr_olen[0] ? planned : base + lr_olen[0];
+            if (total <= out_cap) total = out_cap + 1u;
+        }
+    } else if (st == ZMI_BUF_ERROR) {
+        rs = ZMI_BUF_ERROR;
+        kind = in_len - a > 0xFFFFFFFFull ? MM_D_BIG : MM_D_TRUNC;
+    } else if (st == ZMI_NO_SCRATCH) {
+        rs = ZMI_BUF_ERROR; kind = MM_D_BIG;   // (cannot happen: the last resort's room is clipped to what the bitmap covers)
+    } else if (st == ZMI_DATA_ERROR) {
+        const uint8_t* h = in + a;
+        if (in_len - a < 4u || h[0] != 0x1Fu || h[1] != 0x8Bu || h[2] != 8u || (h[3] & 0xE0u)) kind = MM_D_HEADER;
+        else if (det >= 16) kind = MM_D_DATA;
+        else kind = chk_trailer[0] != chk_crc[0] ? MM_D_CHECK : MM_D_LENGTH;
+    } else {
+        rs = st;
+    }
+    *status = rs; *detail = kind | (int32_t)(idx << 8); *members = m; *in_used = used; *out_len = total;
+    if (member_off) member_off[m] = kind == MM_D_OUT ? base : total;
+}
+
+static MmTab mm_tab(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w) {
+    MmTab T;   // d_tab: eight u32[n] tables
+    T.start = d_starts; T.n = n;
+    T.live = d_tab; T.owned = d_tab + n; T.size = d_tab + 2u * (size_t)n; T.flags = d_tab + 3u * (size_t)n;
+    T.st = (int32_t*)(d_tab + 4u * (size_t)n); T.det = (int32_t*)(d_tab + 5u * (size_t)n); T.used = d_tab + 6u * (size_t)n; T.olen = d_tab + 7u * (size_t)n;
+    T.off = d_off; T.w = d_w;
+    return T;
+}
+extern "C" int zmi_launch_mm_init(const uint64_t* d_starts, uint32_t n, uint64_t in_len, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w,
+                                  hipStream_t stream) {
+    ZMI_LAUNCH(zmi_mm_init_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, mm_tab(d_starts, n, d_tab, d_off, d_w), in_len);
+    return 0;
+}
+extern "C" int zmi_launch_mm_plan(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w, const uint8_t* d_in,
+                                  uint64_t in_len, uint32_t pass, hipStream_t stream) {
+    ZMI_LAUNCH(zmi_mm_plan_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, mm_tab(d_starts, n, d_tab, d_off, d_w), d_in, in_len, pass);
+    return 0;
+}
+extern "C" int zmi_launch_mm_setup(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w, uint64_t out_cap,
+                                   uint64_t half, uint32_t grp, uint64_t* g_ioff, uint32_t* g_in, uint64_t* g_ooff, uint32_t* g_cap,
+                                   hipStream_t stream) {
+    ZMI_LAUNCH(zmi_mm_setup_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, mm_tab(d_starts, n, d_tab, d_off, d_w), out_cap, half, grp, g_ioff, g_in, g_ooff, g_cap);
+    return 0;
+}
+extern "C" int zmi_launch_mm_collect(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w, uint64_t out_cap,
+                                     uint64_t half, uint32_t grp, const uint32_t* g_olen, const int32_t* g_st, const uint32_t* g_used,
+                                     const int32_t* g_det, hipStream_t stream) {
+    ZMI_LAUNCH(zmi_mm_collect_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, mm_tab(d_starts, n, d_tab, d_off, d_w), out_cap, half, grp, g_olen, g_st, g_used, g_det);
+    return 0;
+}
+extern "C" int zmi_launch_mm_verify(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w, uint64_t out_cap,
+                                    uint32_t pass, int repair, hipStream_t stream) {
+    ZMI_LAUNCH(zmi_mm_verify_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, mm_tab(d_starts, n, d_tab, d_off, d_w), out_cap, pass);
+    if (repair) ZMI_LAUNCH(zmi_mm_repair_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, mm_tab(d_starts, n, d_tab, d_off, d_w), out_cap);
+    return 0;
+}
+extern "C" int zmi_launch_mm_lr_setup(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w, uint64_t in_len,
+                                      uint64_t out_cap, uint64_t room_max, uint64_t* l_ioff, uint32_t* l_in, uint64_t* l_ooff, uint32_t* l_cap,
+                                      hipStream_t stream) {
+    ZMI_LAUNCH(zmi_mm_lr_setup_kernel, dim3(1), dim3(64), 0, stream, mm_tab(d_starts, n, d_tab, d_off, d_w), in_len, out_cap, room_max, l_ioff, l_in,
+               l_ooff, l_cap);
+    return 0;
+}
+extern "C" int zmi_launch_mm_final(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w, const uint8_t* d_in,
+                                   uint64_t in_len, uint64_t out_cap, const uint64_t* d_rank, const uint32_t* lr_olen, const int32_t* lr_st,
+                                   const uint32_t* lr_used, const int32_t* lr_det, const uint32_t* chk_trailer, const uint32_t* chk_crc,
+                                   uint64_t* d_out_len, uint64_t* d_in_used, uint32_t* d_members, uint64_t* d_member_off, int32_t* d_status,
+                                   int32_t* d_detail, hipStream_t stream) {
+    uint32_t blocks = (n + 255u) / 256u;
+    if (blocks > 1024u) blocks = 1024u;
+    ZMI_LAUNCH(zmi_mm_final_kernel, dim3(blocks), dim3(256), 0, stream, mm_tab(d_starts, n, d_tab, d_off, d_w), d_in, in_len, out_cap, d_rank, lr_olen,
+               lr_st, lr_used, lr_det, chk_trailer, chk_crc, d_out_len, d_in_used, d_members, d_member_off, d_status, d_detail);
+    return 0;
+}

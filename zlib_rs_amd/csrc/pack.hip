@@ -238,3 +238,117 @@ extern "C" int zmi_launch_frame(uint8_t* d_out, uint64_t out_cap, uint32_t wrap,
                d_out_len, d_status, d_piece_st, n_st, d_index, n_index);
     return 0;
 }
+
+// ---- proposals of gzip member starts (zmi_gzip_find_members_dev) -----------------------------------------------------------------
+// A member announces itself: 1f 8b 08 and a FLG byte whose reserved bits are clear (RFC 1952; the reader of multi-member files,
+// libz-rs-sys/src/gz.rs:1464-1506, looks for the same bytes behind every trailer).  Position p is an entry if p == 0, or if those
+// four bytes stand at p and at least 18 bytes remain (10 of header, 8 of trailer).  One pass, 16-byte loads: the buffer is taken
+// as 16-byte lines of the ADDRESS space (line 0 holds the first input byte at offset `head`), a lane owns the 16 start positions
+// of its line and sees three bytes of the next line -- its neighbour's first dword, moved over by one DPP shift; lane 63 loads it.
+// A hit belongs to the line its first byte lies in, so a pattern across a lane, wave or workgroup boundary is found exactly once.
+// A workgroup takes MM_LINES lines per thread (16 KiB); pass 1 counts, the scan of pack.hip turns the counts into offsets, pass 2
+// reads again only the segments that hold a hit (a real file: one segment in a few dozen) and writes every hit at its rank.
+#define MM_T 256u
+#define MM_LINES 4u
+#define MM_SEG (MM_T * MM_LINES * 16u)
+
+// the 16 bytes of line `li` (bytes outside the input read as zero)
+static __device__ __forceinline__ zmi_b16 mm_line(const uint8_t* line0, uint64_t li, uint32_t head, uint64_t n) {
+    const uint64_t q = li * 16u;               // offset of the line from line0; input byte p stands at q = p + head
+    const uint64_t end = n + head;             // first offset behind the input
+    zmi_b16 r;
+    if (q >= head && q + 16u <= end) {
+        const uint4 v = *(const uint4*)(line0 + q);
+        r.w[0] = v.x; r.w[1] = v.y; r.w[2] = v.z; r.w[3] = v.w;
+    } else {
+        uint64_t lo = 0, hi = 0;
+        for (uint32_t i = 0; i < 16u; ++i) {
+            const uint64_t x = q + i;
+            const uint64_t b = (x >= head && x < end) ? (uint64_t)line0[x] << (8u * (i & 7u)) : 0ull;
+            if (i < 8u) lo |= b; else hi |= b;
+        }
+        r.w[0] = (uint32_t)lo; r.w[1] = (uint32_t)(lo >> 32); r.w[2] = (uint32_t)hi; r.w[3] = (uint32_t)(hi >> 32);
+    }
+    return r;
+}
+
+// bit i set: input position 16 * li - head + i is an entry
+static __device__ __forceinline__ uint32_t mm_hits(const uint8_t* line0, uint64_t li, uint32_t head, uint64_t n) {
+    const zmi_b16 c = mm_line(line0, li, head, n);
+    uint32_t fill = 0;
+    if (zmi_lane() == 63u) fill = mm_line(line0, li + 1u, head, n).w[0];
+    const uint32_t nx = zmi_lane_down1(c.w[0], fill);
+    uint32_t m = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < 16u; ++i) {
+        const uint32_t lo = c.w[i >> 2], hi = (i >> 2) == 3u ? nx : c.w[(i >> 2) + 1u];
+        const uint32_t v = (i & 3u) ? (lo >> (8u * (i & 3u))) | (hi << (32u - 8u * (i & 3u))) : lo;
+        if ((v & 0xE0FFFFFFu) == 0x00088B1Fu) m |= 1u << i;
+    }
+    // positions in front of the input, position 0 (always an entry) and the last 17 positions
+    const uint64_t q = li * 16u;
+    if (q <= head || q + 33u > n + head) {   // (only the first line and the last three)
+        for (uint32_t i = 0; i < 16u; ++i) {
+            const uint64_t x = q + i;
+            if (x < head || x - head + 18u > n) m &= ~(1u << i);
+            if (x == head && n != 0u) m |= 1u << i;
+        }
+    }
+    return m;
+}
+
+__global__ void __launch_bounds__(MM_T) zmi_mm_count_kernel(const uint8_t* __restrict__ line0, uint32_t head, uint64_t n,
+                                                            uint32_t* __restrict__ cnt) {
+    __shared__ uint32_t wsum[MM_T / 64u];
+    const uint32_t t = threadIdx.x;
+    uint32_t c = 0;
+    for (uint32_t r = 0; r < MM_LINES; ++r)
+        c += (uint32_t)__popc(mm_hits(line0, ((uint64_t)blockIdx.x * MM_LINES + r) * MM_T + t, head, n));
+    c = zmi_wave_sum(c);
+    if (zmi_lane() == 0u) wsum[zmi_wave()] = c;
+    __syncthreads();
+    if (t == 0) cnt[blockIdx.x] = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+}
+
+__global__ void __launch_bounds__(MM_T) zmi_mm_gather_kernel(const uint8_t* __restrict__ line0, uint32_t head, uint64_t n,
+                                                             const uint32_t* __restrict__ cnt, const uint64_t* __restrict__ off, uint32_t nseg,
+                                                             uint64_t* __restrict__ starts, uint32_t cap, uint32_t* __restrict__ n_starts) {
+    __shared__ uint32_t wsum[MM_T / 64u];
+    const uint32_t t = threadIdx.x;
+    if (blockIdx.x == 0 && t == 0) { const uint64_t all = off[nseg]; *n_starts = all < cap ? (uint32_t)all : cap; }
+    if (cnt[blockIdx.x] == 0u) return;   // (the whole workgroup)
+    uint64_t at = off[blockIdx.x];
+    for (uint32_t r = 0; r < MM_LINES; ++r) {
+        const uint64_t li = ((uint64_t)blockIdx.x * MM_LINES + r) * MM_T + t;
+        uint32_t m = mm_hits(line0, li, head, n);
+        const uint32_t c = (uint32_t)__popc(m);
+        const uint32_t incl = zmi_wave_incl_scan(c);
+        __syncthreads();   // (wsum of the round before has been read)
+        if (zmi_lane() == 63u) wsum[zmi_wave()] = incl;
+        __syncthreads();
+        uint32_t before = incl - c, total = 0;
+        for (uint32_t w = 0; w < MM_T / 64u; ++w) { if (w < zmi_wave()) before += wsum[w]; total += wsum[w]; }
+        uint64_t k = at + before;
+        while (m) {
+            const uint32_t i = (uint32_t)__ffs(m) - 1u;
+            m &= m - 1u;
+            if (k < cap) starts[k] = li * 16u + i - head;
+            ++k;
+        }
+        at += total;
+    }
+}
+
+extern "C" uint32_t zmi_mm_scan_segments(uint64_t in_len, uint32_t head) { return (uint32_t)((in_len + head + MM_SEG - 1u) / MM_SEG); }
+// d_cnt u32[nseg], d_off u64[nseg + 1]; in_len > 0
+extern "C" int zmi_launch_mm_find(const uint8_t* d_in, uint64_t in_len, uint32_t* d_cnt, uint64_t* d_off, uint64_t* d_starts, uint32_t cap,
+                                  uint32_t* d_n_starts, hipStream_t stream) {
+    const uint32_t head = (uint32_t)((uintptr_t)d_in & 15u);
+    const uint8_t* line0 = d_in - head;
+    const uint32_t nseg = zmi_mm_scan_segments(in_len, head);
+    ZMI_LAUNCH(zmi_mm_count_kernel, dim3(nseg), dim3(MM_T), 0, stream, line0, head, in_len, d_cnt);
+    ZMI_LAUNCH(zmi_scan_sizes_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t*)d_cnt, nseg, d_off, (const uint64_t*)nullptr);
+    ZMI_LAUNCH(zmi_mm_gather_kernel, dim3(nseg), dim3(MM_T), 0, stream, line0, head, in_len, (const uint32_t*)d_cnt, (const uint64_t*)d_off, nseg,
+               d_starts, cap, d_n_starts);
+    return 0;
+}

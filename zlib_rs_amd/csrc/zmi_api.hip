@@ -113,6 +113,7 @@ struct zmi_ctx {
     zmi_buf comb;                       // zmi_checksum_combine_dev: the per-workgroup partial folds
     zmi_buf si_meta, si_work, si_seg;   // zmi_inflate_stream_dev: per-piece tables / one launch group's regions; find_cuts' segment table
     zmi_buf si_scan;                    // zmi_stream_find_blocks_dev: one window's survivor slots and validated list
+    zmi_buf mm_scan, mm_meta;           // zmi_gzip_find_members_dev: segment counts and offsets; zmi_inflate_members_dev: its tables
     zmi_buf dict;                       // the shared-dictionary batch calls: layout words and DICTID | deflate image | inflate image (zmi_sd_*)
 };
 
@@ -170,6 +171,8 @@ extern "C" int zmi_ctx_destroy(zmi_ctx* c) {
     if (c->si_seg.p) (void)hipFree(c->si_seg.p);
     if (c->si_scan.p) (void)hipFree(c->si_scan.p);
     if (c->dict.p) (void)hipFree(c->dict.p);
+    if (c->mm_scan.p) (void)hipFree(c->mm_scan.p);
+    if (c->mm_meta.p) (void)hipFree(c->mm_meta.p);
     for (int k = 0; k < 2; ++k) if (c->st_pin[k].p) (void)hipHostFree(c->st_pin[k].p);
     if (c->st_pin_ev_live) { (void)hipEventDestroy(c->st_pin_ev[0]); (void)hipEventDestroy(c->st_pin_ev[1]); }
     if (c->hb_live) {
@@ -873,13 +876,28 @@ extern "C" int zmi_inflate_batch_dev_ex(zmi_ctx* c, const void* d_in, const uint
                                       d_status, d_in_used, d_detail, stream_);
 }
 
+// The per-stream tables of one zmi_inflate_impl call in c->inf_tmp (32 bytes per stream): they stay valid on the stream until the next
+// inflate call on the context.  check = the trailer's value, adler / crc = those of the produced bytes (zmi_inflate_members_dev reads
+// them to tell a wrong CRC-32 from a wrong ISIZE).
+struct zmi_inf_tables { uint64_t* bm_off; uint32_t *used, *check, *adler, *crc, *order; };
+static zmi_inf_tables zmi_inf_tables_of(zmi_ctx* c, uint32_t n) {
+    zmi_inf_tables t;
+    t.bm_off = (uint64_t*)c->inf_tmp.p;
+    t.used = (uint32_t*)(t.bm_off + n);
+    t.check = t.used + n;
+    t.adler = t.check + n;
+    t.crc = t.adler + n;
+    t.order = t.crc + n;
+    return t;
+}
 // d_out_hist (may be null): per stream, the number of bytes directly in front of its output region that hold a
 // preset dictionary (inflateSetDictionary, zlib-rs/src/inflate.rs:2492-2536; at most 32768 are ever referenced)
 static int zmi_inflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
                             uint32_t n, int wrap, void* d_out, const uint64_t* d_out_off,
                             const uint32_t* d_out_cap, const uint32_t* d_out_hist, uint32_t* d_out_len,
                             int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, const uint32_t* d_in_bit,
-                            uint32_t* d_resume, void* stream_, bool decode_only = false, const zmi_sd_inflate* sd = nullptr) {
+                            uint32_t* d_resume, void* stream_, bool decode_only = false, const zmi_sd_inflate* sd = nullptr,
+                            bool no_jump = false) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_AUTO) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip/auto");
     if (n == 0) return ZMI_E_OK;
@@ -887,12 +905,13 @@ static int zmi_inflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     ZMI_ON_DEVICE(c);
     int rc = zmi_reserve(c->inf_tmp, (size_t)n * 32u);
     if (rc) return rc;
-    uint64_t* d_bm_off = (uint64_t*)c->inf_tmp.p;
-    uint32_t* d_used = (uint32_t*)(d_bm_off + n);
-    uint32_t* d_check = d_used + n;
-    uint32_t* d_adler = d_check + n;
-    uint32_t* d_crc = d_adler + n;
-    uint32_t* d_order = d_crc + n;   // workgroup -> stream: largest compressed size first (zmi_inflate_order_kernel)
+    const zmi_inf_tables tab = zmi_inf_tables_of(c, n);
+    uint64_t* d_bm_off = tab.bm_off;
+    uint32_t* d_used = tab.used;
+    uint32_t* d_check = tab.check;
+    uint32_t* d_adler = tab.adler;
+    uint32_t* d_crc = tab.crc;
+    uint32_t* d_order = tab.order;   // workgroup -> stream: largest compressed size first (zmi_inflate_order_kernel)
     if (d_in_used) d_used = d_in_used;
     if (sd) {   // the decode pass reads no history: all it needs is every stream's `hist` for its distance check and the FDICT branch
         uint32_t* d_hist = d_order + n;
@@ -931,6 +950,7 @@ static int zmi_inflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
                 (c->inf_limit_exact || out_limit <= (uint64_t)n * (64ull << 20) + (1ull << 20));
     if (!decode_only) {
     if (const char* jv = zmi_tune("ZMI_INF_JUMP")) jump = atoi(jv) != 0 && out_limit <= (1ull << 30);
+    if (no_jump) jump = false;   // (the caller's stream is empty in all but a few calls: the jump resolve would sweep the limit for nothing)
     if (sd) jump = false;   // the shared dictionary is read by the one-wave-per-stream pass only (its case is many small streams)
     if (jump && zmi_reserve(c->inf_ptr, (size_t)bm_words * 256u + 512u) != 0) jump = false;   // (no room: the serial pass needs none)
     {
@@ -2300,6 +2320,134 @@ extern "C" int zmi_stream_find_blocks_dev(zmi_ctx* c, const void* d_in, uint64_t
                                      gap_bits, base == 0 ? 1u : 0u, d_cuts, cap, d_n_cuts, stream);
         base += own;
     } while (base < in_len);
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+// ---- multi-member gzip files: one scan for the member starts, one call that decodes every member in place ----------------------------
+// pack.hip (the scan) and inflate.hip ("multi-member gzip files") hold the kernels and their reasons; DESIGN.md section 16.
+extern "C" int zmi_gzip_find_members_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, uint64_t* d_starts, uint32_t cap, uint32_t* d_n_starts,
+                                         void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if ((in_len && !d_in) || (cap && !d_starts) || !d_n_starts) return zmi_fail(ZMI_E_ARG, "null argument");
+    if (in_len >= (1ull << 45)) return zmi_fail(ZMI_E_ARG, "in_len must be below 2^45");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    if (in_len == 0) { ZMI_HIP(hipMemsetAsync(d_n_starts, 0, 4, stream)); return ZMI_E_OK; }
+    const size_t nseg = zmi_mm_scan_segments(in_len, (uint32_t)((uintptr_t)d_in & 15u));
+    int rc = zmi_reserve(c->mm_scan, 8u * (nseg + 1u) + 4u * nseg);
+    if (rc) return rc;
+    uint64_t* d_off = (uint64_t*)c->mm_scan.p;
+    {
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_mm_find((const uint8_t*)d_in, in_len, (uint32_t*)(d_off + nseg + 1u), d_off, d_starts, cap, d_n_starts, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+extern "C" int zmi_inflate_members_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, const uint64_t* d_starts, uint32_t n_starts, void* d_out,
+                                       uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used, uint32_t* d_members, uint64_t* d_member_off,
+                                       int32_t* d_status, int32_t* d_detail, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (!d_out_len || !d_in_used || !d_members || !d_status || !d_detail || (in_len && !d_in) || (out_cap && !d_out))
+        return zmi_fail(ZMI_E_ARG, "null argument");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    if (in_len == 0) {   // no input: no members
+        ZMI_HIP(hipMemsetAsync(d_out_len, 0, 8, stream));
+        ZMI_HIP(hipMemsetAsync(d_in_used, 0, 8, stream));
+        ZMI_HIP(hipMemsetAsync(d_members, 0, 4, stream));
+        ZMI_HIP(hipMemsetAsync(d_status, 0, 4, stream));
+        ZMI_HIP(hipMemsetAsync(d_detail, 0, 4, stream));
+        if (d_member_off) ZMI_HIP(hipMemsetAsync(d_member_off, 0, 8, stream));
+        return ZMI_E_OK;
+    }
+    if (n_starts == 0 || !d_starts) return zmi_fail(ZMI_E_ARG, "zmi_inflate_members_dev: at least one start (offset 0)");
+    // Launch groups: the decode keeps one bit of scratch per byte of output capacity, and all regions of a call lie inside out_cap.
+    // An out_cap above the scratch limit is cut at multiples of half the limit: group g holds the members whose planned offset lies
+    // in [g * half, (g + 1) * half) -- the members come from device words, so every group is a launch over all proposals in which
+    // the others are empty streams.  Offsets and bytes do not depend on the cut.  The limit is the context's scratch limit alone
+    // (as zmi_inflate_stream_dev): the inflate-out limit is whatever the last batch call was sized for and says nothing here.
+    uint64_t limit = c->scratch_limit;
+    if (const char* lv = zmi_tune("ZMI_MM_LIMIT")) if (atoll(lv) >= (128ll << 10)) limit = (uint64_t)atoll(lv);   // (tests: groups on small files)
+    uint64_t half = 0, groups = 1, room_max = ~0ull;
+    if (out_cap > limit) {
+        half = limit / 2u;
+        groups = out_cap / half + 1u;
+        if (groups > 65536u) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for this out_cap (more than 65536 launch groups)");
+        room_max = limit;   // (the last resort decodes one member alone: the whole bitmap is its)
+    }
+    uint32_t repairs = ZMI_MM_REPAIR_PASSES;
+    if (const char* rv = zmi_tune("ZMI_MM_REPAIR")) repairs = (uint32_t)atoi(rv);   // (the probe: what do the idle passes cost?)
+    const size_t n = n_starts;
+    // words u32[16] | last resort: in_off u64, out_off u64, in, cap, olen, st, used, det | off u64[n + 1] | rank u64[n + 1] |
+    // group: in_off u64[n], out_off u64[n] | tables u32[8n] | group: in, cap, olen, st, used, det u32[n] each
+    const size_t m_w = 0, m_lr = 64, m_off = 128, m_rank = m_off + 8 * (n + 1), m_gio = m_rank + 8 * (n + 1), m_goo = m_gio + 8 * n,
+                 m_tab = m_goo + 8 * n, m_g = m_tab + 32 * n, bytes = m_g + 24 * n;
+    int rc = zmi_reserve(c->mm_meta, bytes);
+    if (rc) return rc;
+    uint8_t* M = (uint8_t*)c->mm_meta.p;
+    uint32_t* d_w = (uint32_t*)(M + m_w);
+    uint64_t* l_ioff = (uint64_t*)(M + m_lr);
+    uint64_t* l_ooff = l_ioff + 1;
+    uint32_t* l_in = (uint32_t*)(l_ooff + 1);
+    uint32_t *l_cap = l_in + 1, *l_olen = l_in + 2, *l_used = l_in + 4;
+    int32_t *l_st = (int32_t*)(l_in + 3), *l_det = (int32_t*)(l_in + 5);
+    uint64_t* d_off = (uint64_t*)(M + m_off);
+    uint64_t* d_rank = (uint64_t*)(M + m_rank);
+    uint64_t* g_ioff = (uint64_t*)(M + m_gio);
+    uint64_t* g_ooff = (uint64_t*)(M + m_goo);
+    uint32_t* d_tab = (uint32_t*)(M + m_tab);
+    uint32_t* g_in = (uint32_t*)(M + m_g);
+    uint32_t *g_cap = g_in + n, *g_olen = g_in + 2 * n, *g_used = g_in + 4 * n;
+    int32_t *g_st = (int32_t*)(g_in + 3 * n), *g_det = (int32_t*)(g_in + 5 * n);
+    // the decode's bitmap covers one group's regions
+    const uint64_t saved_limit = c->inflate_out_limit;
+    c->inflate_out_limit = (out_cap > limit ? limit : out_cap) + (1ull << 16);
+    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; } } restore_limit{c, saved_limit};
+    ZMI_HIP(hipMemsetAsync(d_w, 0, 64, stream));
+    {
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_mm_init(d_starts, n_starts, in_len, d_tab, d_off, d_w, stream);
+    }
+    for (uint32_t pass = 0; pass <= repairs; ++pass) {
+        {
+            zmi_scope_timer tm(c, ZMI_K_PARSE, stream);   // (class 5: the plan; an inflate call runs no cost parse)
+            zmi_launch_mm_plan(d_starts, n_starts, d_tab, d_off, d_w, (const uint8_t*)d_in, in_len, pass, stream);
+        }
+        {
+            zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+            zmi_launch_scan_sizes(d_tab + 2 * n, n_starts, d_off, stream);   // (the planned sizes)
+        }
+        for (uint64_t g = 0; g < groups; ++g) {
+            {
+                zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
+                zmi_launch_mm_setup(d_starts, n_starts, d_tab, d_off, d_w, out_cap, half, (uint32_t)g, g_ioff, g_in, g_ooff, g_cap, stream);
+            }
+            rc = zmi_inflate_impl(c, d_in, g_ioff, g_in, n_starts, ZMI_WRAP_GZIP, d_out, g_ooff, g_cap, nullptr, g_olen, g_st, g_used, g_det, nullptr,
+                                  nullptr, stream_);
+            if (rc) return rc;
+            zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+            zmi_launch_mm_collect(d_starts, n_starts, d_tab, d_off, d_w, out_cap, half, (uint32_t)g, g_olen, g_st, g_used, g_det, stream);
+        }
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_mm_verify(d_starts, n_starts, d_tab, d_off, d_w, out_cap, pass, pass < repairs ? 1 : 0, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_mm_lr_setup(d_starts, n_starts, d_tab, d_off, d_w, in_len, out_cap, room_max, l_ioff, l_in, l_ooff, l_cap, stream);
+    }
+    rc = zmi_inflate_impl(c, d_in, l_ioff, l_in, 1u, ZMI_WRAP_GZIP, d_out, l_ooff, l_cap, nullptr, l_olen, l_st, l_used, l_det, nullptr, nullptr,
+                          stream_, false, nullptr, true);
+    if (rc) return rc;
+    {
+        const zmi_inf_tables lr = zmi_inf_tables_of(c, 1u);   // (of the last-resort launch)
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_scan_sizes(d_tab, n_starts, d_rank, stream);   // (the live flags)
+        zmi_launch_mm_final(d_starts, n_starts, d_tab, d_off, d_w, (const uint8_t*)d_in, in_len, out_cap, d_rank, l_olen, l_st, l_used, l_det, lr.check,
+                            lr.crc, d_out_len, d_in_used, d_members, d_member_off, d_status, d_detail, stream);
+    }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;
 }

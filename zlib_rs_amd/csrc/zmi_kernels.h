@@ -164,4 +164,27 @@ uint32_t zmi_block_scan_look(void);
 int zmi_launch_block_scan_window(const uint8_t* d_win, uint32_t n_vis, uint64_t base_bit, uint32_t own_bits, const uint32_t* d_hdr,
                                  uint32_t* d_slots, uint32_t* d_cnt, uint32_t* d_vcnt, uint64_t* d_voff, uint32_t* d_vlist, uint32_t vcap,
                                  uint64_t gap_bits, uint32_t first, uint64_t* d_cuts, uint32_t cap, uint32_t* d_n_cuts, hipStream_t stream);
+// multi-member gzip files: proposals of member starts (pack.hip: count, scan, gather) and the plan / verify / repair steps of
+// zmi_inflate_members_dev (inflate.hip).  d_tab: eight u32[n] tables, d_off: u64[n + 1], d_w: sixteen words
+uint32_t zmi_mm_scan_segments(uint64_t in_len, uint32_t head);
+int zmi_launch_mm_find(const uint8_t* d_in, uint64_t in_len, uint32_t* d_cnt, uint64_t* d_off, uint64_t* d_starts, uint32_t cap,
+                       uint32_t* d_n_starts, hipStream_t stream);
+int zmi_launch_mm_init(const uint64_t* d_starts, uint32_t n, uint64_t in_len, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w, hipStream_t stream);
+int zmi_launch_mm_plan(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w, const uint8_t* d_in,
+                       uint64_t in_len, uint32_t pass, hipStream_t stream);
+int zmi_launch_mm_setup(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w, uint64_t out_cap, uint64_t half,
+                        uint32_t grp, uint64_t* g_ioff, uint32_t* g_in, uint64_t* g_ooff, uint32_t* g_cap, hipStream_t stream);
+int zmi_launch_mm_collect(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w, uint64_t out_cap, uint64_t half,
+                          uint32_t grp, const uint32_t* g_olen, const int32_t* g_st, const uint32_t* g_used, const int32_t* g_det,
+                          hipStream_t stream);
+int zmi_launch_mm_verify(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w, uint64_t out_cap, uint32_t pass,
+                         int repair, hipStream_t stream);
+int zmi_launch_mm_lr_setup(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w, uint64_t in_len,
+                           uint64_t out_cap, uint64_t room_max, uint64_t* l_ioff, uint32_t* l_in, uint64_t* l_ooff, uint32_t* l_cap,
+                           hipStream_t stream);
+int zmi_launch_mm_final(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, uint64_t* d_off, uint32_t* d_w, const uint8_t* d_in,
+                        uint64_t in_len, uint64_t out_cap, const uint64_t* d_rank, const uint32_t* lr_olen, const int32_t* lr_st,
+                        const uint32_t* lr_used, const int32_t* lr_det, const uint32_t* chk_trailer, const uint32_t* chk_crc,
+                        uint64_t* d_out_len, uint64_t* d_in_used, uint32_t* d_members, uint64_t* d_member_off, int32_t* d_status,
+                        int32_t* d_detail, hipStream_t stream);
 }

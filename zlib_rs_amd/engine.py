@@ -16,6 +16,7 @@ WRAP_RAW, WRAP_ZLIB, WRAP_GZIP, WRAP_AUTO = 0, 1, 2, 3
 GEN_SEED = 0x5A4C4942
 # zmi_inflate_stream_dev detail kinds (include/zmi355.h ZMI_SI_*)
 SI_CUT, SI_PIECE, SI_OUT = 3, 4, 9
+MM_HEADER, MM_TRUNC, MM_DATA, MM_CHECK, MM_LENGTH, MM_OUT, MM_BIG, MM_AGAIN = 1, 2, 3, 4, 5, 6, 7, 8   # ZMI_MM_* (include/zmi355.h)
 
 
 def _stream_ptr():
@@ -212,6 +213,95 @@ class Engine:
         _lib.check(self.L.zmi_stream_find_blocks_dev(self._ctx, data.data_ptr() if n else None, n, int(wrap), int(min_gap), cuts.data_ptr(),
                                                      int(cap), cnt.data_ptr(), _stream_ptr()), "zmi_stream_find_blocks_dev")
         return cuts[:int(cnt.item())]
+
+    def find_members(self, data, cap=None):
+        """Proposed member starts of a multi-member gzip file (pack_slab's output with the gzip wrapper, BGZF, concatenated .gz files):
+        0, then every offset that holds 1f 8b 08 and a FLG byte without reserved bits with at least 18 bytes behind it -- an int64
+        device tensor, ascending.  Proposals may be false; inflate_members verifies them.  One synchronisation, for the count."""
+        n = int(data.numel())
+        grow = cap is None
+        if grow:
+            cap = max(1, n // 18 + 1)   # (members: an empty one is 20 bytes; proposals can be denser, see below)
+        while True:
+            starts = torch.zeros(cap, dtype=torch.int64, device=self.device)
+            cnt = torch.zeros(1, dtype=torch.int32, device=self.device)
+            _lib.check(self.L.zmi_gzip_find_members_dev(self._ctx, data.data_ptr() if n else None, n, starts.data_ptr(), int(cap),
+                                                        cnt.data_ptr(), _stream_ptr()), "zmi_gzip_find_members_dev")
+            found = int(cnt.item())
+            if found < cap or not grow or cap >= n // 3 + 1:
+                return starts[:found]
+            cap = n // 3 + 1            # a full list may be a cut one: stored 1f 8b 08 1f 8b 08 ... proposes every third byte
+
+    def inflate_members_raw(self, data, starts, out, member_off=None):
+        """One zmi_inflate_members_dev call -> (status, case, index, members, in_used, out_len), read back from the device words."""
+        n = int(data.numel())
+        meta = torch.zeros(4, dtype=torch.int64, device=self.device)   # out_len | in_used | members, status | detail
+        mp = meta.data_ptr()
+        _lib.check(self.L.zmi_inflate_members_dev(self._ctx, data.data_ptr() if n else None, n, starts.data_ptr() if starts.numel() else None,
+                                                  int(starts.numel()), out.data_ptr() if out.numel() else None, int(out.numel()), mp, mp + 8,
+                                                  mp + 16, member_off.data_ptr() if member_off is not None else None, mp + 20, mp + 24,
+                                                  _stream_ptr()), "zmi_inflate_members_dev")
+        olen, used, ms, det = meta.tolist()
+        st = (ms >> 32) & 0xFFFFFFFF
+        st = st - (1 << 32) if st >= 1 << 31 else st
+        det &= 0xFFFFFFFF
+        return st, det & 0xFF, det >> 8, ms & 0xFFFFFFFF, used, olen
+
+    def inflate_members(self, data, starts=None, out=None, out_cap=None, index=False):
+        """A multi-member gzip file -> uint8 view of the output (index=True: also the int64 output offset of every member, then the
+        total).  starts: proposed member starts (find_members'; None runs it).  All members decode in one call when no two false
+        proposals share a member or lie in adjacent ones; the call answers ZMI_MM_AGAIN otherwise and the loop here continues behind
+        the last verified member.  Without `out` the buffer is out_cap bytes (default 4x the input + 1 MiB) and grows to the size the
+        device plans when that is too small.  Any other status raises with the case and the proposal's index.  A list that ends
+        early (a caller's list without the last starts, find_members with a cap) does not end the file: where the verified members
+        stop on another gzip header the rest is scanned and decoded too.  self.last_members_in_used is the input offset behind the
+        last member; bytes behind it (in_used < data.numel()) are not a member.  Trailing bytes that begin with 1f 8b 08 are taken
+        for a member and raise if they are none, as Python's gzip does; any other trailing bytes return quietly."""
+        n = int(data.numel())
+        if starts is None:
+            starts = self.find_members(data)
+        starts = starts.to(torch.int64)
+        own = out is None
+        if own:
+            out = torch.empty(int(out_cap) if out_cap is not None else 4 * n + (1 << 20), dtype=torch.uint8, device=self.device)
+        pos = opos = 0
+        offs = []
+        sub = starts
+        for _ in range(2 * int(starts.numel()) + 64):
+            moff = torch.zeros(int(sub.numel()) + 1, dtype=torch.int64, device=self.device) if index else None
+            st, kind, at, members, used, olen = self.inflate_members_raw(data[pos:], sub, out[opos:], moff)
+            if kind == MM_OUT and own and opos + olen > out.numel():
+                grown = torch.empty(opos + olen, dtype=torch.uint8, device=self.device)
+                grown[:opos] = out[:opos]
+                out = grown
+                continue
+            if st != 0 and kind != MM_AGAIN:
+                raise RuntimeError("zmi_inflate_members_dev: status %d, case %d at proposal %d (input offset %d; %d members, %d bytes verified)"
+                                   % (st, kind, at, pos + (int(sub[at]) if at < sub.numel() else 0), members, opos + olen))
+            if st == 0 and pos + used + 18 <= n and members and bytes(data[pos + used:pos + used + 3].tolist()) == b"\x1f\x8b\x08":
+                if index:
+                    offs.append(moff[:members] + opos)
+                pos += used
+                opos += olen
+                rest = self.find_members(data[pos:])
+                starts = rest + pos
+                sub = rest
+                continue
+            if index:
+                offs.append(moff[:members] + opos)
+            if st == 0:
+                self.last_members_in_used = pos + used
+                total = opos + olen
+                if index:
+                    return out[:total], torch.cat(offs + [torch.tensor([total], dtype=torch.int64, device=self.device)])
+                return out[:total]
+            if members == 0:
+                raise RuntimeError("zmi_inflate_members_dev: ZMI_MM_AGAIN without progress at input offset %d" % pos)
+            pos += used
+            opos += olen
+            rest = starts[starts > pos] - pos
+            sub = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), rest])
+        raise RuntimeError("zmi_inflate_members_dev: no result")
 
     def inflate_plain_stream(self, data, wrap=WRAP_AUTO, bit_index=None, min_gap=1 << 16, piece_out_max=None, out=None, out_cap=None):
         """One raw / zlib / gzip member, with or without flush points -> (uint8 view of the output, in_used).  bit_index: the piece

@@ -175,6 +175,43 @@ int zmi_inflate_batch_shared_dict_dev(zmi_ctx* ctx, const void* d_in, const uint
                                       uint32_t n_streams, int wrap, const void* d_dict, uint32_t dict_len, void* d_out,
                                       const uint64_t* d_out_off, const uint32_t* d_out_cap, uint32_t* d_out_len,
                                       int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, void* stream);
+/* ---- batch inflate without an output size table ----
+ * A raw or zlib stream carries no size and a gzip ISIZE is untrusted, so a caller who kept only the compressed bytes has no
+ * d_out_off / d_out_cap to give.  Both calls are asynchronous on `stream`, no value passes through the host.
+ *
+ * zmi_inflate_sizes_dev   the decode kernel walking every stream's true token chain and adding up the output bytes; nothing is
+ *   stored, no bitmap scratch is used, no check value is computed.
+ *   d_size[i]    what inflateInit2_ + inflate(Z_FINISH) would produce with unlimited room; for a stream that ends in an error the
+ *                count up to the error -- the number zmi_inflate_batch_dev_ex reports in d_out_len given ample room.
+ *   d_status, d_in_used, d_detail (the last two may be NULL)   those of zmi_inflate_batch_dev_ex, with ONE difference: check values
+ *                are not compared -- Adler-32, CRC-32 and ISIZE are skipped.  0 = the deflate data is well formed, ends, and a
+ *                full-length trailer follows; a trailer cut short is truncation (Z_BUF_ERROR, detail 1).
+ *   hist         bytes of preset dictionary every stream may reach, 0 .. 32768 (above: ZMI_E_ARG); for the shared-dictionary call
+ *                min(dict_len, 32768).  With hist 0 a zlib stream with FDICT reports Z_NEED_DICT (2); DICTID is not checked here.
+ *   size_limit   0 = 2^32 - 1.  A stream that would produce more stops with Z_BUF_ERROR, detail 2, d_size[i] = size_limit: the
+ *                guard against decompression bombs and the overflow rule in one -- a size never wraps.
+ *
+ * zmi_inflate_batch_packed_dev   the size pass, a plan kernel, then zmi_inflate_batch_dev_ex (d_dict non-NULL and dict_len > 0:
+ *   zmi_inflate_batch_shared_dict_dev, raw or zlib only, otherwise ZMI_E_ARG) with the planned tables: the batch decoded densely
+ *   into one buffer.
+ *   d_out_off[i] (n_streams + 1 words)  where stream i's output stands: the sizes in front of it, each rounded up to out_align (a
+ *                power of two, 1 .. 4096, otherwise ZMI_E_ARG).  d_out_off[n_streams] = the room the whole batch needs -- exact
+ *                whether or not it fitted, it comes from the size pass.  n_streams 0 writes d_out_off[0] = 0.
+ *   out_cap      bytes at d_out.  When d_out_off[n_streams] > out_cap the streams whose bytes end at or before out_cap are decoded
+ *                and are right; every other stream reports Z_BUF_ERROR, detail 2, d_out_len 0 (d_in_used 0); nothing at or behind
+ *                d_out + out_cap and nothing in the alignment gaps is written.  The caller reads one word and calls again.
+ *   size_limit   as above; a stream that hit it gets a region of size_limit bytes (rounded up) and reports Z_BUF_ERROR, detail 2.
+ *   For every stream that fits d_out_len, d_status, d_in_used, d_detail and the bytes are exactly those of
+ *   zmi_inflate_batch_dev_ex (or the shared-dictionary call) given d_out_off and the sizes as capacities.
+ *   Scratch: the bitmap is sized from out_cap (1 bit per byte) for this call; there are no launch groups yet, so a buffer whose
+ *   bitmap cannot be reserved returns ZMI_E_NOMEM -- decode such a batch in parts. */
+int zmi_inflate_sizes_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                          uint32_t n_streams, int wrap, uint32_t hist, uint32_t size_limit, uint32_t* d_size,
+                          int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, void* stream);
+int zmi_inflate_batch_packed_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                 uint32_t n_streams, int wrap, const void* d_dict, uint32_t dict_len, uint32_t size_limit,
+                                 uint32_t out_align, void* d_out, uint64_t out_cap, uint64_t* d_out_off /* n_streams + 1 */,
+                                 uint32_t* d_out_len, int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, void* stream);
 /* Resumable decode of raw deflate streams -- the device half of a streaming inflate() that is fed partial input
  * (the reference keeps Mode / BitReader / Window for this, zlib-rs/src/inflate.rs:288-320; here the state is a
  * block-boundary checkpoint).  Stream i starts at bit d_in_bit[i] (0..7, array may be NULL) of its first byte, with

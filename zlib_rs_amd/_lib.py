@@ -32,6 +32,9 @@ def lib():
     L.zmi_deflate_dict_bound.argtypes = [u64, i32]
     L.zmi_deflate_batch_shared_dict_dev.argtypes = [vp, vp, vp, vp, u32, u32, i32, i32, i32, vp, u32, vp, u64, vp, vp, vp]
     L.zmi_inflate_batch_shared_dict_dev.argtypes = [vp, vp, vp, vp, u32, i32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
+    # batch inflate without an output size table: the size pass, and the dense decode built on it (csrc/inflate.hip, zmi_api.hip)
+    L.zmi_inflate_sizes_dev.argtypes = [vp, vp, vp, vp, u32, i32, u32, u32, vp, vp, vp, vp, vp]
+    L.zmi_inflate_batch_packed_dev.argtypes = [vp, vp, vp, vp, u32, i32, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp, vp]
     L.zmi_checksum_batch_dev.argtypes = [vp, vp, vp, vp, u32, i32, vp, vp, vp]
     L.zmi_gen_shards_dev.argtypes = [vp, vp, u64, u32, u32, u32, vp]
     L.zmi_gen_shards_strided_dev.argtypes = [vp, vp, u64, u32, u32, u32, u32, vp]

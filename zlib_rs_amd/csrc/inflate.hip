@@ -767,6 +767,10 @@ static __device__ __noinline__ void inf_stage_tail(const uint8_t* line, uint32_t
 
 // One fast pass from bit P of the stream.  Returns the number of lanes committed (0: nothing done); *bits_used / *out_made
 // / *hit_eob describe what was committed.  All lanes call.
+// SIZE (the size pass, zmi_inflate_sizes_dev): the pass ends behind the scan -- the committed lanes' byte counts are the result, nothing
+// is stored (dst and bm32 are null); cap may be 2^32 - 1 there, so the two bounds are tested in forms that cannot wrap (opos <= cap
+// always; a match reaches at most 32 768 bytes back, so with 64 KiB of output in front of the pass nothing can be too far)
+template <bool SIZE>
 static __device__ __forceinline__ uint32_t inf_fast_pass(InfShared* S, const uint8_t* src, uint64_t P, uint8_t* dst,
                                                       uint32_t* bm32, uint32_t opos, uint32_t cap, uint32_t hist, uint32_t sub,
                                                       uint32_t* bits_used, uint32_t* out_made, uint32_t* hit_eob, bool fixed_code, uint32_t n_in) {
@@ -827,13 +831,14 @@ static __device__ __forceinline__ uint32_t inf_fast_pass(InfShared* S, const uin
     const uint32_t nout = in ? R.nout : 0u;
     const uint32_t incl = zmi_wave_incl_scan(nout);
     const uint32_t base = opos + incl - nout;
-    const bool bad = in && ((R.flags & 1u) != 0u || base + nout > cap || R.need > base + hist);
+    const bool bad = SIZE ? in && ((R.flags & 1u) != 0u || incl > cap - opos || (opos < 65536u && R.need > base + hist))
+                          : in && ((R.flags & 1u) != 0u || base + nout > cap || R.need > base + hist);
     const uint64_t badm = __ballot(bad);
     uint32_t commit = good;
     if (badm) { const uint32_t fb1 = (uint32_t)__ffsll((unsigned long long)badm) - 1u; commit = fb1 < commit ? fb1 : commit; }
     if (commit == 0u) return 0u;
     // 3. write
-    (void)inf_lane_decode<true>(S, S->fb, start, boundary, lane < commit, dst, bm32, base, R.nout);
+    if (!SIZE) (void)inf_lane_decode<true>(S, S->fb, start, boundary, lane < commit, dst, bm32, base, R.nout);
     const uint32_t last = commit - 1u;
     *bits_used = zmi_readlane(R.exit, last) - p_rel;
     *out_made = zmi_readlane(incl, last);
@@ -875,6 +880,8 @@ struct InfMulti {
 __shared__ InfMulti g_inf_mw;
 
 // one pass, executed by ALL waves of the workgroup between the barrier that posts it and the one that ends it
+// (SIZE: as in inf_fast_pass -- no write walk, bounds that cannot wrap)
+template <bool SIZE>
 static __device__ __noinline__ void inf_pass_mw(const uint8_t* src, uint8_t* dst, uint32_t* bm32) {
     InfShared* S = &g_inf_lds;
     InfMulti* M = &g_inf_mw;
@@ -1001,7 +1008,8 @@ static __device__ __noinline__ void inf_pass_mw(const uint8_t* src, uint8_t* dst
 #pragma unroll
     for (uint32_t w = 0; w < INF_MW; ++w) wbase += (w < wave && w < nact) ? zmi_uniform(M->nsum[w]) : 0u;
     const uint32_t base = wbase + incl - nout;
-    const bool bad = lane < commit && ((R.flags & 1u) != 0u || base + nout > cap || R.need > base + hist);
+    const bool bad = SIZE ? lane < commit && ((R.flags & 1u) != 0u || wbase - opos + incl > cap - opos || (wbase < 65536u && R.need > base + hist))
+                          : lane < commit && ((R.flags & 1u) != 0u || base + nout > cap || R.need > base + hist);
     const uint64_t badm = __ballot(bad);
     if (lane == 0u) M->cut[wave] = badm ? (uint32_t)__ffsll((unsigned long long)badm) - 1u : 64u;
     __syncthreads();
@@ -1021,7 +1029,7 @@ static __device__ __noinline__ void inf_pass_mw(const uint8_t* src, uint8_t* dst
             fc = w == wave ? c : fc;
         }
     }
-    if (fc != 0u) (void)inf_lane_decode<true>(S, fb, start, boundary, lane < fc, dst, bm32, base, R.nout);
+    if (!SIZE && fc != 0u) (void)inf_lane_decode<true>(S, fb, start, boundary, lane < fc, dst, bm32, base, R.nout);
     if (total_lanes != 0u && wave == last_wave) {
         const uint32_t k = fc - 1u;
         const uint32_t bits = zmi_readlane(R.exit, k) - p_rel + org, outm = wbase - opos + zmi_readlane(incl, k),
@@ -1038,7 +1046,13 @@ static __device__ __noinline__ void inf_pass_mw(const uint8_t* src, uint8_t* dst
 // resume[4s..4s+3] receives {byte, bit, output position, complete} of the start of the block the decode stopped
 // in -- or of the end of the final block.  Decoding the same input again from there, with the output in front of
 // that point as history, continues the stream.  A separate instantiation: the batch kernel's registers are full.
-template <bool RESUME, uint32_t NW>   // NW: waves per stream, 1 (the batch kernels) or INF_MW (launches of a few streams)
+// SIZE (zmi_inflate_sizes_dev; not with RESUME): the same walk through wrapper, block headers, tables and the true token chain, adding up
+// the output bytes and storing none of them.  out, out_off, out_cap, check, bitmap, bm_off and out_hist are not read (null): every stream
+// may produce size_limit bytes with size_hist bytes of history in front of it.  A fast pass ends behind its scan, a token round counts
+// where the decoder emits, a stored block is one step.  The trailer's values are not compared (the bytes they cover do not exist), so
+// the stream's final words are written here: out_len = the size (size_limit for a stream that would pass it), status and size_detail
+// (may be null, as in_used) in zlib's numbering as zmi_inflate_verify_kernel resolves them.
+template <bool RESUME, uint32_t NW, bool SIZE = false>   // NW: waves per stream, 1 (the batch kernels) or INF_MW (launches of a few streams)
 __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                          const uint32_t* __restrict__ in_len, uint32_t wrap,
                                                          uint8_t* out, const uint64_t* __restrict__ out_off,
@@ -1048,7 +1062,9 @@ __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __r
                                                          uint64_t* __restrict__ bitmap, const uint64_t* __restrict__ bm_off,
                                                          const uint32_t* __restrict__ out_hist,
                                                          const uint32_t* __restrict__ in_bit, uint32_t* __restrict__ resume,
-                                                         const uint32_t* __restrict__ order) {
+                                                         const uint32_t* __restrict__ order, uint32_t size_limit, uint32_t size_hist,
+                                                         int32_t* __restrict__ size_detail) {
+    static_assert(!(RESUME && SIZE), "the size pass starts at a stream's first bit");
     InfShared* S = &g_inf_lds;
     const uint32_t lane = zmi_lane();
     const uint32_t s = order[blockIdx.x];   // longest streams first (zmi_inflate_order_kernel)
@@ -1060,16 +1076,16 @@ __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __r
     B.nbits = 0;
     B.inbuf = S->inbuf;
     B.cbase = -(int32_t)(2u * INF_CHUNK);  // nothing staged yet: the first refill loads a chunk
-    uint8_t* dst = out + out_off[s];
-    const uint32_t cap = out_cap[s];
+    uint8_t* dst = SIZE ? nullptr : out + out_off[s];
+    const uint32_t cap = SIZE ? size_limit : out_cap[s];
     uint32_t opos = 0;
     int32_t st = ZMI_OK;
     // preset dictionary (inflateSetDictionary, zlib-rs/src/inflate.rs:2492-2536): `hist` bytes in front of the output
     // region are history the stream may refer to
-    const uint32_t hist = out_hist ? out_hist[s] : 0u;
-    const uint64_t bmo = bm_off[s];
-    uint32_t* bm32 = (uint32_t*)(bitmap + (bmo == ~0ull ? 0ull : bmo));   // bit p set: a back-reference starts at output byte p
-    if (bmo == ~0ull) {
+    const uint32_t hist = SIZE ? size_hist : (out_hist ? out_hist[s] : 0u);
+    const uint64_t bmo = SIZE ? 0ull : bm_off[s];
+    uint32_t* bm32 = SIZE ? nullptr : (uint32_t*)(bitmap + (bmo == ~0ull ? 0ull : bmo));   // bit p set: a back-reference starts at output byte p
+    if (!SIZE && bmo == ~0ull) {
         if (lane == 0) {
             out_len[s] = 0; in_used[s] = 0; check[s] = 0; status[s] = ZMI_NO_SCRATCH;
             if (RESUME) { resume[4u * s] = 0; resume[4u * s + 1u] = in_bit ? (in_bit[s] & 7u) : 0u; resume[4u * s + 2u] = 0; resume[4u * s + 3u] = 0; }
@@ -1081,7 +1097,7 @@ __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __r
         for (;;) {
             __syncthreads();
             if (zmi_uniform(g_inf_mw.cmd) == 2u) return;
-            inf_pass_mw(B.src, dst, bm32);
+            inf_pass_mw<SIZE>(B.src, dst, bm32);
         }
     }
     uint32_t kind_found = wrap;  // resolved wrapper: 0 raw, 1 zlib, 2 gzip
@@ -1182,7 +1198,7 @@ __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __r
                 const uint32_t have = B.n - B.ipos, room = cap > opos ? cap - opos : 0u;
                 uint32_t copy = l < have ? l : have;
                 copy = copy < room ? copy : room;
-                for (uint32_t i = lane; i < copy; i += 64u) dst[opos + i] = B.src[B.ipos + i];
+                if (!SIZE) for (uint32_t i = lane; i < copy; i += 64u) dst[opos + i] = B.src[B.ipos + i];
                 opos += copy;
                 B.ipos += copy;
                 if (copy < l) { st = (room < l && room <= have) ? ZMI_NEED_OUTPUT : ZMI_BUF_ERROR; break; }
@@ -1391,11 +1407,11 @@ __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __r
                                 M->opos = opos; M->cap = cap; M->hist = hist; M->fixed = fixed_ready;
                             }
                             __syncthreads();
-                            inf_pass_mw(B.src, dst, bm32);
+                            inf_pass_mw<SIZE>(B.src, dst, bm32);
                             lanes = zmi_uniform(g_inf_mw.res_lanes);
                             if (lanes != 0u) { fbits = zmi_uniform(g_inf_mw.res_bits); fout = zmi_uniform(g_inf_mw.res_out); feob = zmi_uniform(g_inf_mw.res_eob); }
                         } else
-                        lanes = zmi_uniform(inf_fast_pass(S, B.src, P, dst, bm32, opos, cap, hist, sub, &fbits, &fout, &feob, fixed_ready != 0u, B.n));
+                        lanes = zmi_uniform(inf_fast_pass<SIZE>(S, B.src, P, dst, bm32, opos, cap, hist, sub, &fbits, &fout, &feob, fixed_ready != 0u, B.n));
                         B.cbase = -(int32_t)(2u * INF_CHUNK);   // the pass staged its input over the token rounds' chunk
                         if (lanes < 8u && sub >= 288u) { fskip_len = fskip_len == 0u ? 4u : (fskip_len < 64u ? fskip_len * 2u : 64u); fskip = fskip_len; }
                         else if (lanes >= 32u) fskip_len = 0u;
@@ -1451,10 +1467,11 @@ __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __r
                 const uint32_t totA = zmi_readlane(inclA, 63u);
                 const uint32_t inclB = zmi_wave_incl_scan(lenB) + totA;
                 const uint32_t exclA = inclA - lenA, exclB = inclB - lenB;
-                const bool farA = onA && TA.kind == 1u && TA.dist > opos + exclA + hist;   // "invalid distance too far back"
-                const bool farB = onB && TB.kind == 1u && TB.dist > opos + exclB + hist;
-                const bool fullA = onA && lenA != 0u && opos + inclA > cap;
-                const bool fullB = onB && lenB != 0u && opos + inclB > cap;
+                // (SIZE: cap may be 2^32 - 1 -- the same tests in forms that cannot wrap, see inf_fast_pass)
+                const bool farA = onA && TA.kind == 1u && (!SIZE || opos < 65536u) && TA.dist > opos + exclA + hist;   // "invalid distance too far back"
+                const bool farB = onB && TB.kind == 1u && (!SIZE || opos < 65536u) && TB.dist > opos + exclB + hist;
+                const bool fullA = onA && lenA != 0u && (SIZE ? inclA > cap - opos : opos + inclA > cap);
+                const bool fullB = onB && lenB != 0u && (SIZE ? inclB > cap - opos : opos + inclB > cap);
                 const uint64_t cutA = __ballot(farA || fullA), cutB = __ballot(farB || fullB);
                 uint32_t tot;
                 if (cutA | cutB) {
@@ -1481,8 +1498,10 @@ __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __r
                 } else {
                     tot = zmi_readlane(inclB, 63u);
                 }
-                inf_emit(dst, bm32, onA, TA, opos + exclA);
-                inf_emit(dst, bm32, onB, TB, opos + exclB);
+                if (!SIZE) {
+                    inf_emit(dst, bm32, onA, TA, opos + exclA);
+                    inf_emit(dst, bm32, onB, TB, opos + exclB);
+                }
                 opos += tot;
                 P += pos;
                 if (rst != ZMI_OK) st = rst;
@@ -1532,7 +1551,20 @@ __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __r
             }
         }
     }
-    if (lane == 0) {
+    if (SIZE) {
+        // the words zmi_inflate_verify_kernel would make of `st`, without the comparisons: a full-length trailer is as good as a right one
+        int32_t det = 0;
+        if (st == ZMI_NEED_OUTPUT) { st = ZMI_BUF_ERROR; det = 2; opos = cap; }   // (a token that would pass the limit is not counted in part)
+        else if (st <= ZMI_DERR(1)) { det = 16 + (-3000 - st); st = ZMI_DATA_ERROR; }
+        else if (st == ZMI_BUF_ERROR || st == ZMI_TRAILER_SHORT) { st = ZMI_BUF_ERROR; det = 1; }
+        else if (st == ZMI_LENGTH_MISMATCH) st = ZMI_OK;
+        if (lane == 0) {
+            out_len[s] = opos;
+            status[s] = st;
+            if (in_used) in_used[s] = B.ipos;
+            if (size_detail) size_detail[s] = det;
+        }
+    } else if (lane == 0) {
         out_len[s] = opos;
         in_used[s] = B.ipos;
         check[s] = RESUME ? S->misc[5] : chk;   // (a resumable decode is a raw stream: no trailer value; the word carries the tables' size)
@@ -2047,10 +2079,81 @@ extern "C" int zmi_launch_inflate(const uint8_t* d_in, const uint64_t* d_in_off,
     const bool mw = n_streams <= mw_max;
 #define INF_GO(R, W, IB, RS) ZMI_LAUNCH((zmi_inflate_kernel<R, W>), dim3(n_streams), dim3(64u * W), 0, stream, d_in, d_in_off, d_in_len, wrap, d_out, \
                                 d_out_off, d_out_cap, d_out_len, d_in_used, d_check, d_status, d_bitmap, (const uint64_t*)d_bm_off, d_out_hist, IB, RS,  \
-                                (const uint32_t*)d_order)
+                                (const uint32_t*)d_order, 0u, 0u, (int32_t*)nullptr)
     if (d_resume) { if (mw) INF_GO(true, INF_MW, d_in_bit, d_resume); else INF_GO(true, 1u, d_in_bit, d_resume); }
     else { if (mw) INF_GO(false, INF_MW, (const uint32_t*)nullptr, (uint32_t*)nullptr); else INF_GO(false, 1u, (const uint32_t*)nullptr, (uint32_t*)nullptr); }
 #undef INF_GO
+    return 0;
+}
+
+// The size pass (zmi_inflate_sizes_dev): the decode kernel's SIZE form under the same selection; d_size receives what the decoder would
+// report in d_out_len given room for size_limit bytes, d_status / d_detail the stream's final words.  Needs d_order only.
+extern "C" int zmi_launch_inflate_sizes(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_streams,
+                                        uint32_t wrap, uint32_t hist, uint32_t size_limit, uint32_t* d_size, int32_t* d_status,
+                                        uint32_t* d_in_used, int32_t* d_detail, uint32_t* d_order, uint32_t mw_max, hipStream_t stream) {
+    if (n_streams == 0) return 0;
+    ZMI_LAUNCH(zmi_inflate_order_kernel, dim3(1), dim3(1024), 0, stream, d_in_len, n_streams, d_order);
+#define INF_SZ(W) ZMI_LAUNCH((zmi_inflate_kernel<false, W, true>), dim3(n_streams), dim3(64u * W), 0, stream, d_in, d_in_off, d_in_len, wrap,        \
+                             (uint8_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)nullptr, d_size, d_in_used, (uint32_t*)nullptr, d_status,  \
+                             (uint64_t*)nullptr, (const uint64_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr,    \
+                             (const uint32_t*)d_order, size_limit, hist, d_detail)
+    if (n_streams <= mw_max) INF_SZ(INF_MW); else INF_SZ(1u);
+#undef INF_SZ
+    return 0;
+}
+
+// ---- the packed call's plan (zmi_inflate_batch_packed_dev): where every stream's output stands in one dense buffer ----
+// One workgroup, the scan of zmi_inflate_plan_kernel in 64 bits: out_off[i] = the sizes in front of stream i, each rounded up to
+// `align` (a power of two); out_off[n] = the room the whole batch needs; cap[i] = size[i] where [out_off[i], out_off[i] + size[i]) ends
+// at or before out_cap, 0 where it does not (such a stream is handed to the decoder with no room and is marked by the kernel below).
+__global__ void __launch_bounds__(1024) zmi_inflate_pack_plan_kernel(const uint32_t* __restrict__ size, uint32_t n, uint64_t align,
+                                                                      uint64_t out_cap, uint64_t* __restrict__ out_off,
+                                                                      uint32_t* __restrict__ cap) {
+    __shared__ uint64_t part[1024];
+    const uint32_t t = threadIdx.x;
+    const uint32_t per = (n + 1023u) / 1024u;
+    const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
+    uint64_t sum = 0;
+    for (uint32_t i = lo; i < hi; ++i) sum += ((uint64_t)size[i] + align - 1ull) & ~(align - 1ull);
+    part[t] = sum;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {
+        uint64_t v = t >= d ? part[t - d] : 0ull;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint64_t o = part[t] - sum;
+    for (uint32_t i = lo; i < hi; ++i) {
+        const uint64_t sz = size[i];
+        out_off[i] = o;
+        cap[i] = o + sz <= out_cap ? (uint32_t)sz : 0u;
+        o += (sz + align - 1ull) & ~(align - 1ull);
+    }
+    if (t == 1023u) out_off[n] = part[t];
+}
+// after the decode: a stream whose region does not end inside out_cap has not been decoded -- Z_BUF_ERROR, detail 2, no output
+__global__ void __launch_bounds__(256) zmi_inflate_pack_mark_kernel(const uint32_t* __restrict__ size, const uint64_t* __restrict__ out_off,
+                                                                     uint32_t n, uint64_t out_cap, uint32_t* __restrict__ out_len,
+                                                                     int32_t* __restrict__ status, uint32_t* __restrict__ in_used,
+                                                                     int32_t* __restrict__ detail) {
+    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n || out_off[s] + (uint64_t)size[s] <= out_cap) return;
+    out_len[s] = 0u;
+    status[s] = ZMI_BUF_ERROR;
+    if (in_used) in_used[s] = 0u;
+    if (detail) detail[s] = 2;
+}
+extern "C" int zmi_launch_inflate_pack_plan(const uint32_t* d_size, uint32_t n_streams, uint32_t align, uint64_t out_cap, uint64_t* d_out_off,
+                                            uint32_t* d_cap, hipStream_t stream) {
+    ZMI_LAUNCH(zmi_inflate_pack_plan_kernel, dim3(1), dim3(1024), 0, stream, d_size, n_streams, (uint64_t)align, out_cap, d_out_off, d_cap);
+    return 0;
+}
+extern "C" int zmi_launch_inflate_pack_mark(const uint32_t* d_size, const uint64_t* d_out_off, uint32_t n_streams, uint64_t out_cap,
+                                            uint32_t* d_out_len, int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, hipStream_t stream) {
+    if (n_streams == 0) return 0;
+    ZMI_LAUNCH(zmi_inflate_pack_mark_kernel, dim3((n_streams + 255u) / 256u), dim3(256), 0, stream, d_size, d_out_off, n_streams, out_cap,
+               d_out_len, d_status, d_in_used, d_detail);
     return 0;
 }
 

@@ -114,6 +114,7 @@ struct zmi_ctx {
     zmi_buf si_meta, si_work, si_seg;   // zmi_inflate_stream_dev: per-piece tables / one launch group's regions; find_cuts' segment table
     zmi_buf si_scan;                    // zmi_stream_find_blocks_dev: one window's survivor slots and validated list
     zmi_buf mm_scan, mm_meta;           // zmi_gzip_find_members_dev: segment counts and offsets; zmi_inflate_members_dev: its tables
+    zmi_buf pk;                         // zmi_inflate_batch_packed_dev: size[n] cap[n] (the size pass's result, the planned capacity table)
     zmi_buf dict;                       // the shared-dictionary batch calls: layout words and DICTID | deflate image | inflate image (zmi_sd_*)
 };
 
@@ -171,6 +172,7 @@ extern "C" int zmi_ctx_destroy(zmi_ctx* c) {
     if (c->si_seg.p) (void)hipFree(c->si_seg.p);
     if (c->si_scan.p) (void)hipFree(c->si_scan.p);
     if (c->dict.p) (void)hipFree(c->dict.p);
+    if (c->pk.p) (void)hipFree(c->pk.p);
     if (c->mm_scan.p) (void)hipFree(c->mm_scan.p);
     if (c->mm_meta.p) (void)hipFree(c->mm_meta.p);
     for (int k = 0; k < 2; ++k) if (c->st_pin[k].p) (void)hipHostFree(c->st_pin[k].p);
@@ -1043,6 +1045,84 @@ extern "C" int zmi_inflate_batch_dev(zmi_ctx* c, const void* d_in, const uint64_
                                      uint32_t* d_out_len, int32_t* d_status, void* stream_) {
     return zmi_inflate_batch_dev_ex(c, d_in, d_in_off, d_in_len, n, wrap, d_out, d_out_off, d_out_cap, d_out_len, d_status, nullptr,
                                     nullptr, stream_);
+}
+
+// ---- batch inflate without an output size table (include/zmi355.h) ----
+// The size pass: the decode kernel's SIZE form (inflate.hip).  Of the context's inf_tmp tables it uses `order` (and `used` when the
+// caller wants no d_in_used); it needs no bitmap.
+static int zmi_inflate_sizes_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n, int wrap,
+                                  uint32_t hist, uint32_t size_limit, uint32_t* d_size, int32_t* d_status, uint32_t* d_in_used,
+                                  int32_t* d_detail, hipStream_t stream) {
+    int rc = zmi_reserve(c->inf_tmp, (size_t)n * 32u);
+    if (rc) return rc;
+    const zmi_inf_tables tab = zmi_inf_tables_of(c, n);
+    uint32_t mw_max = c->inf_mw_max;
+    if (const char* mv = zmi_tune("ZMI_INF_MW_MAX")) mw_max = (uint32_t)atoi(mv);   // (tests: both selections, per call)
+    zmi_scope_timer tm(c, ZMI_K_INFLATE, stream);
+    int lrc = zmi_launch_inflate_sizes((const uint8_t*)d_in, d_in_off, d_in_len, n, (uint32_t)wrap, hist, size_limit ? size_limit : 0xFFFFFFFFu,
+                                       d_size, d_status, d_in_used, d_detail, tab.order, mw_max, stream);
+    if (lrc) return zmi_fail(ZMI_E_HIP, "inflate size pass launch setup", (hipError_t)lrc);
+    return ZMI_E_OK;
+}
+
+extern "C" int zmi_inflate_sizes_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
+                                     int wrap, uint32_t hist, uint32_t size_limit, uint32_t* d_size, int32_t* d_status,
+                                     uint32_t* d_in_used, int32_t* d_detail, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_AUTO) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip/auto");
+    if (hist > 32768u) return zmi_fail(ZMI_E_ARG, "hist must be 0 .. 32768");
+    if (n == 0) return ZMI_E_OK;
+    if (!d_size || !d_status) return zmi_fail(ZMI_E_ARG, "d_size and d_status are required");
+    ZMI_ON_DEVICE(c);
+    int rc = zmi_inflate_sizes_impl(c, d_in, d_in_off, d_in_len, n, wrap, hist, size_limit, d_size, d_status, d_in_used, d_detail,
+                                    (hipStream_t)stream_);
+    if (rc) return rc;
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+extern "C" int zmi_inflate_batch_packed_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
+                                            int wrap, const void* d_dict, uint32_t dict_len, uint32_t size_limit, uint32_t out_align,
+                                            void* d_out, uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status,
+                                            uint32_t* d_in_used, int32_t* d_detail, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_AUTO) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip/auto");
+    if (out_align == 0u || out_align > 4096u || (out_align & (out_align - 1u)) != 0u)
+        return zmi_fail(ZMI_E_ARG, "out_align must be a power of two, 1 .. 4096");
+    const bool dict = d_dict != nullptr && dict_len != 0u;
+    if (dict && wrap != ZMI_WRAP_RAW && wrap != ZMI_WRAP_ZLIB)
+        return zmi_fail(ZMI_E_ARG, "a preset dictionary needs wrap raw or zlib (a gzip member has no dictionary field)");
+    if (!d_out_off) return zmi_fail(ZMI_E_ARG, "d_out_off is required");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    if (n == 0) {
+        ZMI_HIP(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), stream));
+        return ZMI_E_OK;
+    }
+    if (!d_out_len || !d_status) return zmi_fail(ZMI_E_ARG, "d_out_len and d_status are required");
+    int rc = zmi_reserve(c->pk, (size_t)n * 8u);
+    if (rc) return rc;
+    uint32_t* d_size = (uint32_t*)c->pk.p;
+    uint32_t* d_cap = d_size + n;
+    // (the size pass leaves its words in the caller's arrays; the decode below overwrites them)
+    rc = zmi_inflate_sizes_impl(c, d_in, d_in_off, d_in_len, n, wrap, dict ? (dict_len < 32768u ? dict_len : 32768u) : 0u, size_limit, d_size,
+                                d_status, d_in_used, d_detail, stream);
+    if (rc) return rc;
+    zmi_launch_inflate_pack_plan(d_size, n, out_align, out_cap, d_out_off, d_cap, stream);
+    // the bitmap scratch covers what the planned capacities can sum to: out_cap (no stream holds more than 2^32 - 1 bytes)
+    const uint64_t most = (uint64_t)n * 0xFFFFFFFFull;
+    const uint64_t saved_limit = c->inflate_out_limit;
+    c->inflate_out_limit = (out_cap < most ? out_cap : most) + (1ull << 16);
+    c->inf_limit_exact = true;
+    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; c->inf_limit_exact = false; } } restore_limit{c, saved_limit};
+    if (dict) rc = zmi_inflate_batch_shared_dict_dev(c, d_in, d_in_off, d_in_len, n, wrap, d_dict, dict_len, d_out, d_out_off, d_cap, d_out_len,
+                                                     d_status, d_in_used, d_detail, stream_);
+    else rc = zmi_inflate_impl(c, d_in, d_in_off, d_in_len, n, wrap, d_out, d_out_off, d_cap, nullptr, d_out_len, d_status, d_in_used, d_detail,
+                               nullptr, nullptr, stream_);
+    if (rc) return rc;
+    zmi_launch_inflate_pack_mark(d_size, d_out_off, n, out_cap, d_out_len, d_status, d_in_used, d_detail, stream);
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
 }
 
 // ---------------- host-buffer wrappers ----------------

@@ -113,6 +113,14 @@ int zmi_launch_inflate(const uint8_t* d_in, const uint64_t* d_in_off, const uint
                        uint32_t* d_out_len, uint32_t* d_in_used, uint32_t* d_check, int32_t* d_status,
                        uint64_t* d_bitmap, uint64_t bitmap_words, uint64_t* d_bm_off, const uint32_t* d_out_hist,
                        const uint32_t* d_in_bit, uint32_t* d_resume, uint32_t* d_order, uint32_t mw_max, hipStream_t stream);
+// the size pass (the decode kernel counting instead of storing) and the packed call's plan / mark kernels
+int zmi_launch_inflate_sizes(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_streams,
+                             uint32_t wrap, uint32_t hist, uint32_t size_limit, uint32_t* d_size, int32_t* d_status,
+                             uint32_t* d_in_used, int32_t* d_detail, uint32_t* d_order, uint32_t mw_max, hipStream_t stream);
+int zmi_launch_inflate_pack_plan(const uint32_t* d_size, uint32_t n_streams, uint32_t align, uint64_t out_cap, uint64_t* d_out_off,
+                                 uint32_t* d_cap, hipStream_t stream);
+int zmi_launch_inflate_pack_mark(const uint32_t* d_size, const uint64_t* d_out_off, uint32_t n_streams, uint64_t out_cap,
+                                 uint32_t* d_out_len, int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, hipStream_t stream);
 int zmi_launch_resolve_jump(uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_len, uint32_t n_streams,
                             const uint64_t* d_bitmap, const uint64_t* d_bm_off, int32_t* d_ptr, uint64_t n_idx, uint32_t rounds,
                             uint32_t* d_flags, hipStream_t stream);

@@ -419,6 +419,59 @@ class Engine:
                    "zmi_inflate_batch_dev")
         return out_len, status
 
+    # ---- batch inflate without an output size table ----
+    def inflate_sizes(self, data, offsets, lengths, wrap=WRAP_ZLIB, hist=0, size_limit=0, in_used=None, detail=None):
+        """(sizes int32 [n], status int32 [n]) of zmi_inflate_sizes_dev: what every stream would decode to, found by the decode kernel
+        counting instead of storing (no output buffer, no check values).  The words are uint32: a size of 2 GiB or more reads negative
+        in the int32 tensor.  hist: bytes of preset dictionary every stream may reach; size_limit 0: 2^32 - 1.  No synchronisation."""
+        n = int(lengths.numel())
+        sizes = torch.empty(n, dtype=torch.int32, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        _lib.check(self.L.zmi_inflate_sizes_dev(self._ctx, data.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, int(wrap), int(hist),
+                                                int(size_limit), sizes.data_ptr(), status.data_ptr(),
+                                                in_used.data_ptr() if in_used is not None else None,
+                                                detail.data_ptr() if detail is not None else None, _stream_ptr()),
+                   "zmi_inflate_sizes_dev")
+        return sizes, status
+
+    def inflate_batch_packed(self, data, offsets, lengths, wrap=WRAP_ZLIB, zdict=None, size_limit=0, align=1, out=None, in_used=None,
+                             detail=None):
+        """(out, out_offsets int64 [n + 1], out_len int32 [n], status int32 [n]): the batch decoded densely into one buffer, stream i at
+        out_offsets[i] (the sizes in front of it, each rounded up to `align`), out_offsets[n] = the room the whole batch needs.
+        With `out` given this is zmi_inflate_batch_packed_dev as it stands: no synchronisation; where out_offsets[n] > out.numel() the
+        streams that do not fit report Z_BUF_ERROR with length 0 and the caller calls again with that much room.
+        With out=None the size pass and the plan run first, ONE word -- the total -- is read by the host (the one synchronisation), the
+        buffer is allocated exactly, and the ordinary inflate_batch runs with the planned table: no stream is decoded for its size twice
+        (in_used / detail are then filled as inflate_batch fills them: with zdict only)."""
+        n = int(lengths.numel())
+        if align < 1 or align > 4096 or align & (align - 1):
+            raise ValueError("align must be a power of two, 1 .. 4096")
+        if zdict is not None:
+            _check_zdict(zdict, self.device)
+        out_len = torch.empty(n, dtype=torch.int32, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        if out is not None:
+            out_offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+            _lib.check(self.L.zmi_inflate_batch_packed_dev(self._ctx, data.data_ptr(), offsets.data_ptr(), lengths.data_ptr(), n, int(wrap),
+                                                           zdict.data_ptr() if zdict is not None and zdict.numel() else None,
+                                                           int(zdict.numel()) if zdict is not None else 0, int(size_limit), int(align),
+                                                           out.data_ptr(), int(out.numel()), out_offsets.data_ptr(), out_len.data_ptr(),
+                                                           status.data_ptr(), in_used.data_ptr() if in_used is not None else None,
+                                                           detail.data_ptr() if detail is not None else None, _stream_ptr()),
+                       "zmi_inflate_batch_packed_dev")
+            return out, out_offsets, out_len, status
+        hist = min(int(zdict.numel()), 32768) if zdict is not None else 0
+        sizes, _ = self.inflate_sizes(data, offsets, lengths, wrap=wrap, hist=hist, size_limit=size_limit)
+        room = ((sizes.to(torch.int64) & 0xFFFFFFFF) + (align - 1)) & ~(align - 1)
+        out_offsets = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        torch.cumsum(room, 0, out=out_offsets[1:])
+        total = int(out_offsets[n].item()) if n else 0
+        out = torch.empty(total, dtype=torch.uint8, device=self.device)
+        if n:
+            self.inflate_batch(data, offsets, lengths, out, out_offsets, sizes, wrap=wrap, out_len=out_len, status=status,
+                               zdict=zdict if zdict is not None and zdict.numel() else None, in_used=in_used, detail=detail)
+        return out, out_offsets, out_len, status
+
     # ---- checksums ----
     def checksums(self, data, offsets, lengths, adler=True, crc=True, out_adler=None, out_crc=None):
         """(adler int32 [n], crc int32 [n]); the array of a checksum that was not asked for is left as it is (zeros when

@@ -427,6 +427,63 @@ int zmi_inflate_stream_bits_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len,
                                 uint32_t piece_out_max, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used,
                                 int32_t* d_status, int32_t* d_detail, void* stream);
 
+/* ---- random access into ONE stream: an index kept while it is decoded once, byte ranges read from it afterwards -----------------------
+ * A block start in the middle of an ordinary stream (gzip / zlib / zlib-rs at default settings, this library's carry-mode stream, pigz)
+ * needs the 32 KiB of output in front of it.  With the reference one access is inflateInit2_(-15) + inflatePrime (the bits of the first
+ * byte in front of the point) + inflateSetDictionary (the window) + inflate, per access, on one core: libz-rs-sys/src/lib.rs:968
+ * (inflateInit2_), :1029 (inflatePrime), :1121 (inflateSetDictionary), :637 (inflate) -- zlib's examples/zran.c.  Here the index is a
+ * by-product of the verified decode of zmi_inflate_stream_bits_dev, and a batch of ranges is one group of launches.  Both calls are
+ * asynchronous on `stream` and do not synchronise with the host.  (gzip members and ZMI_STREAM_INDEPENDENT pieces forget history:
+ * their indices -- d_member_off, d_piece_off -- are read through zmi_inflate_batch_dev, or through zmi_inflate_ranges_dev with
+ * d_ix_win NULL.)
+ *
+ * zmi_inflate_stream_index_dev  the arguments of zmi_inflate_stream_bits_dev (cuts in BITS), then the index.  The four device words and
+ *                               the bytes at d_out are those of zmi_inflate_stream_bits_dev on the same arguments.  A POINT is (bit
+ *                               position in d_in, output offset, the 32 768 bytes of output in front of it).  Point 0 is (d_cuts[0], 0):
+ *                               the end of the header, no window.  Greedy and exact: point k + 1 is the first verified piece start g
+ *                               whose output offset is >= d_ix_out[k] + max(span, 1); the same entries on every run, whatever the
+ *                               scratch limit (the selection continues across launch groups from device words).
+ *                               d_ix_bit[ix_cap], d_ix_out[ix_cap + 1]: *d_n_points entries, d_ix_out[*d_n_points] = the total output
+ *                               length.  *d_max_gap = the greatest d_ix_out[k + 1] - d_ix_out[k], k < *d_n_points.  If more points
+ *                               qualify than ix_cap the first ix_cap are kept, and *d_max_gap includes the long tail behind them.
+ *                               d_ix_win (NULL: offsets only; 16-byte aligned, ix_cap * 32768 bytes): window k at d_ix_win + k * 32768,
+ *                               right-aligned -- its last byte is output byte d_ix_out[k] - 1, positions in front of the stream's
+ *                               start are zero.
+ *                               The index is valid only for a verified stream: with *d_status != 0 (a cut that failed, a wrong check
+ *                               value, ZMI_SI_OUT: the output did not fit out_cap, ...) *d_n_points = 0.  An index cannot be built
+ *                               without room for the whole output.  ix_cap 0 or a NULL d_ix_bit / d_ix_out / d_n_points / d_max_gap:
+ *                               ZMI_E_ARG.
+ * zmi_inflate_ranges_dev        n_ranges byte ranges of the stream's OUTPUT: range i = [d_lo[i], d_lo[i] + d_len[i]).  The bytes
+ *                               [lo, min(lo + len, total)) are written at d_out + off_i (off_i = d_out_off[i], or i * out_stride with
+ *                               d_out_off NULL; any alignment), d_got[i] = their count; nothing outside [off_i, off_i + got) is written.
+ *                               d_ix_bit / d_ix_out / d_ix_win / n_points / max_gap: an index as built above (max_gap may be any bound
+ *                               >= *d_max_gap; it sizes the scratch).  d_ix_win (16-byte aligned) NULL: the points have no history.
+ *                               d_status[i]  0: the bytes are right; also for len 0 and for lo >= total (got 0), which decode nothing.
+ *                                            Z_DATA_ERROR (-3): corrupt data behind the point, or a distance that reaches in front of
+ *                                            the available history (d_ix_win NULL: any distance in front of the point).
+ *                                            Z_BUF_ERROR (-5): the input ends inside the extent the range needs.
+ *                                            ZMI_E_ARG (-103; the tables live on the device, so it arrives here): len > max_len; the
+ *                                            entries around the range's point do not ascend, or the point's bit lies at or behind
+ *                                            8 x in_len; lo - d_ix_out[k] >= max_gap or d_ix_out[k + 1] - d_ix_out[k] > max_gap.
+ *                               Every non-zero status reports got 0 and writes no byte.
+ *                               NO CHECK VALUE IS VERIFIED: the index was built from a verified stream, and a part of a stream has no
+ *                               CRC.  A caller who hands in other input than the index was built from gets that input's bytes.
+ *                               max_len 1 .. 2^30, max_gap <= 2^30, n_points >= 1 and non-NULL tables, otherwise ZMI_E_ARG as the
+ *                               return value; n_ranges 0 is a no-op.  A range decodes from the last point at or in front of lo, up to
+ *                               the byte that holds the first point at or behind its end.  Scratch of the context per range: 32 KiB +
+ *                               max_gap + max_len, an eighth of that again, 128 bytes; ranges beyond the scratch limit run in launch
+ *                               groups.  Bytes and words do not depend on the limit, the order of the ranges, n_ranges or the decode
+ *                               kernel.  Event timing: 5 = plan and history, 3 / 6 = decode, resolve, 4 = the decode's status step,
+ *                               7 = got / status and the trimmed copy. */
+int zmi_inflate_stream_index_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, int wrap, const uint64_t* d_cuts, uint32_t n_cuts,
+                                 uint32_t piece_out_max, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used,
+                                 int32_t* d_status, int32_t* d_detail, uint64_t span, uint64_t* d_ix_bit, uint64_t* d_ix_out, void* d_ix_win,
+                                 uint32_t ix_cap, uint32_t* d_n_points, uint64_t* d_max_gap, void* stream);
+int zmi_inflate_ranges_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, const uint64_t* d_ix_bit, const uint64_t* d_ix_out,
+                           const void* d_ix_win, uint32_t n_points, uint64_t max_gap, const uint64_t* d_lo, const uint32_t* d_len,
+                           uint32_t n_ranges, uint32_t max_len, void* d_out, const uint64_t* d_out_off, uint64_t out_stride, uint32_t* d_got,
+                           int32_t* d_status, void* stream);
+
 /* ---- multi-member gzip files: what zmi_pack_slab_dev and the exchange calls write with the gzip wrapper, bgzip / BGZF, `cat a.gz b.gz`,
  * pigz -i -- read by the reference one member after the other (libz-rs-sys/src/gz.rs:1464-1506).  Two calls, both asynchronous on
  * `stream`, neither synchronises with the host, every result is a device word.

@@ -60,6 +60,9 @@ def lib():
     # ... of streams without flush points: cuts at bit positions, proposed by the block scan (csrc/blockscan.hip)
     L.zmi_stream_find_blocks_dev.argtypes = [vp, vp, u64, i32, u64, vp, u32, vp, vp]
     L.zmi_inflate_stream_bits_dev.argtypes = [vp, vp, u64, i32, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp]
+    # random access into one stream: the index kept while it is decoded, byte ranges read from it (csrc/inflate.hip, zmi_api.hip)
+    L.zmi_inflate_stream_index_dev.argtypes = [vp, vp, u64, i32, vp, u32, u32, vp, u64, vp, vp, vp, vp, u64, vp, vp, vp, u32, vp, vp, vp]
+    L.zmi_inflate_ranges_dev.argtypes = [vp, vp, u64, vp, vp, vp, u32, u64, vp, vp, u32, u32, vp, vp, u64, vp, vp, vp]
     # multi-member gzip files: proposals of member starts, then every member decoded in place and verified
     L.zmi_gzip_find_members_dev.argtypes = [vp, vp, u64, vp, u32, vp, vp]
     L.zmi_inflate_members_dev.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp]

@@ -3152,3 +3152,242 @@ extern "C" int zmi_launch_mm_final(const uint64_t* d_starts, uint32_t n, uint32_
                lr_st, lr_used, lr_det, chk_trailer, chk_crc, d_out_len, d_in_used, d_members, d_member_off, d_status, d_detail);
     return 0;
 }
+
+// ==== random access into one stream (zmi_inflate_stream_index_dev, zmi_inflate_ranges_dev) ===================
+// The index: a thinned list of verified piece starts (bit position, output offset, the 32 KiB of output in front), kept while the
+// stream pipeline above decodes a stream once.  A range read enters the stream at the last point at or in front of its first byte.
+#define IX_NONE 0xFFFFFFFFu
+#define IX_E_ARG (-103)              // ZMI_E_ARG (include/zmi355.h), in a range's status word
+#define IX_TAIL 258u                 // a decode that stops for want of room stops in front of a token: no token is longer
+
+// One wave per launch group.  The greedy rule of find_blocks' min_gap, applied to output offsets: point k + 1 is the first piece
+// start g with off[g] >= ix_out[k] + span.  The state (count, last offset, greatest gap) lives in *n_points, ix_out[count - 1] and
+// *max_gap, so the walk continues where the group before stopped.  off[] ascends (a prefix sum): the next point is looked for among
+// the next 64 entries with one ballot, behind them by bisection.
+__global__ void __launch_bounds__(64) zmi_ix_select_kernel(const uint64_t* __restrict__ cuts, const uint64_t* __restrict__ off, uint32_t first,
+                                                           uint32_t cnt, uint64_t span, uint64_t* ix_bit, uint64_t* ix_out, uint32_t ix_cap,
+                                                           uint32_t* n_points, uint64_t* max_gap) {
+    const uint32_t lane = zmi_lane();
+    uint32_t n = *n_points, pos = 0;
+    uint64_t mg = *max_gap;
+    uint64_t last = n ? ix_out[n - 1u] : 0ull;
+    const uint64_t step = span ? span : 1ull;
+    if (first == 0u && cnt != 0u && ix_cap != 0u) {   // point 0: the end of the header
+        if (lane == 0) { ix_bit[0] = cuts[0]; ix_out[0] = off[0]; }
+        n = 1u; last = off[0]; pos = 1u;
+    }
+    while (n < ix_cap && pos < cnt) {
+        const uint64_t target = last + step < last ? ~0ull : last + step;
+        const uint32_t i = pos + lane;
+        const uint64_t hit = __ballot(i < cnt && off[i] >= target);
+        uint32_t g;
+        if (hit) g = pos + (uint32_t)__ffsll((unsigned long long)hit) - 1u;
+        else {
+            uint32_t lo = pos + 64u, hi = cnt;
+            if (lo >= hi) break;
+            while (lo < hi) {
+                const uint32_t mid = lo + ((hi - lo) >> 1);
+                if (off[mid] >= target) hi = mid; else lo = mid + 1u;
+            }
+            if (lo >= cnt) break;
+            g = lo;
+        }
+        const uint64_t o = off[g];
+        if (lane == 0) { ix_bit[n] = cuts[first + g]; ix_out[n] = o; }
+        mg = o - last > mg ? o - last : mg;
+        last = o;
+        ++n;
+        pos = g + 1u;
+    }
+    if (lane == 0) { *n_points = n; *max_gap = mg; }
+}
+
+// One workgroup per piece of the group; only those of selected pieces copy.  A piece is selected if the point list holds its
+// (output offset, bit position) pair: ix_out ascends strictly, so one bisection finds the candidate.
+__global__ void __launch_bounds__(256) zmi_ix_gather_kernel(const uint64_t* __restrict__ cuts, const uint64_t* __restrict__ off, uint32_t first,
+                                                            const uint64_t* __restrict__ ix_bit, const uint64_t* __restrict__ ix_out,
+                                                            const uint32_t* __restrict__ n_points, const uint8_t* __restrict__ win,
+                                                            uint8_t* __restrict__ ix_win) {
+    __shared__ uint32_t ksel;
+    const uint32_t i = blockIdx.x, t = threadIdx.x;
+    if (t == 0) {
+        const uint32_t n = *n_points;
+        const uint64_t o = off[i];
+        uint32_t lo = 0, hi = n;   // the last k with ix_out[k] <= o
+        while (hi - lo > 1u) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (ix_out[mid] <= o) lo = mid; else hi = mid;
+        }
+        ksel = (n != 0u && ix_out[lo] == o && ix_bit[lo] == cuts[first + i]) ? lo : IX_NONE;
+    }
+    __syncthreads();
+    const uint32_t k = ksel;
+    if (k == IX_NONE) return;
+    const uint4* s = (const uint4*)(win + (uint64_t)i * SI_HIST);
+    uint4* d = (uint4*)(ix_win + (uint64_t)k * SI_HIST);
+    for (uint32_t j = t; j < SI_HIST / 16u; j += 256u) d[j] = s[j];
+}
+
+// Thread 0, behind zmi_si_final_kernel: a stream that did not verify has no index; a verified one gets its total and the last gap.
+__global__ void __launch_bounds__(64) zmi_ix_final_kernel(const int32_t* __restrict__ status, const uint64_t* __restrict__ total, uint64_t* ix_out,
+                                                          uint32_t* n_points, uint64_t* max_gap) {
+    if (threadIdx.x != 0) return;
+    const uint32_t n = *n_points;
+    if (*status != 0 || n == 0u) { *n_points = 0u; *max_gap = 0ull; return; }
+    const uint64_t T = *total, last = ix_out[n - 1u];
+    ix_out[n] = T;
+    if (T - last > *max_gap) *max_gap = T - last;
+}
+
+extern "C" int zmi_launch_ix_select(const uint64_t* d_cuts, const uint64_t* d_off, uint32_t first, uint32_t cnt, uint64_t span, uint64_t* d_ix_bit,
+                                    uint64_t* d_ix_out, uint32_t ix_cap, uint32_t* d_n_points, uint64_t* d_max_gap, hipStream_t stream) {
+    if (cnt == 0) return 0;
+    ZMI_LAUNCH(zmi_ix_select_kernel, dim3(1), dim3(64), 0, stream, d_cuts, d_off, first, cnt, span, d_ix_bit, d_ix_out, ix_cap, d_n_points, d_max_gap);
+    return 0;
+}
+extern "C" int zmi_launch_ix_gather(const uint64_t* d_cuts, const uint64_t* d_off, uint32_t first, uint32_t cnt, const uint64_t* d_ix_bit,
+                                    const uint64_t* d_ix_out, const uint32_t* d_n_points, const uint8_t* d_win, uint8_t* d_ix_win,
+                                    hipStream_t stream) {
+    if (cnt == 0) return 0;
+    ZMI_LAUNCH(zmi_ix_gather_kernel, dim3(cnt), dim3(256), 0, stream, d_cuts, d_off, first, d_ix_bit, d_ix_out, d_n_points, d_win, d_ix_win);
+    return 0;
+}
+extern "C" int zmi_launch_ix_final(const int32_t* d_status, const uint64_t* d_total, uint64_t* d_ix_out, uint32_t* d_n_points, uint64_t* d_max_gap,
+                                   hipStream_t stream) {
+    ZMI_LAUNCH(zmi_ix_final_kernel, dim3(1), dim3(64), 0, stream, d_status, d_total, d_ix_out, d_n_points, d_max_gap);
+    return 0;
+}
+
+// ---- range reads: plan, history, finish --------------------------------------------------------------------------------------------
+// Range r = first + i of the launch group decodes from point k = the last one with ix_out[k] <= lo into the region at i * rstride:
+// [32 KiB history | output], skip = lo - ix_out[k] bytes in front of what it wants, need = skip + len' (len' = the length inside the
+// stream's total).  Its input ends with the byte that holds the first point at or behind lo + len' (in_len where there is none).
+// The decode's room is need + IX_TAIL, so a decode that stopped for want of room has passed need.
+// pre[i]: 0 decode, 1 nothing to decode (got 0, status 0), below 0 the status word.  A range that does not decode is an empty
+// stream with no room.
+struct RgTab {
+    uint64_t *ioff, *ooff;
+    uint32_t *in_n, *cap, *hist, *bit, *skip, *need, *k;
+    int32_t* pre;
+};
+__global__ void __launch_bounds__(256) zmi_rg_plan_kernel(const uint64_t* __restrict__ ix_bit, const uint64_t* __restrict__ ix_out, uint32_t n_points,
+                                                          uint32_t has_win, uint64_t in_len, uint64_t max_gap, const uint64_t* __restrict__ lo_,
+                                                          const uint32_t* __restrict__ len, uint32_t first, uint32_t cnt, uint32_t max_len,
+                                                          uint64_t rstride, RgTab T) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= cnt) return;
+    const uint32_t r = first + i;
+    const uint32_t L = len[r];
+    const uint64_t a = lo_[r], total = ix_out[n_points];
+    uint64_t ioff = 0;
+    uint32_t in_n = 0, cap = 0, hist = 0, bit = 0, skip = 0, need = 0, k = 0;
+    int32_t pre = IX_E_ARG;
+    if (L > max_len) pre = IX_E_ARG;
+    else if (L == 0u || a >= total) pre = 1;
+    else {
+        uint32_t lo = 0, hi = n_points;   // the last k with ix_out[k] <= a
+        while (hi - lo > 1u) {
+            const uint32_t mid = lo + ((hi - lo) >> 1);
+            if (ix_out[mid] <= a) lo = mid; else hi = mid;
+        }
+        const uint64_t o0 = ix_out[lo], o1 = ix_out[lo + 1u];
+        const bool ascends = lo == 0u || ix_out[lo - 1u] < o0;   // (with o0 <= a < o1: the entries on both sides of the point)
+        if (ascends && o0 <= a && a < o1 && o1 - o0 <= max_gap && a - o0 < max_gap) {
+            const uint64_t Lc = total - a < (uint64_t)L ? total - a : (uint64_t)L, endo = a + Lc;
+            uint32_t el = lo + 1u, eh = n_points;   // the first e behind k with ix_out[e] >= endo (n_points: the total)
+            while (el < eh) {
+                const uint32_t mid = el + ((eh - el) >> 1);
+                if (ix_out[mid] >= endo) eh = mid; else el = mid + 1u;
+            }
+            const uint64_t b0 = ix_bit[lo];
+            if (b0 < 8ull * in_len) {
+                uint64_t end = in_len;
+                bool bad = false;
+                if (el < n_points) {
+                    const uint64_t b1 = ix_bit[el];
+                    if (b1 <= b0) bad = true;
+                    else if ((b1 >> 3) + 1u < end) end = (b1 >> 3) + 1u;
+                }
+                const uint64_t start = b0 >> 3;
+                if (!bad && end - start <= 0xFFFFFF00ull) {
+                    ioff = start; in_n = (uint32_t)(end - start); bit = (uint32_t)(b0 & 7u);
+                    skip = (uint32_t)(a - o0); need = skip + (uint32_t)Lc; cap = need + IX_TAIL;
+                    hist = has_win ? (o0 < SI_HIST ? (uint32_t)o0 : SI_HIST) : 0u;
+                    k = lo;
+                    pre = 0;
+                }
+            }
+        }
+    }
+    T.ioff[i] = ioff; T.ooff[i] = (uint64_t)i * rstride + SI_HIST;
+    T.in_n[i] = in_n; T.cap[i] = cap; T.hist[i] = hist; T.bit[i] = bit; T.skip[i] = skip; T.need[i] = need; T.k[i] = k; T.pre[i] = pre;
+}
+
+// the window of range i's point, in front of its region's output (16-byte lanes; the window is right-aligned: its last `hist` bytes count)
+__global__ void __launch_bounds__(256) zmi_rg_hist_kernel(const uint8_t* __restrict__ ix_win, const uint32_t* __restrict__ k, const uint32_t* __restrict__ hist,
+                                                          const int32_t* __restrict__ pre, uint64_t rstride, uint8_t* __restrict__ work) {
+    const uint32_t i = blockIdx.x, t = threadIdx.x;
+    if (pre[i] != 0 || hist[i] == 0u) return;
+    const uint4* s = (const uint4*)(ix_win + (uint64_t)k[i] * SI_HIST);
+    uint4* d = (uint4*)(work + (uint64_t)i * rstride);
+    for (uint32_t j = t; j < SI_HIST / 16u; j += 256u) d[j] = s[j];
+}
+
+// got / status of every range of the group, and the table of the trimmed copy: [skip, skip + got) of its region to its place.
+// A decode that passed `need` delivered the range whatever stopped it afterwards; one that did not reports why.
+__global__ void __launch_bounds__(256) zmi_rg_finish_kernel(RgTab T, const uint32_t* __restrict__ olen, const int32_t* __restrict__ st,
+                                                            const int32_t* __restrict__ det, uint32_t first, uint32_t cnt,
+                                                            const uint64_t* __restrict__ out_off, uint64_t out_stride, uint32_t* __restrict__ got_,
+                                                            int32_t* __restrict__ status, uint64_t* __restrict__ c_src, uint32_t* __restrict__ c_len,
+                                                            uint64_t* __restrict__ c_dst) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= cnt) return;
+    const uint32_t r = first + i;
+    const int32_t pre = T.pre[i];
+    uint32_t got = 0;
+    int32_t s;
+    if (pre < 0) s = pre;
+    else if (pre == 1) s = 0;
+    else if (olen[i] >= T.need[i]) { s = 0; got = T.need[i] - T.skip[i]; }
+    else if (st[i] == ZMI_BUF_ERROR && det[i] == 1) s = ZMI_BUF_ERROR;
+    else if (st[i] == ZMI_OK || st[i] == ZMI_BUF_ERROR) s = ZMI_DATA_ERROR;   // (the stream ends in front of what the index promises)
+    else s = st[i];
+    got_[r] = got;
+    status[r] = s;
+    c_src[i] = T.ooff[i] + T.skip[i];
+    c_len[i] = got;
+    c_dst[i] = out_off ? out_off[r] : (uint64_t)r * out_stride;
+}
+
+static RgTab rg_tab(uint64_t* d_ioff, uint64_t* d_ooff, uint32_t* d_u32, uint32_t g) {
+    RgTab T;
+    T.ioff = d_ioff; T.ooff = d_ooff;
+    T.in_n = d_u32; T.cap = d_u32 + g; T.hist = d_u32 + 2u * (size_t)g; T.bit = d_u32 + 3u * (size_t)g; T.skip = d_u32 + 4u * (size_t)g;
+    T.need = d_u32 + 5u * (size_t)g; T.k = d_u32 + 6u * (size_t)g; T.pre = (int32_t*)(d_u32 + 7u * (size_t)g);
+    return T;
+}
+// d_u32: eight u32[g] tables (in_n | cap | hist | bit | skip | need | k | pre)
+extern "C" int zmi_launch_rg_plan(const uint64_t* d_ix_bit, const uint64_t* d_ix_out, uint32_t n_points, uint32_t has_win, uint64_t in_len,
+                                  uint64_t max_gap, const uint64_t* d_lo, const uint32_t* d_len, uint32_t first, uint32_t cnt, uint32_t max_len,
+                                  uint64_t rstride, uint64_t* d_ioff, uint64_t* d_ooff, uint32_t* d_u32, uint32_t g, hipStream_t stream) {
+    if (cnt == 0) return 0;
+    ZMI_LAUNCH(zmi_rg_plan_kernel, dim3((cnt + 255u) / 256u), dim3(256), 0, stream, d_ix_bit, d_ix_out, n_points, has_win, in_len, max_gap, d_lo,
+               d_len, first, cnt, max_len, rstride, rg_tab(d_ioff, d_ooff, d_u32, g));
+    return 0;
+}
+extern "C" int zmi_launch_rg_hist(const uint8_t* d_ix_win, const uint32_t* d_u32, uint32_t g, uint32_t cnt, uint64_t rstride, uint8_t* d_work,
+                                  hipStream_t stream) {
+    if (cnt == 0) return 0;
+    const RgTab T = rg_tab(nullptr, nullptr, (uint32_t*)d_u32, g);
+    ZMI_LAUNCH(zmi_rg_hist_kernel, dim3(cnt), dim3(256), 0, stream, d_ix_win, (const uint32_t*)T.k, (const uint32_t*)T.hist, (const int32_t*)T.pre,
+               rstride, d_work);
+    return 0;
+}
+extern "C" int zmi_launch_rg_finish(uint64_t* d_ioff, uint64_t* d_ooff, uint32_t* d_u32, uint32_t g, const uint32_t* d_olen, const int32_t* d_st,
+                                    const int32_t* d_det, uint32_t first, uint32_t cnt, const uint64_t* d_out_off, uint64_t out_stride,
+                                    uint32_t* d_got, int32_t* d_status, uint64_t* d_c_src, uint32_t* d_c_len, uint64_t* d_c_dst, hipStream_t stream) {
+    if (cnt == 0) return 0;
+    ZMI_LAUNCH(zmi_rg_finish_kernel, dim3((cnt + 255u) / 256u), dim3(256), 0, stream, rg_tab(d_ioff, d_ooff, d_u32, g), d_olen, d_st, d_det, first,
+               cnt, d_out_off, out_stride, d_got, d_status, d_c_src, d_c_len, d_c_dst);
+    return 0;
+}

@@ -2210,9 +2210,11 @@ extern "C" int zmi_inflate_resume(zmi_ctx* c, const uint8_t* in, uint32_t in_len
 #define ZMI_SI_SLACK 4096u
 // bits: the cuts are bit offsets (zmi_inflate_stream_bits_dev) -- the pieces' start bits go to the decode, the setup and verify steps
 // are the bit forms; everything else is one code path
+// ix (zmi_inflate_stream_index_dev; null: nothing more is enqueued): the access points kept while the stream is decoded
+struct zmi_si_index { uint64_t span; uint64_t *bit, *out; uint8_t* win; uint32_t cap; uint32_t* n_points; uint64_t* max_gap; };
 static int zmi_inflate_stream_body(zmi_ctx* c, const void* d_in, uint64_t in_len, int wrap, const uint64_t* d_cuts, uint32_t n_cuts,
                                    uint32_t piece_out_max, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used,
-                                   int32_t* d_status, int32_t* d_detail, void* stream_, bool bits) {
+                                   int32_t* d_status, int32_t* d_detail, void* stream_, bool bits, const zmi_si_index* ix = nullptr) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_AUTO) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip/auto");
     if (n_cuts == 0 || !d_cuts)
@@ -2266,6 +2268,10 @@ static int zmi_inflate_stream_body(zmi_ctx* c, const void* d_in, uint64_t in_len
     ZMI_HIP(hipMemsetAsync(d_tail, 0, 8, stream));
     ZMI_HIP(hipMemsetAsync(d_chk, 0, 8, stream));
     ZMI_HIP(hipMemsetAsync(d_carry, 0, ZMI_SI_WIN, stream));
+    if (ix) {
+        ZMI_HIP(hipMemsetAsync(ix->n_points, 0, 4, stream));
+        ZMI_HIP(hipMemsetAsync(ix->max_gap, 0, 8, stream));
+    }
     {
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
         zmi_launch_si_header((const uint8_t*)d_in, in_len, (uint32_t)wrap, d_hdr, stream);
@@ -2319,6 +2325,11 @@ static int zmi_inflate_stream_body(zmi_ctx* c, const void* d_in, uint64_t in_len
             zmi_scope_timer tm(c, ZMI_K_CHECKSUM, stream);
             zmi_launch_checksum((const uint8_t*)d_out, d_off + f, d_clen + f, cnt, kind, d_adler + f, d_crc + f, stream);
         }
+        if (ix) {   // the group's points (the walk goes on from the device words the group before left), then their windows out of w_win
+            zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+            zmi_launch_ix_select(d_cuts, d_off + f, f, cnt, ix->span, ix->bit, ix->out, ix->cap, ix->n_points, ix->max_gap, stream);
+            if (ix->win) zmi_launch_ix_gather(d_cuts, d_off + f, f, cnt, ix->bit, ix->out, ix->n_points, W + w_win, ix->win, stream);
+        }
         ZMI_HIP(hipGetLastError());
     }
     if (kind == 1u || kind == 3u) { rc = zmi_checksum_combine_dev(c, ZMI_WRAP_ZLIB, d_adler, d_clen, 1u, n_cuts, d_chk, nullptr, stream_); if (rc) return rc; }
@@ -2327,6 +2338,7 @@ static int zmi_inflate_stream_body(zmi_ctx* c, const void* d_in, uint64_t in_len
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
         zmi_launch_si_final((const uint8_t*)d_in, in_len, d_hdr, d_cuts, bits ? 3u : 0u, d_bad, d_tail, d_off + n, d_chk, d_chk + 1, out_cap, d_status,
                             d_detail, d_out_len, d_in_used, stream);
+        if (ix) zmi_launch_ix_final(d_status, d_off + n, ix->out, ix->n_points, ix->max_gap, stream);
     }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;
@@ -2342,6 +2354,90 @@ extern "C" int zmi_inflate_stream_bits_dev(zmi_ctx* c, const void* d_in, uint64_
                                            int32_t* d_status, int32_t* d_detail, void* stream_) {
     return zmi_inflate_stream_body(c, d_in, in_len, wrap, d_cuts, n_cuts, piece_out_max, d_out, out_cap, d_out_len, d_in_used, d_status, d_detail,
                                    stream_, true);
+}
+
+
+// ---- random access into one stream (include/zmi355.h) ----------------------------------------------------------
+// The stream body with an index: per launch group the greedy selection over the group's output offsets and the gather of the selected
+// pieces' windows out of the window scan's result; behind the trailer check the closing step, which voids the index of a stream that
+// did not verify.
+extern "C" int zmi_inflate_stream_index_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, int wrap, const uint64_t* d_cuts, uint32_t n_cuts,
+                                            uint32_t piece_out_max, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used,
+                                            int32_t* d_status, int32_t* d_detail, uint64_t span, uint64_t* d_ix_bit, uint64_t* d_ix_out,
+                                            void* d_ix_win, uint32_t ix_cap, uint32_t* d_n_points, uint64_t* d_max_gap, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (ix_cap == 0) return zmi_fail(ZMI_E_ARG, "zmi_inflate_stream_index_dev: ix_cap must be at least 1");
+    if (!d_ix_bit || !d_ix_out || !d_n_points || !d_max_gap) return zmi_fail(ZMI_E_ARG, "zmi_inflate_stream_index_dev: null index argument");
+    if ((uintptr_t)d_ix_win & 15u) return zmi_fail(ZMI_E_ARG, "zmi_inflate_stream_index_dev: d_ix_win must be 16-byte aligned");
+    const zmi_si_index ix{span, d_ix_bit, d_ix_out, (uint8_t*)d_ix_win, ix_cap, d_n_points, d_max_gap};
+    return zmi_inflate_stream_body(c, d_in, in_len, wrap, d_cuts, n_cuts, piece_out_max, d_out, out_cap, d_out_len, d_in_used, d_status, d_detail,
+                                   stream_, true, &ix);
+}
+
+// Per launch group of ranges, all on `stream`: plan (one lane per range) -> the points' windows in front of the regions -> decode and
+// resolve (raw, from a bit position, history in front: the form zmi_inflate_resume_dev uses) -> got / status and the copy table ->
+// the trimmed copy.  Scratch per range: 32 KiB + max_gap + max_len + 514 rounded to 16, an eighth of that as bitmap, 128 bytes of
+// tables.
+#define ZMI_RG_TAIL 258u   // IX_TAIL, inflate.hip
+extern "C" int zmi_inflate_ranges_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, const uint64_t* d_ix_bit, const uint64_t* d_ix_out,
+                                      const void* d_ix_win, uint32_t n_points, uint64_t max_gap, const uint64_t* d_lo, const uint32_t* d_len,
+                                      uint32_t n_ranges, uint32_t max_len, void* d_out, const uint64_t* d_out_off, uint64_t out_stride,
+                                      uint32_t* d_got, int32_t* d_status, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (n_points == 0 || !d_ix_bit || !d_ix_out) return zmi_fail(ZMI_E_ARG, "zmi_inflate_ranges_dev: an index of at least one point");
+    if (max_len == 0 || max_len > (1u << 30)) return zmi_fail(ZMI_E_ARG, "zmi_inflate_ranges_dev: max_len must be 1 .. 2^30");
+    if (max_gap > (1ull << 30)) return zmi_fail(ZMI_E_ARG, "zmi_inflate_ranges_dev: max_gap must be at most 2^30");
+    if (in_len >= (1ull << 60)) return zmi_fail(ZMI_E_ARG, "in_len must be below 2^60 (bit offsets are 64-bit)");
+    if ((uintptr_t)d_ix_win & 15u) return zmi_fail(ZMI_E_ARG, "zmi_inflate_ranges_dev: d_ix_win must be 16-byte aligned");
+    if (n_ranges == 0) return ZMI_E_OK;
+    if ((in_len && !d_in) || !d_lo || !d_len || !d_out || !d_got || !d_status) return zmi_fail(ZMI_E_ARG, "null argument");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    const uint64_t room = ((max_gap + max_len + ZMI_RG_TAIL + 15u) & ~15ull) + 256u;
+    const uint64_t rstride = ZMI_SI_WIN + room;
+    const uint64_t per = rstride + room / 8u + 128u + 32u;
+    uint64_t group = c->scratch_limit / per;
+    if (group == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one range");
+    if (group > n_ranges) group = n_ranges;
+    const uint32_t G = (uint32_t)group;
+    const size_t g = G;
+    // launch group: in_off | out_off | copy src | copy dst (u64[G] each) | in_n | cap | hist | bit | skip | need | k | pre | olen | st |
+    // used | det | copy len (u32[G] each) | res u32[4G] | the regions
+    const size_t w_ioff = 0, w_ooff = 8 * g, w_csrc = 16 * g, w_cdst = 24 * g, w_u32 = 32 * g, w_olen = w_u32 + 32 * g, w_st = w_olen + 4 * g,
+                 w_used = w_st + 4 * g, w_det = w_used + 4 * g, w_clen = w_det + 4 * g, w_res = w_clen + 4 * g,
+                 w_reg = (w_res + 16 * g + 255) & ~(size_t)255, work_bytes = w_reg + g * rstride;
+    int rc = zmi_reserve(c->si_work, work_bytes);
+    if (rc) return rc;
+    uint8_t* W = (uint8_t*)c->si_work.p;
+    uint32_t* d_u32 = (uint32_t*)(W + w_u32);   // in_n | cap | hist | bit | ... (rg_tab, inflate.hip)
+    // the decode's bitmap covers one group's rooms
+    const uint64_t saved_limit = c->inflate_out_limit;
+    c->inflate_out_limit = group * room + (1ull << 16);
+    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; } } restore_limit{c, saved_limit};
+    for (uint64_t first = 0; first < n_ranges; first += group) {
+        const uint32_t cnt = (uint32_t)(n_ranges - first < group ? n_ranges - first : group);
+        const uint32_t f = (uint32_t)first;
+        {
+            zmi_scope_timer tm(c, ZMI_K_PARSE, stream);   // (plan and history; an inflate call runs no cost parse)
+            zmi_launch_rg_plan(d_ix_bit, d_ix_out, n_points, d_ix_win ? 1u : 0u, in_len, max_gap, d_lo, d_len, f, cnt, max_len, rstride,
+                               (uint64_t*)(W + w_ioff), (uint64_t*)(W + w_ooff), d_u32, G, stream);
+            if (d_ix_win) zmi_launch_rg_hist((const uint8_t*)d_ix_win, d_u32, G, cnt, rstride, W + w_reg, stream);
+        }
+        rc = zmi_inflate_impl(c, d_in, (const uint64_t*)(W + w_ioff), d_u32, cnt, ZMI_WRAP_RAW, W + w_reg, (const uint64_t*)(W + w_ooff), d_u32 + g,
+                              d_u32 + 2 * g, (uint32_t*)(W + w_olen), (int32_t*)(W + w_st), (uint32_t*)(W + w_used), (int32_t*)(W + w_det),
+                              d_u32 + 3 * g, (uint32_t*)(W + w_res), stream_);
+        if (rc) return rc;
+        {
+            zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+            zmi_launch_rg_finish((uint64_t*)(W + w_ioff), (uint64_t*)(W + w_ooff), d_u32, G, (const uint32_t*)(W + w_olen), (const int32_t*)(W + w_st),
+                                 (const int32_t*)(W + w_det), f, cnt, d_out_off, out_stride, d_got, d_status, (uint64_t*)(W + w_csrc),
+                                 (uint32_t*)(W + w_clen), (uint64_t*)(W + w_cdst), stream);
+            zmi_launch_copy_ranges(W + w_reg, (const uint64_t*)(W + w_csrc), 0, (const uint32_t*)(W + w_clen), cnt, (uint8_t*)d_out,
+                                   (const uint64_t*)(W + w_cdst), ~0ull, max_len, stream);
+        }
+        ZMI_HIP(hipGetLastError());
+    }
+    return ZMI_E_OK;
 }
 
 extern "C" int zmi_stream_find_cuts_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, int wrap, uint64_t min_gap, uint64_t* d_cuts, uint32_t cap,

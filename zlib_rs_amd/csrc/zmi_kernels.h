@@ -162,6 +162,23 @@ int zmi_launch_si_verify_bits(const uint64_t* d_cuts, uint32_t n_cuts, uint32_t 
 int zmi_launch_si_clamp(const uint32_t* d_len, const uint64_t* d_off, uint32_t n, uint64_t out_cap, uint32_t* d_clen, hipStream_t stream);
 int zmi_launch_si_find_cuts(const uint8_t* d_in, uint64_t n, const uint32_t* d_hdr, uint32_t* d_seg, uint64_t min_gap, uint64_t* d_cuts,
                             uint32_t cap, uint32_t* d_n_cuts, hipStream_t stream);
+// random access into one stream (inflate.hip): the index kept by zmi_inflate_stream_index_dev -- the greedy selection of one launch
+// group's piece starts (its state is *d_n_points, d_ix_out[count - 1], *d_max_gap), the windows of the selected pieces, the closing
+// step -- and the plan / history / finish steps of zmi_inflate_ranges_dev.  d_u32: eight u32[g] tables, d_ioff / d_ooff: u64[g]
+int zmi_launch_ix_select(const uint64_t* d_cuts, const uint64_t* d_off, uint32_t first, uint32_t cnt, uint64_t span, uint64_t* d_ix_bit,
+                         uint64_t* d_ix_out, uint32_t ix_cap, uint32_t* d_n_points, uint64_t* d_max_gap, hipStream_t stream);
+int zmi_launch_ix_gather(const uint64_t* d_cuts, const uint64_t* d_off, uint32_t first, uint32_t cnt, const uint64_t* d_ix_bit,
+                         const uint64_t* d_ix_out, const uint32_t* d_n_points, const uint8_t* d_win, uint8_t* d_ix_win, hipStream_t stream);
+int zmi_launch_ix_final(const int32_t* d_status, const uint64_t* d_total, uint64_t* d_ix_out, uint32_t* d_n_points, uint64_t* d_max_gap,
+                        hipStream_t stream);
+int zmi_launch_rg_plan(const uint64_t* d_ix_bit, const uint64_t* d_ix_out, uint32_t n_points, uint32_t has_win, uint64_t in_len,
+                       uint64_t max_gap, const uint64_t* d_lo, const uint32_t* d_len, uint32_t first, uint32_t cnt, uint32_t max_len,
+                       uint64_t rstride, uint64_t* d_ioff, uint64_t* d_ooff, uint32_t* d_u32, uint32_t g, hipStream_t stream);
+int zmi_launch_rg_hist(const uint8_t* d_ix_win, const uint32_t* d_u32, uint32_t g, uint32_t cnt, uint64_t rstride, uint8_t* d_work,
+                       hipStream_t stream);
+int zmi_launch_rg_finish(uint64_t* d_ioff, uint64_t* d_ooff, uint32_t* d_u32, uint32_t g, const uint32_t* d_olen, const int32_t* d_st,
+                         const int32_t* d_det, uint32_t first, uint32_t cnt, const uint64_t* d_out_off, uint64_t out_stride, uint32_t* d_got,
+                         int32_t* d_status, uint64_t* d_c_src, uint32_t* d_c_len, uint64_t* d_c_dst, hipStream_t stream);
 // the block scan (blockscan.hip): the host-buffer form of zmi_inflate_blocks, and one window of the ordered form of
 // zmi_stream_find_blocks_dev
 int zmi_launch_block_scan(const uint8_t* d_in, uint32_t n, uint64_t first_bit, uint32_t* d_pre, uint32_t pre_cap, uint32_t* d_list,

@@ -23,6 +23,50 @@ def _stream_ptr():
     return torch.cuda.current_stream().cuda_stream
 
 
+class StreamIndex:
+    """Access points into ONE deflate stream (zmi_inflate_stream_index_dev, include/zmi355.h): bit int64 [n] (bit positions in the
+    stream), out int64 [n + 1] (output offsets, then the total), win uint8 [n, 32768] (the output in front of every point,
+    right-aligned; None: the points forget history) -- device tensors -- and max_gap, the greatest distance between two entries of
+    `out`."""
+    WIN = 32768
+
+    def __init__(self, bit, out, win, max_gap):
+        self.bit, self.out, self.win, self.max_gap = bit, out, win, int(max_gap)
+
+    @property
+    def n_points(self):
+        return int(self.bit.numel())
+
+    def save(self, path):
+        """one .npz: bit, out, max_gap and, where there are windows, win"""
+        import numpy as np
+        arrays = {"bit": self.bit.cpu().numpy(), "out": self.out.cpu().numpy(), "max_gap": np.array([self.max_gap], dtype=np.int64)}
+        if self.win is not None:
+            arrays["win"] = self.win.cpu().numpy()
+        with open(path, "wb") as f:
+            np.savez(f, **arrays)
+
+    @classmethod
+    def load(cls, path, device):
+        import numpy as np
+        with np.load(path) as z:
+            bit, out, gap = z["bit"], z["out"], int(z["max_gap"][0])
+            win = z["win"] if "win" in z.files else None
+        dev = torch.device(device)
+        return cls(torch.from_numpy(bit).to(dev), torch.from_numpy(out).to(dev), torch.from_numpy(win).to(dev) if win is not None else None, gap)
+
+    @classmethod
+    def from_pieces(cls, piece_off, piece_bytes, n):
+        """The history-free index of deflate_stream(independent=True, index=True): piece_off is that call's index (the byte offset
+        of every piece's first deflate byte, then the end of the deflate data), piece_bytes its piece size, n the length of the
+        data.  Every piece starts on a byte boundary and refers to nothing in front of it, so there are no windows."""
+        pieces = int(piece_off.numel()) - 1
+        bit = piece_off[:pieces].to(torch.int64) * 8
+        out = torch.arange(pieces + 1, dtype=torch.int64, device=piece_off.device) * int(piece_bytes)
+        out[pieces] = int(n)
+        return cls(bit, out, None, min(int(piece_bytes), int(n)))
+
+
 class Engine:
     def __init__(self, device=None, scratch_bytes=None):
         if not torch.cuda.is_available():
@@ -353,6 +397,92 @@ class Engine:
             else:
                 raise RuntimeError("%s: status %d detail %d (kind %d, index %d)" % (name, st, det, kind, at))
         raise RuntimeError("%s: no result after %d attempts" % (name, tries))
+
+    # ---- random access into one stream: index while inflating, then byte ranges (include/zmi355.h) ----
+    def inflate_stream_indexed(self, data, wrap=WRAP_AUTO, bit_cuts=None, min_gap=1 << 16, span=1 << 20, piece_out_max=None, out=None,
+                               out_cap=None):
+        """inflate_plain_stream that also keeps a StreamIndex -> (uint8 view of the output, in_used, index): a point at the end of
+        the header, then the first verified piece start at least `span` output bytes behind the point before, each with the 32 KiB
+        of output in front of it.  bit_cuts: the piece starts as BIT offsets (find_blocks'; a stream with flush points passes
+        8 * find_cuts(...)); None runs find_blocks(min_gap).  The loop is inflate_stream's -- a cut that does not verify is dropped, a
+        piece above piece_out_max doubles it, an output above the room is decoded again into a buffer of the reported size -- with one
+        synchronisation per try.  The index needs the whole output: there is no index-only build."""
+        cuts = self.find_blocks(data, wrap, min_gap) if bit_cuts is None else bit_cuts.to(torch.int64)
+        pom = min(1 << 30, max(1 << 20, 16 * int(min_gap))) if piece_out_max is None else int(piece_out_max)
+        n = int(data.numel())
+        name = "zmi_inflate_stream_index_dev"
+        if out is None:
+            out = torch.empty(int(out_cap) if out_cap is not None else 4 * n + (1 << 20), dtype=torch.uint8, device=self.device)
+        meta = torch.zeros(5, dtype=torch.int64, device=self.device)   # out_len | in_used | status, detail (int32) | n_points (int32) | max_gap
+        mp = meta.data_ptr()
+        tries = int(cuts.numel()) + 64
+        bufs = None
+        for _ in range(tries):
+            # points lie at least max(span, 1) output bytes apart
+            cap = max(1, min(int(cuts.numel()), int(out.numel()) // max(int(span), 1) + 2))
+            if bufs is None or bufs[0].numel() < cap:
+                bufs = (torch.empty(cap, dtype=torch.int64, device=self.device), torch.empty(cap + 1, dtype=torch.int64, device=self.device),
+                        torch.empty((cap, StreamIndex.WIN), dtype=torch.uint8, device=self.device))
+            bit, off, win = bufs
+            meta.zero_()
+            _lib.check(self.L.zmi_inflate_stream_index_dev(self._ctx, data.data_ptr() if n else None, n, int(wrap), cuts.data_ptr(),
+                                                           int(cuts.numel()), pom, out.data_ptr() if out.numel() else None, int(out.numel()), mp,
+                                                           mp + 8, mp + 16, mp + 20, int(span), bit.data_ptr(), off.data_ptr(), win.data_ptr(),
+                                                           int(bit.numel()), mp + 24, mp + 32, _stream_ptr()), name)
+            olen, used, sd, pts, gap = meta.tolist()
+            st = sd & 0xFFFFFFFF
+            st = st - (1 << 32) if st >= 1 << 31 else st
+            det = (sd >> 32) & 0xFFFFFFFF
+            kind, at = det & 0xFF, det >> 8
+            if st == 0:
+                self.last_piece_out_max = pom
+                k = pts & 0xFFFFFFFF
+                return out[:olen], used, StreamIndex(bit[:k], off[:k + 1], win[:k], gap)
+            if kind == SI_CUT and 0 < at < cuts.numel():
+                cuts = torch.cat([cuts[:at], cuts[at + 1:]])
+            elif kind == SI_PIECE and pom < (1 << 30):
+                pom = min(pom * 2, 1 << 30)
+            elif kind == SI_OUT:
+                out = torch.empty(olen, dtype=torch.uint8, device=self.device)
+            else:
+                raise RuntimeError("%s: status %d detail %d (kind %d, index %d)" % (name, st, det, kind, at))
+        raise RuntimeError("%s: no result after %d attempts" % (name, tries))
+
+    def read_ranges(self, data, index, lo, lengths, out=None, out_offsets=None, max_len=None):
+        """Byte ranges [lo[i], lo[i] + lengths[i]) of the OUTPUT of the stream `data`, through its StreamIndex -> (out, got int32 [n],
+        status int32 [n]).  lo (int64) and lengths (int32) are device tensors or lists.  Range i lands at out_offsets[i] (int64 device
+        tensor) of `out`, or in row i of the [n, max_len] buffer this call allocates; got[i] counts its bytes (less than asked where
+        the stream ends), status[i] is 0, Z_DATA_ERROR, Z_BUF_ERROR or -103 (include/zmi355.h); a range with a non-zero status writes
+        nothing.  No check value is verified.  max_len bounds every length (it sizes the scratch); None takes the row length of `out`,
+        or reads the greatest length from the device when `out` is not given -- the only synchronisation of this call."""
+        if not torch.is_tensor(lo):
+            lo = torch.tensor(list(lo), dtype=torch.int64, device=self.device)
+        if not torch.is_tensor(lengths):
+            if max_len is None and out is None:
+                max_len = max(list(lengths) + [1])
+            lengths = torch.tensor(list(lengths), dtype=torch.int32, device=self.device)
+        n = int(lengths.numel())
+        got = torch.zeros(n, dtype=torch.int32, device=self.device)
+        status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        if out is None:
+            if max_len is None:
+                max_len = max(1, int(lengths.max().item())) if n else 1
+            out = torch.empty((n, int(max_len)), dtype=torch.uint8, device=self.device)
+        stride = 0
+        if out_offsets is None:
+            stride = int(out.stride(0)) if out.dim() == 2 else (int(out.numel()) // n if n else 0)
+        if max_len is None:
+            max_len = stride if out_offsets is None else int(out.numel())
+        max_len = max(1, min(int(max_len), 1 << 30))
+        if n == 0:
+            return out, got, status
+        nd = int(data.numel())
+        _lib.check(self.L.zmi_inflate_ranges_dev(self._ctx, data.data_ptr() if nd else None, nd, index.bit.data_ptr(), index.out.data_ptr(),
+                                                 index.win.data_ptr() if index.win is not None and index.win.numel() else None,
+                                                 index.n_points, int(index.max_gap), lo.data_ptr(), lengths.data_ptr(), n, max_len,
+                                                 out.data_ptr(), out_offsets.data_ptr() if out_offsets is not None else None, stride,
+                                                 got.data_ptr(), status.data_ptr(), _stream_ptr()), "zmi_inflate_ranges_dev")
+        return out, got, status
 
     def deflate_pieces(self, data, offsets, lengths, max_len, level=6, strategy=0, wrap=WRAP_GZIP, independent=True, final=True):
         """One rank's pieces of a single stream: (slots [n, stride] uint8, sizes int32 [n], checks int32 [n], status int32 [n])."""

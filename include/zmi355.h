@@ -551,6 +551,48 @@ int zmi_inflate_members_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, con
                             uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_in_used, uint32_t* d_members, uint64_t* d_member_off,
                             int32_t* d_status, int32_t* d_detail, void* stream);
 
+/* ---- writing BGZF: the blocked gzip file that samtools, tabix, bcftools and everything on htslib's bgzf_* seek in (the calls above
+ * read it).  A block is a gzip member of at most 64 KiB that names its own size:
+ *     1f 8b 08 04 | MTIME 0 0 0 0 | XFL 0 | OS ff | XLEN 06 00 | 'B' 'C' 02 00 | BSIZE u16 LE     (18 bytes; BSIZE = block size - 1)
+ *     a complete raw deflate stream (BFINAL set) | CRC-32 u32 LE | ISIZE u32 LE
+ * -- htslib's own header bytes -- and the file ends with the empty block
+ *     1f 8b 08 04 00 00 00 00 00 ff 06 00 42 43 02 00 1b 00 03 00 00 00 00 00 00 00 00 00      (ZMI_BGZF_EOF bytes).
+ * The deflate stream of a block is what zmi_deflate_batch_dev(..., ZMI_WRAP_RAW) writes for that shard (blocks of at most
+ * ZMI_BGZF_BLOCK_MAX bytes are one encoder piece), so a block's bytes depend on its own bytes, level and strategy alone -- not on
+ * n_blocks, its index, the alignment of the input, the scratch limit or the launch grouping.  One exception: where that stream is
+ * longer than len + 5 bytes the block carries ONE stored block instead, 01 | LEN u16 | ~LEN u16 | the raw bytes (what htslib does when
+ * a block overflows).  Every block is therefore at most len + 31 <= 65311 bytes and BSIZE fits, whatever the encoder's block splitting
+ * does; an empty shard is the 28 bytes above (payload 03 00).
+ *
+ * zmi_bgzf_bound        the exact worst case: ceil(n / block_bytes) blocks of 31 + their length, plus ZMI_BGZF_EOF; block_bytes 0: 0.
+ * zmi_bgzf_blocks_dev   the batch form, and a rank's building block.  Shard i = d_in[d_in_off[i] .. + d_in_len[i]), any layout, every
+ *                       length <= max_len <= ZMI_BGZF_BLOCK_MAX (a larger max_len: ZMI_E_ARG; a larger d_in_len[i]: ZMI_E_ARG in
+ *                       *d_status, the table lives on the device -- that shard becomes an empty block).  The blocks stand dense at
+ *                       d_out + d_block_off[i]; d_block_off[n_blocks] = their total, exact whether or not they fitted;
+ *                       d_block_len (NULL or n_blocks entries) = the block sizes as u32, the table zmi_exchange_sizes takes.  No
+ *                       end-of-file block.  n_blocks 0: d_block_off[0] = 0, status 0.
+ * zmi_bgzf_deflate_dev  a whole buffer: block i = [i * block_bytes, min(n, (i + 1) * block_bytes)), block_bytes 1 ..
+ *                       ZMI_BGZF_BLOCK_MAX, n_blocks = ceil(n / block_bytes) (n 0: none, the file is the end-of-file block, as bgzip
+ *                       writes), then the end-of-file block.  *d_out_len = the file's length (the size needed when it does not
+ *                       fit); d_block_off (NULL or n_blocks + 1 entries): the offset of every block, then that of the end-of-file
+ *                       block -- the virtual offset of raw byte u is d_block_off[u / block_bytes] << 16 | u % block_bytes.
+ *   *d_status   0, or an encoder status, or Z_BUF_ERROR (-5) when the result exceeds out_cap: the blocks that end at or before
+ *               out_cap are right then, a block that crosses it (and the end-of-file block, if it does) is not written, nothing at
+ *               or behind d_out + out_cap is.
+ *   Both calls are asynchronous on `stream` and do not synchronise with the host.  Launch groups as in zmi_deflate_stream_dev: a
+ *   group's slots and match scratch stay within the scratch limit, the running offset stays in a device word; the bytes do not
+ *   depend on the grouping.  Event timing: 0 = CRC-32, 1 / 5 / 2 = match search, parse, encode, 7 = sizes, scan, pack and close.
+ *   Scratch of the context: at most 40 bytes per block, and one group's slots of zmi_deflate_bound(max_len, raw) bytes each. */
+#define ZMI_BGZF_BLOCK_MAX 65280u   /* most input bytes per block: htslib's BGZF_BLOCK_SIZE, 0xff00 */
+#define ZMI_BGZF_HEADER 18u
+#define ZMI_BGZF_EOF 28u            /* the empty end-of-file block */
+uint64_t zmi_bgzf_bound(uint64_t n, uint32_t block_bytes);
+int zmi_bgzf_blocks_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_blocks,
+                        uint32_t max_len, int level, int strategy, void* d_out, uint64_t out_cap, uint64_t* d_block_off,
+                        uint32_t* d_block_len, int32_t* d_status, void* stream);
+int zmi_bgzf_deflate_dev(zmi_ctx* ctx, const void* d_in, uint64_t n, uint32_t block_bytes, int level, int strategy, void* d_out,
+                         uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_block_off, int32_t* d_status, void* stream);
+
 /* ---- host-buffer convenience wrappers: copy in, run the batch on the GPU, copy back ---- */
 int zmi_deflate_batch(zmi_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_shards,
                       int level, int strategy, int wrap, uint8_t* out, uint64_t out_stride, uint32_t* out_len,

@@ -66,6 +66,11 @@ def lib():
     # multi-member gzip files: proposals of member starts, then every member decoded in place and verified
     L.zmi_gzip_find_members_dev.argtypes = [vp, vp, u64, vp, u32, vp, vp]
     L.zmi_inflate_members_dev.argtypes = [vp, vp, u64, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp]
+    # writing BGZF: blocked gzip with a block index (csrc/pack.hip, zmi_api.hip)
+    L.zmi_bgzf_bound.restype = u64
+    L.zmi_bgzf_bound.argtypes = [u64, u32]
+    L.zmi_bgzf_blocks_dev.argtypes = [vp, vp, vp, vp, u32, u32, i32, i32, vp, u64, vp, vp, vp, vp]
+    L.zmi_bgzf_deflate_dev.argtypes = [vp, vp, u64, u32, i32, i32, vp, u64, vp, vp, vp, vp]
     # the multi-GPU stitch (csrc/exchange.hip); RCCL itself is loaded by the library on first use
     L.zmi_comm_unique_id.argtypes = [vp]
     L.zmi_comm_create.argtypes = [C.POINTER(vp), vp, i32, i32, vp]

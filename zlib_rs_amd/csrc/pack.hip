@@ -42,21 +42,11 @@ __global__ void __launch_bounds__(1024) zmi_scan_sizes_kernel(const uint32_t* __
     if (t == 1023u) off[n] = b + part[1023];
 }
 
-// n * split jobs: job b handles tiles b % split, b % split + split, ... of range b / split; the grid is the number of jobs, or
-// fewer workgroups that take the jobs in turn (a destination in host memory: see zmi_launch_copy_ranges_few)
-__global__ void __launch_bounds__(PK_T) zmi_copy_ranges_kernel(const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off,
-                                                              uint64_t src_stride, const uint32_t* __restrict__ len,
-                                                              uint8_t* __restrict__ dst, const uint64_t* __restrict__ dst_off,
-                                                              uint64_t dst_cap, uint32_t split, uint32_t jobs) {
-    __shared__ __attribute__((aligned(16))) uint8_t stage[PK_TILE + 32];
-    const uint32_t t = threadIdx.x;
-  for (uint32_t job = blockIdx.x; job < jobs; job += gridDim.x) {
-    const uint32_t r = job / split, part = job % split;
-    const uint32_t l = len[r];
-    const uint64_t so = src_off ? src_off[r] : (uint64_t)r * src_stride;
-    const uint64_t d0 = dst_off[r];
-    if (d0 + l > dst_cap) continue;   // does not fit: the caller sees that from the offsets
-    const uint8_t* s = src + so;
+// Tiles part, part + split, ... of the l bytes at s go to dst + d0, either at any alignment, through the workgroup's stage of
+// PK_TILE + 32 bytes; every thread of the workgroup calls it with the same arguments.  Nothing outside [s, s + l) is read, nothing
+// outside [dst + d0, dst + d0 + l) written.
+static __device__ __forceinline__ void pk_copy_tiles(uint8_t* stage, const uint8_t* s, uint32_t l, uint8_t* dst, uint64_t d0, uint32_t part,
+                                                     uint32_t split, uint32_t t) {
     const uint32_t mis = (uint32_t)((uintptr_t)s & 15u);   // the tile loads start at the 16-byte line at or below s
     for (uint32_t base = part * PK_TILE; base < l; base += split * PK_TILE) {
         const uint32_t nb = l - base < PK_TILE ? l - base : PK_TILE;
@@ -88,6 +78,23 @@ __global__ void __launch_bounds__(PK_T) zmi_copy_ranges_kernel(const uint8_t* __
         }
         __syncthreads();
     }
+}
+
+// n * split jobs: job b handles tiles b % split, b % split + split, ... of range b / split; the grid is the number of jobs, or
+// fewer workgroups that take the jobs in turn (a destination in host memory: see zmi_launch_copy_ranges_few)
+__global__ void __launch_bounds__(PK_T) zmi_copy_ranges_kernel(const uint8_t* __restrict__ src, const uint64_t* __restrict__ src_off,
+                                                              uint64_t src_stride, const uint32_t* __restrict__ len,
+                                                              uint8_t* __restrict__ dst, const uint64_t* __restrict__ dst_off,
+                                                              uint64_t dst_cap, uint32_t split, uint32_t jobs) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[PK_TILE + 32];
+    const uint32_t t = threadIdx.x;
+  for (uint32_t job = blockIdx.x; job < jobs; job += gridDim.x) {
+    const uint32_t r = job / split, part = job % split;
+    const uint32_t l = len[r];
+    const uint64_t so = src_off ? src_off[r] : (uint64_t)r * src_stride;
+    const uint64_t d0 = dst_off[r];
+    if (d0 + l > dst_cap) continue;   // does not fit: the caller sees that from the offsets
+    pk_copy_tiles(stage, src + so, l, dst, d0, part, split, t);
   }
 }
 
@@ -350,5 +357,129 @@ extern "C" int zmi_launch_mm_find(const uint8_t* d_in, uint64_t in_len, uint32_t
     ZMI_LAUNCH(zmi_scan_sizes_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t*)d_cnt, nseg, d_off, (const uint64_t*)nullptr);
     ZMI_LAUNCH(zmi_mm_gather_kernel, dim3(nseg), dim3(MM_T), 0, stream, line0, head, in_len, (const uint32_t*)d_cnt, (const uint64_t*)d_off, nseg,
                d_starts, cap, d_n_starts);
+    return 0;
+}
+
+// ---- BGZF: blocked gzip (zmi_bgzf_blocks_dev, zmi_bgzf_deflate_dev) ---------------------------------------------------------------
+// A block is a gzip member of 18 header bytes (FEXTRA with the one subfield BC, which holds BSIZE = the member's size - 1), a
+// complete raw deflate stream and CRC-32 | ISIZE: the bytes htslib's bgzf.c writes.  The deflate stream is the encoder's slot, or,
+// where that is longer than a stored block of the raw bytes (5 + len), that stored block -- so a member of len <= 65280 raw bytes
+// is at most len + 31 bytes whatever the encoder did, and BSIZE fits its 16 bits.  The sizes kernel chooses, the scan above turns
+// the sizes into offsets, the pack kernel writes every member in one pass: one read and one write of the compressed bytes.
+#define BGZF_HEAD 18u
+#define BGZF_TAIL 8u
+#define BGZF_EOF 28u
+#define BGZF_E_ARG (-103)   // ZMI_E_ARG (include/zmi355.h), in the call's status word
+
+// header byte k < 16: 1f 8b 08 04 | MTIME 0 | XFL 0 | OS ff | XLEN 6 | 'B' 'C' 2 0
+static __device__ __forceinline__ uint8_t bgzf_fixed(uint32_t k) {
+    const uint64_t w = k < 8u ? 0x0000000004088B1Full : 0x000243420006FF00ull;
+    return (uint8_t)(w >> (8u * (k & 7u)));
+}
+
+// the batch call's length table lives on the device: a shard above max_len becomes an empty one (the scratch is sized by max_len)
+// and the call's status ZMI_E_ARG
+__global__ void __launch_bounds__(256) zmi_bgzf_lens_kernel(const uint32_t* __restrict__ len, uint32_t n, uint32_t max_len,
+                                                            uint32_t* __restrict__ clen, int32_t* status) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t l = len[i];
+    clen[i] = l > max_len ? 0u : l;
+    if (l > max_len) atomicCAS(status, 0, BGZF_E_ARG);
+}
+
+// framed[i] = min(olen[i], len[i] + 5) + 26, stored[i] = the stored block was chosen (also behind an encoder status, which lands
+// in *status: whatever the slot holds then is not read)
+__global__ void __launch_bounds__(256) zmi_bgzf_sizes_kernel(const uint32_t* __restrict__ len, const uint32_t* __restrict__ olen,
+                                                             const int32_t* __restrict__ st, uint32_t n, uint32_t* __restrict__ framed,
+                                                             uint32_t* __restrict__ stored, int32_t* status) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t l = len[i], e = olen[i];
+    const int32_t s = st[i];
+    const bool sb = s != 0 || e > l + 5u;
+    framed[i] = (sb ? l + 5u : e) + BGZF_HEAD + BGZF_TAIL;
+    stored[i] = sb ? 1u : 0u;
+    if (s != 0) atomicCAS(status, 0, s);
+}
+
+// n * split jobs as in zmi_copy_ranges_kernel: job b copies tiles b % split, ... of block b / split's payload -- from its slot, or
+// from the raw input behind the five bytes of a stored block -- and part 0 also writes the 18 + 8 (+ 5) bytes around it, one byte
+// per thread.  A block that crosses out_cap is not written at all.
+__global__ void __launch_bounds__(PK_T) zmi_bgzf_pack_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+                                                             const uint32_t* __restrict__ len, const uint8_t* __restrict__ slots,
+                                                             uint64_t slot_stride, const uint32_t* __restrict__ olen,
+                                                             const uint32_t* __restrict__ stored, const uint32_t* __restrict__ crc,
+                                                             uint8_t* __restrict__ out, const uint64_t* __restrict__ boff, uint64_t out_cap,
+                                                             uint32_t split, uint32_t jobs) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[PK_TILE + 32];
+    const uint32_t t = threadIdx.x;
+  for (uint32_t job = blockIdx.x; job < jobs; job += gridDim.x) {
+    const uint32_t r = job / split, part = job % split;
+    const uint32_t l = len[r];
+    const bool sb = stored[r] != 0u;
+    const uint32_t pl = sb ? l + 5u : olen[r];
+    const uint32_t total = BGZF_HEAD + pl + BGZF_TAIL;
+    const uint64_t d0 = boff[r];
+    if (d0 + total > out_cap) continue;   // does not fit: the call's status says so
+    uint8_t* B = out + d0;
+    if (part == 0u) {
+        if (t < 16u) B[t] = bgzf_fixed(t);
+        else if (t < BGZF_HEAD) B[t] = (uint8_t)((total - 1u) >> (8u * (t - 16u)));
+        else if (t < BGZF_HEAD + BGZF_TAIL) {
+            const uint32_t k = t - BGZF_HEAD;
+            B[BGZF_HEAD + pl + k] = (uint8_t)((k < 4u ? crc[r] : l) >> (8u * (k & 3u)));
+        } else if (sb && t < BGZF_HEAD + BGZF_TAIL + 5u) {
+            const uint32_t k = t - (BGZF_HEAD + BGZF_TAIL);   // 01 | LEN | ~LEN
+            B[BGZF_HEAD + k] = k == 0u ? (uint8_t)1u : (uint8_t)((k < 3u ? l : ~l) >> (8u * ((k - 1u) & 1u)));
+        }
+    }
+    if (sb) pk_copy_tiles(stage, in + in_off[r], l, out, d0 + BGZF_HEAD + 5u, part, split, t);
+    else pk_copy_tiles(stage, slots + (uint64_t)r * slot_stride, pl, out, d0 + BGZF_HEAD, part, split, t);
+  }
+}
+
+// one thread: the total behind the last block (+ the end-of-file block), the status of a result that does not fit, and the
+// end-of-file block itself: an empty member, 1f 8b 08 04 ... 42 43 02 00 | 1b 00 | 03 00 | CRC 0 | ISIZE 0
+__global__ void zmi_bgzf_close_kernel(uint8_t* __restrict__ out, uint64_t out_cap, const uint64_t* __restrict__ blocks_end, uint32_t eof,
+                                      uint64_t* __restrict__ out_len, int32_t* status) {
+    const uint64_t at = *blocks_end;
+    const uint64_t total = at + (eof ? BGZF_EOF : 0u);
+    if (out_len) *out_len = total;
+    if (total > out_cap) { atomicCAS(status, 0, ZMI_BUF_ERROR); return; }
+    if (!eof) return;
+    uint8_t* B = out + at;
+    for (uint32_t k = 0; k < 16u; ++k) B[k] = bgzf_fixed(k);
+    B[16] = (uint8_t)(BGZF_EOF - 1u);
+    B[17] = 0;
+    B[18] = 3;
+    for (uint32_t k = 19u; k < BGZF_EOF; ++k) B[k] = 0;
+}
+
+extern "C" int zmi_launch_bgzf_lens(const uint32_t* d_len, uint32_t n, uint32_t max_len, uint32_t* d_clen, int32_t* d_status, hipStream_t stream) {
+    if (n == 0) return 0;
+    ZMI_LAUNCH(zmi_bgzf_lens_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_len, n, max_len, d_clen, d_status);
+    return 0;
+}
+extern "C" int zmi_launch_bgzf_sizes(const uint32_t* d_len, const uint32_t* d_olen, const int32_t* d_st, uint32_t n, uint32_t* d_framed,
+                                     uint32_t* d_stored, int32_t* d_status, hipStream_t stream) {
+    if (n == 0) return 0;
+    ZMI_LAUNCH(zmi_bgzf_sizes_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_len, d_olen, d_st, n, d_framed, d_stored, d_status);
+    return 0;
+}
+extern "C" int zmi_launch_bgzf_pack(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_len, const uint8_t* d_slots,
+                                    uint64_t slot_stride, const uint32_t* d_olen, const uint32_t* d_stored, const uint32_t* d_crc, uint32_t n,
+                                    uint32_t max_len, uint8_t* d_out, const uint64_t* d_boff, uint64_t out_cap, hipStream_t stream) {
+    if (n == 0) return 0;
+    uint32_t split = 1;
+    const uint32_t tiles = (max_len + 5u + PK_TILE - 1u) / PK_TILE;
+    while ((uint64_t)n * split < 4096u && split < tiles) split <<= 1;
+    ZMI_LAUNCH(zmi_bgzf_pack_kernel, dim3(n * split), dim3(PK_T), 0, stream, d_in, d_in_off, d_len, d_slots, slot_stride, d_olen, d_stored,
+               d_crc, d_out, d_boff, out_cap, split, n * split);
+    return 0;
+}
+extern "C" int zmi_launch_bgzf_close(uint8_t* d_out, uint64_t out_cap, const uint64_t* d_blocks_end, uint32_t eof, uint64_t* d_out_len,
+                                     int32_t* d_status, hipStream_t stream) {
+    ZMI_LAUNCH(zmi_bgzf_close_kernel, dim3(1), dim3(1), 0, stream, d_out, out_cap, d_blocks_end, eof, d_out_len, d_status);
     return 0;
 }

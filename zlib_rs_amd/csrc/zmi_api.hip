@@ -109,7 +109,7 @@ struct zmi_ctx {
     hipStream_t host_stream = nullptr;  // zmi_ctx_set_stream: where the host-buffer wrappers copy and launch
     hipStream_t side = nullptr;         // deflate: the wrapper checksums run here, beside the match search (zmi_deflate_impl)
     hipEvent_t ev_fork{}, ev_join{};
-    zmi_buf sd_meta, sd_slots;          // zmi_deflate_stream_dev: per-piece tables / one launch group's output slots
+    zmi_buf sd_meta, sd_slots;          // zmi_deflate_stream_dev, the BGZF calls: per-piece tables / one launch group's output slots
     zmi_buf comb;                       // zmi_checksum_combine_dev: the per-workgroup partial folds
     zmi_buf si_meta, si_work, si_seg;   // zmi_inflate_stream_dev: per-piece tables / one launch group's regions; find_cuts' segment table
     zmi_buf si_scan;                    // zmi_stream_find_blocks_dev: one window's survivor slots and validated list
@@ -860,6 +860,128 @@ extern "C" int zmi_deflate_stream_dev(zmi_ctx* c, const void* d_in, uint64_t n, 
         zmi_scope_timer tm(c, ZMI_K_PACK, stream);
         zmi_launch_frame((uint8_t*)d_out, out_cap, (uint32_t)wrap, (uint32_t)level, (uint32_t)strategy, d_poff + np, d_comb, d_raw, d_out_len,
                          d_status, d_st, np, d_piece_off, d_piece_off ? np + 1u : 0u, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+// ---- BGZF: blocked gzip with a block index (include/zmi355.h; the kernels: pack.hip) ---------------------------------------------
+// Every block is one shard of the batch encoder (chain mode 0, raw, one piece: max_len <= 65280 < block_span), framed by the pack
+// kernel with htslib's header; the launch groups, the device-resident running offset and the ZMI_STREAM_GROUP knob are
+// zmi_deflate_stream_dev's.
+extern "C" uint64_t zmi_bgzf_bound(uint64_t n, uint32_t block_bytes) {
+    if (block_bytes == 0) return 0;
+    const uint64_t nb = n / block_bytes + (n % block_bytes ? 1u : 0u);
+    return n + nb * (ZMI_BGZF_HEADER + 5u + 8u) + ZMI_BGZF_EOF;
+}
+
+// Blocks d_len[0 .. n) (every length <= max_len <= ZMI_BGZF_BLOCK_MAX: the callers saw to that) framed and packed into d_out from
+// *d_boff on, which the caller zeroed; d_boff[1 .. n] and d_blen[0 .. n) are written.  d_tab: four u32[n] tables (the encoder's
+// sizes and statuses, the CRC-32 values, the stored flags).  The first non-zero encoder status lands in *d_status.
+static int zmi_bgzf_body(zmi_ctx* c, const void* d_in, const uint64_t* d_off, const uint32_t* d_len, uint32_t n, uint32_t max_len, int level,
+                         int strategy, void* d_out, uint64_t out_cap, uint64_t* d_boff, uint32_t* d_blen, uint32_t* d_tab, int32_t* d_status,
+                         hipStream_t stream) {
+    if (n == 0) return ZMI_E_OK;
+    uint32_t* d_olen = d_tab;
+    int32_t* d_st = (int32_t*)(d_tab + n);
+    uint32_t* d_crc = d_tab + 2u * (size_t)n;
+    uint32_t* d_stored = d_tab + 3u * (size_t)n;
+    // launch groups: one group's output slots and the encoder's match scratch together stay within the scratch limit
+    const uint64_t stride = zmi_deflate_bound(max_len, ZMI_WRAP_RAW);
+    const uint64_t match_per = ((((uint64_t)max_len + 63u) & ~63ull) ? (((uint64_t)max_len + 63u) & ~63ull) : 64u) * 4u;
+    uint64_t group = c->scratch_limit / (stride + match_per + match_per / 16u);
+    if (const char* gv = zmi_tune("ZMI_STREAM_GROUP")) if (atoll(gv) > 0) group = (uint64_t)atoll(gv);
+    if (group == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one block");
+    if (group > n) group = n;
+    int rc = zmi_reserve(c->sd_slots, (size_t)(group * stride));
+    if (rc) return rc;
+    rc = zmi_piece_checks(c, d_in, d_off, d_len, n, ZMI_WRAP_GZIP, d_crc, stream);
+    if (rc) return rc;
+    for (uint64_t first = 0; first < n; first += group) {
+        const uint32_t cnt = (uint32_t)(n - first < group ? n - first : group);
+        rc = zmi_deflate_impl(c, d_in, d_off + first, d_len + first, cnt, max_len, level, strategy, ZMI_WRAP_RAW, 0u, 0u, 15u, c->sd_slots.p,
+                              stride, d_olen + first, d_st + first, stream);
+        if (rc) return rc;
+        // the group's blocks go behind the previous group's, the running offset never leaves the device
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_bgzf_sizes(d_len + first, d_olen + first, d_st + first, cnt, d_blen + first, d_stored + first, d_status, stream);
+        zmi_launch_scan_sizes_base(d_blen + first, cnt, d_boff + first, d_boff + first, stream);
+        zmi_launch_bgzf_pack((const uint8_t*)d_in, d_off + first, d_len + first, (const uint8_t*)c->sd_slots.p, stride, d_olen + first,
+                             d_stored + first, d_crc + first, cnt, max_len, (uint8_t*)d_out, d_boff + first, out_cap, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+static int zmi_bgzf_check_args(int& level, int strategy) {
+    if (level == -1) level = 6;
+    if (level < 0 || level > 9) return zmi_fail(ZMI_E_ARG, "level must be -1..9");
+    if (strategy < 0 || strategy > 4) return zmi_fail(ZMI_E_ARG, "strategy must be 0..4");
+    return ZMI_E_OK;
+}
+
+extern "C" int zmi_bgzf_blocks_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
+                                   uint32_t max_len, int level, int strategy, void* d_out, uint64_t out_cap, uint64_t* d_block_off,
+                                   uint32_t* d_block_len, int32_t* d_status, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (max_len > ZMI_BGZF_BLOCK_MAX) return zmi_fail(ZMI_E_ARG, "zmi_bgzf_blocks_dev: max_len must be <= ZMI_BGZF_BLOCK_MAX");
+    int rc = zmi_bgzf_check_args(level, strategy);
+    if (rc) return rc;
+    if (!d_block_off || !d_status || (out_cap && !d_out) || (n && (!d_in_off || !d_in_len || (max_len && !d_in))))
+        return zmi_fail(ZMI_E_ARG, "null argument");
+    if (n > 0x7FFFFFFFu) return zmi_fail(ZMI_E_ARG, "zmi_bgzf_blocks_dev: more than 2^31 - 1 blocks");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    // per-block tables: checked lengths u32 | block sizes u32 (unless the caller's table holds them) | the body's four
+    rc = zmi_reserve(c->sd_meta, (size_t)n * (d_block_len ? 20u : 24u) + 16u);
+    if (rc) return rc;
+    uint32_t* d_len = (uint32_t*)c->sd_meta.p;
+    uint32_t* d_blen = d_block_len ? d_block_len : d_len + n;
+    uint32_t* d_tab = d_len + (size_t)n * (d_block_len ? 1u : 2u);
+    ZMI_HIP(hipMemsetAsync(d_status, 0, 4, stream));
+    ZMI_HIP(hipMemsetAsync(d_block_off, 0, 8, stream));
+    zmi_launch_bgzf_lens(d_in_len, n, max_len, d_len, d_status, stream);
+    rc = zmi_bgzf_body(c, d_in, d_in_off, d_len, n, max_len, level, strategy, d_out, out_cap, d_block_off, d_blen, d_tab, d_status, stream);
+    if (rc) return rc;
+    {
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_bgzf_close((uint8_t*)d_out, out_cap, d_block_off + n, 0u, nullptr, d_status, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+extern "C" int zmi_bgzf_deflate_dev(zmi_ctx* c, const void* d_in, uint64_t n, uint32_t block_bytes, int level, int strategy, void* d_out,
+                                    uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_block_off, int32_t* d_status, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (block_bytes == 0 || block_bytes > ZMI_BGZF_BLOCK_MAX) return zmi_fail(ZMI_E_ARG, "zmi_bgzf_deflate_dev: block_bytes must be 1 .. ZMI_BGZF_BLOCK_MAX");
+    int rc = zmi_bgzf_check_args(level, strategy);
+    if (rc) return rc;
+    if ((n && !d_in) || (out_cap && !d_out) || !d_out_len || !d_status) return zmi_fail(ZMI_E_ARG, "null argument");
+    const uint64_t nb64 = n / block_bytes + (n % block_bytes ? 1u : 0u);
+    if (nb64 > 0x7FFFFFFFull) return zmi_fail(ZMI_E_ARG, "zmi_bgzf_deflate_dev: more than 2^31 - 1 blocks");
+    const uint32_t nb = (uint32_t)nb64;
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    // per-block tables: in_off u64 | block offsets u64 [nb + 1] (unless the caller's index holds them) | in_len u32 | block sizes
+    // u32 | the body's four
+    const size_t own_off = d_block_off ? 0u : ((size_t)nb + 1u) * 8u;
+    rc = zmi_reserve(c->sd_meta, (size_t)nb * 8u + own_off + (size_t)nb * 24u + 16u);
+    if (rc) return rc;
+    uint64_t* d_off = (uint64_t*)c->sd_meta.p;
+    uint64_t* d_boff = d_block_off ? d_block_off : d_off + nb;
+    uint32_t* d_len = (uint32_t*)((uint8_t*)c->sd_meta.p + (size_t)nb * 8u + own_off);
+    uint32_t* d_blen = d_len + nb;
+    uint32_t* d_tab = d_blen + nb;
+    ZMI_HIP(hipMemsetAsync(d_status, 0, 4, stream));
+    ZMI_HIP(hipMemsetAsync(d_boff, 0, 8, stream));   // where the first group's pack starts
+    zmi_launch_piece_layout(n, block_bytes, nb, d_off, d_len, stream);
+    const uint32_t max_len = n < block_bytes ? (uint32_t)n : block_bytes;
+    rc = zmi_bgzf_body(c, d_in, d_off, d_len, nb, max_len, level, strategy, d_out, out_cap, d_boff, d_blen, d_tab, d_status, stream);
+    if (rc) return rc;
+    {
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_bgzf_close((uint8_t*)d_out, out_cap, d_boff + nb, 1u, d_out_len, d_status, stream);
     }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;

@@ -189,6 +189,17 @@ uint32_t zmi_block_scan_look(void);
 int zmi_launch_block_scan_window(const uint8_t* d_win, uint32_t n_vis, uint64_t base_bit, uint32_t own_bits, const uint32_t* d_hdr,
                                  uint32_t* d_slots, uint32_t* d_cnt, uint32_t* d_vcnt, uint64_t* d_voff, uint32_t* d_vlist, uint32_t vcap,
                                  uint64_t gap_bits, uint32_t first, uint64_t* d_cuts, uint32_t cap, uint32_t* d_n_cuts, hipStream_t stream);
+// BGZF (pack.hip): the batch call's length check, the framed sizes with the choice between the encoder's slot and a stored block,
+// the members written in one pass (n blocks of one launch group: slot i at d_slots + i * slot_stride), the closing step (total,
+// Z_BUF_ERROR, the end-of-file block)
+int zmi_launch_bgzf_lens(const uint32_t* d_len, uint32_t n, uint32_t max_len, uint32_t* d_clen, int32_t* d_status, hipStream_t stream);
+int zmi_launch_bgzf_sizes(const uint32_t* d_len, const uint32_t* d_olen, const int32_t* d_st, uint32_t n, uint32_t* d_framed,
+                          uint32_t* d_stored, int32_t* d_status, hipStream_t stream);
+int zmi_launch_bgzf_pack(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_len, const uint8_t* d_slots,
+                         uint64_t slot_stride, const uint32_t* d_olen, const uint32_t* d_stored, const uint32_t* d_crc, uint32_t n,
+                         uint32_t max_len, uint8_t* d_out, const uint64_t* d_boff, uint64_t out_cap, hipStream_t stream);
+int zmi_launch_bgzf_close(uint8_t* d_out, uint64_t out_cap, const uint64_t* d_blocks_end, uint32_t eof, uint64_t* d_out_len,
+                          int32_t* d_status, hipStream_t stream);
 // multi-member gzip files: proposals of member starts (pack.hip: count, scan, gather) and the plan / verify / repair steps of
 // zmi_inflate_members_dev (inflate.hip).  d_tab: eight u32[n] tables, d_off: u64[n + 1], d_w: sixteen words
 uint32_t zmi_mm_scan_segments(uint64_t in_len, uint32_t head);

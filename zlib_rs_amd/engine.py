@@ -16,6 +16,7 @@ WRAP_RAW, WRAP_ZLIB, WRAP_GZIP, WRAP_AUTO = 0, 1, 2, 3
 GEN_SEED = 0x5A4C4942
 # zmi_inflate_stream_dev detail kinds (include/zmi355.h ZMI_SI_*)
 SI_CUT, SI_PIECE, SI_OUT = 3, 4, 9
+BGZF_BLOCK_MAX, BGZF_HEADER, BGZF_EOF = 65280, 18, 28   # ZMI_BGZF_* (include/zmi355.h)
 MM_HEADER, MM_TRUNC, MM_DATA, MM_CHECK, MM_LENGTH, MM_OUT, MM_BIG, MM_AGAIN = 1, 2, 3, 4, 5, 6, 7, 8   # ZMI_MM_* (include/zmi355.h)
 
 
@@ -65,6 +66,74 @@ class StreamIndex:
         out = torch.arange(pieces + 1, dtype=torch.int64, device=piece_off.device) * int(piece_bytes)
         out[pieces] = int(n)
         return cls(bit, out, None, min(int(piece_bytes), int(n)))
+
+
+class BgzfIndex:
+    """The block index of a BGZF file written by Engine.bgzf_compress: block_off int64 [n_blocks + 1] (device tensor: the file offset
+    of every block, then that of the end-of-file block), block_bytes (raw bytes per block, the last one may be shorter) and n, the
+    length of the raw data."""
+
+    def __init__(self, block_off, block_bytes, n):
+        self.block_off, self.block_bytes, self.n = block_off, int(block_bytes), int(n)
+        self._host = None
+
+    @property
+    def n_blocks(self):
+        return int(self.block_off.numel()) - 1
+
+    def _offsets(self):
+        if self._host is None:
+            self._host = self.block_off.tolist()
+        return self._host
+
+    def stream_index(self):
+        """the window-less StreamIndex of the file: a point at the first deflate byte of every block (18 bytes behind its start)"""
+        nb = self.n_blocks
+        bit = (self.block_off[:nb].to(torch.int64) + BGZF_HEADER) * 8
+        out = torch.arange(nb + 1, dtype=torch.int64, device=self.block_off.device) * self.block_bytes
+        out[nb] = self.n
+        return StreamIndex(bit, out, None, min(self.block_bytes, self.n))
+
+    def virtual_offset(self, u):
+        """htslib's virtual file offset of raw byte u: the block's file offset << 16 | the offset inside the block"""
+        return self._offsets()[int(u) // self.block_bytes] << 16 | int(u) % self.block_bytes
+
+    def save_gzi(self, path):
+        """htslib's .gzi: a little-endian u64 count, then (compressed offset, uncompressed offset) u64 pairs of blocks 1 .. n_blocks - 1"""
+        import struct
+        off = self._offsets()
+        pairs = [(off[i], i * self.block_bytes) for i in range(1, self.n_blocks)]
+        with open(path, "wb") as f:
+            f.write(struct.pack("<Q", len(pairs)) + b"".join(struct.pack("<QQ", c, u) for c, u in pairs))
+
+    @classmethod
+    def load_gzi(cls, path, file_bytes, device, block_bytes=None):
+        """file_bytes: the BGZF file the table belongs to (bytes or a uint8 tensor): its length gives the end-of-file block's offset,
+        the ISIZE word in front of that block the length of the last block.  block_bytes is read from the first pair; a file of 0 or
+        1 blocks has none, there the caller passes it."""
+        import struct
+        with open(path, "rb") as f:
+            raw = f.read()
+        count = struct.unpack_from("<Q", raw, 0)[0]
+        if len(raw) != 8 + 16 * count:
+            raise ValueError("%s: not a .gzi table (%d bytes for %d entries)" % (path, len(raw), count))
+        words = struct.unpack_from("<%dQ" % (2 * count), raw, 8)
+        size = int(file_bytes.numel()) if torch.is_tensor(file_bytes) else len(file_bytes)
+        if size < BGZF_EOF:
+            raise ValueError("a BGZF file is at least its %d-byte end-of-file block" % BGZF_EOF)
+        if count:
+            block_bytes = words[1]
+        elif block_bytes is None:
+            raise ValueError("a table without entries does not tell block_bytes: pass it")
+        off = [0] + list(words[0::2]) + [size - BGZF_EOF]
+        n = 0
+        if size > BGZF_EOF:
+            tail = file_bytes[size - BGZF_EOF - 4:size - BGZF_EOF]
+            isize = struct.unpack("<I", bytes(tail.tolist()) if torch.is_tensor(tail) else bytes(tail))[0]
+            n = count * int(block_bytes) + isize
+        else:
+            off = [0]
+        return cls(torch.tensor(off, dtype=torch.int64, device=torch.device(device)), block_bytes, n)
 
 
 class Engine:
@@ -232,6 +301,85 @@ class Engine:
         if status != 0:
             raise RuntimeError("zmi_deflate_stream_dev: status %d (stream of %d bytes, room for %d)" % (status, length, out.numel()))
         return (out[:length], idx) if index else out[:length]
+
+    # ---- BGZF: blocked gzip with a block index (include/zmi355.h) ----
+    def bgzf_bound(self, n, block_bytes=BGZF_BLOCK_MAX):
+        return int(self.L.zmi_bgzf_bound(int(n), int(block_bytes)))
+
+    def bgzf_compress(self, data, level=6, strategy=0, block_bytes=BGZF_BLOCK_MAX, index=False, out=None):
+        """data: uint8 device tensor -> a uint8 view of exactly the BGZF file: blocks of block_bytes raw bytes, then the end-of-file
+        block (and, with index=True, its BgzfIndex).  One synchronisation, for the length; a non-zero status raises."""
+        n = int(data.numel())
+        n_blocks = -(-n // int(block_bytes)) if 0 < int(block_bytes) <= BGZF_BLOCK_MAX else 0
+        if out is None:
+            out = torch.empty(self.bgzf_bound(n, block_bytes), dtype=torch.uint8, device=self.device)
+        meta = torch.zeros(2, dtype=torch.int64, device=self.device)     # length | status (int32)
+        idx = torch.empty(n_blocks + 1, dtype=torch.int64, device=self.device) if index else None
+        _lib.check(self.L.zmi_bgzf_deflate_dev(self._ctx, data.data_ptr() if n else None, n, int(block_bytes), int(level), int(strategy),
+                                               out.data_ptr() if out.numel() else None, int(out.numel()), meta.data_ptr(),
+                                               idx.data_ptr() if index else None, meta.data_ptr() + 8, _stream_ptr()), "zmi_bgzf_deflate_dev")
+        length, status = _len_status(meta)
+        if status != 0:
+            raise RuntimeError("zmi_bgzf_deflate_dev: status %d (file of %d bytes, room for %d)" % (status, length, out.numel()))
+        return (out[:length], BgzfIndex(idx, block_bytes, n)) if index else out[:length]
+
+    def bgzf_blocks(self, data, offsets, lengths, max_len, level=6, strategy=0, out=None):
+        """The shards data[offsets[i] : + lengths[i]] (every length <= max_len <= 65280) as BGZF blocks, no end-of-file block: one
+        rank's slab of a file.  Returns (slab: a uint8 view of exactly the blocks, block_off int64 [n + 1], block_len int32 [n]: the
+        table exchange_sizes takes).  One synchronisation, for the total and the status; a non-zero status raises."""
+        n = int(lengths.numel())
+        if out is None:
+            out = torch.empty(n * (int(max_len) + 31) + 16, dtype=torch.uint8, device=self.device)
+        meta = torch.zeros(n + 2, dtype=torch.int64, device=self.device)   # block_off [n + 1] | status (int32)
+        block_len = torch.zeros(n, dtype=torch.int32, device=self.device)
+        _lib.check(self.L.zmi_bgzf_blocks_dev(self._ctx, data.data_ptr() if data.numel() else None, offsets.data_ptr() if n else None,
+                                              lengths.data_ptr() if n else None, n, int(max_len), int(level), int(strategy),
+                                              out.data_ptr() if out.numel() else None, int(out.numel()), meta.data_ptr(),
+                                              block_len.data_ptr() if n else None, meta.data_ptr() + 8 * (n + 1), _stream_ptr()),
+                   "zmi_bgzf_blocks_dev")
+        total, status = _len_status(meta[n:])
+        if status != 0:
+            raise RuntimeError("zmi_bgzf_blocks_dev: status %d (%d blocks, %d bytes, room for %d)" % (status, n, total, out.numel()))
+        return out[:total], meta[:n + 1], block_len
+
+    def bgzf_read_ranges(self, file, index, lo, lengths, out=None):
+        """Byte ranges [lo[i], lo[i] + lengths[i]) of the raw data of the BGZF file `file` (uint8 device tensor) through its BgzfIndex
+        -> (out [n, width] uint8, got int32 [n], status int32 [n]); lo and lengths are lists, numpy arrays or tensors.  A range may
+        cross any number of blocks: the host splits it at the multiples of block_bytes and ONE zmi_inflate_ranges_dev call reads every
+        part to its place in row i of `out` (allocated here with width = the greatest length).  A range that runs past the end of the
+        data is cut there (got[i]); status[i] is 0 or the status of its first failing part."""
+        import numpy as np
+        to_np = lambda x: x.cpu().numpy() if torch.is_tensor(x) else np.asarray(list(x))
+        lo_h = to_np(lo).astype(np.int64).reshape(-1)
+        ln_h = to_np(lengths).astype(np.int64).reshape(-1)
+        r = int(lo_h.size)
+        bb, n = index.block_bytes, index.n
+        if out is None:
+            out = torch.empty((r, max(1, int(ln_h.max()) if r else 1)), dtype=torch.uint8, device=self.device)
+        width = int(out.stride(0)) if out.dim() == 2 else (int(out.numel()) // r if r else 0)
+        if r and int(ln_h.max()) > width:
+            raise ValueError("a range of %d bytes does not fit a row of %d" % (int(ln_h.max()), width))
+        got = torch.zeros(r, dtype=torch.int32, device=self.device)
+        status = torch.zeros(r, dtype=torch.int32, device=self.device)
+        a = np.minimum(np.maximum(lo_h, 0), n)
+        b = np.minimum(a + np.maximum(ln_h, 0), n)
+        first = a // bb
+        cnt = np.where(b > a, (b - 1) // bb - first + 1, 0)
+        parts = int(cnt.sum())
+        if parts == 0:
+            return out, got, status
+        rid = np.repeat(np.arange(r, dtype=np.int64), cnt)
+        blk = first[rid] + np.arange(parts, dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+        p_lo = np.maximum(a[rid], blk * bb)
+        p_len = np.minimum(b[rid], (blk + 1) * bb) - p_lo
+        p_off = rid * width + (p_lo - a[rid])
+        dev = lambda x, dt: torch.from_numpy(np.ascontiguousarray(x)).to(dtype=dt, device=self.device)
+        rid_d = dev(rid, torch.int64)
+        _, p_got, p_st = self.read_ranges(file, index.stream_index(), dev(p_lo, torch.int64), dev(p_len, torch.int32), out=out,
+                                          out_offsets=dev(p_off, torch.int64), max_len=int(p_len.max()))
+        got.index_add_(0, rid_d, p_got)
+        status.scatter_reduce_(0, rid_d, p_st, "amin")   # (statuses are 0 or negative)
+        return out, got, status
 
     def find_cuts(self, data, wrap=WRAP_AUTO, min_gap=1 << 16, cap=None):
         """Proposed piece starts of a stream with flush points (the end of the header, then the byte behind every byte-aligned

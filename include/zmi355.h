@@ -593,6 +593,101 @@ int zmi_bgzf_blocks_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off
 int zmi_bgzf_deflate_dev(zmi_ctx* ctx, const void* d_in, uint64_t n, uint32_t block_bytes, int level, int strategy, void* d_out,
                          uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_block_off, int32_t* d_status, void* stream);
 
+/* ---- reading ZIP archives (.zip, .npz, .whl / .jar / .docx / .xlsx): the directory, a batch inflate of entries, the CRC check --------
+ * A ZIP is a batch of independent raw-deflate (method 8) or stored (method 0) streams; the size table and the CRC-32s stand in the
+ * central directory at its end -- the input shape of zmi_inflate_batch_dev_ex, which checks nothing on a raw stream.  Two calls, both
+ * asynchronous on `stream`, neither synchronises with the host, every result is a device word.  Positions are 64-bit, d_in may stand at
+ * any alignment.  Not read: encrypted entries, methods other than 0 and 8, multi-disk archives, entries of 4 GiB or more (the batch
+ * decoder's lengths are uint32_t) -- they are listed and flagged.
+ *
+ * zmi_zip_directory_dev   d_in[0 .. in_len) is the whole file.
+ *   End record  the HIGHEST offset p in [max(0, in_len - 65557), in_len - 22] with in[p .. p + 4) = 50 4b 05 06 AND
+ *               p + 22 + comment_len == in_len.  Stricter than Python's zipfile, which takes the last signature: an end record spelled
+ *               inside the archive comment does not fool this one.  Bytes behind the archive are ZMI_ZA_NOEOCD, as is in_len < 22.
+ *   ZIP64       where the 20-byte locator 50 4b 06 07 stands at p - 20, the 56-byte record 50 4b 06 06 at p - 76 gives count, size and
+ *               offset (zipfile and Info-ZIP write the locator whenever a count field is 0xFFFF or the size or offset field
+ *               0xFFFFFFFF; without a locator such fields are taken as they stand -- 65 535 entries is a valid plain archive).  A
+ *               locator without that record in front of it, or a version-2 record with an extensible data sector (record size
+ *               field != 44), is ZMI_ZA_ZIP64.
+ *   Base        base = (start of the end structure: p, or p - 76) - cd_size - cd_off, the number of bytes that stand in front of the
+ *               archive (a self-extractor, a concatenated prefix); it is added to every local-header offset.  A negative base is
+ *               ZMI_ZA_BOUNDS; the directory ends exactly where the end structure begins by construction.
+ *   Disks       a non-zero disk number anywhere (end record, ZIP64 record, locator, an entry's disk field; a locator that counts more
+ *               than one disk) is ZMI_ZA_MULTIDISK.
+ *   The chain   the bytes [base + cd_off, + cd_size): entry k starts where entry k - 1 ended, begins with 50 4b 01 02 and occupies
+ *               46 + name + extra + comment bytes; the chain must end exactly at the directory's end, otherwise ZMI_ZA_CHAIN with the
+ *               index of the first bad entry above the low 8 bits of detail.  n_entries = the entries walked (the good ones in front
+ *               of a break); it must equal the end structure's count -- modulo 65 536 for the 16-bit field, exactly for the ZIP64
+ *               record -- otherwise ZMI_ZA_COUNT.  n_listed = min(n_entries, cap): more entries than cap is no error, the first cap
+ *               are listed and n_entries tells the rest (reading d_info is the caller's one synchronisation).
+ *   Per entry   the fixed fields; the ZIP64 extra (id 0x0001), whose 8-byte values stand only for those of usize, csize and
+ *               local-header offset -- in that order -- whose 32-bit field is 0xFFFFFFFF; then the local header at base + offset:
+ *               data_off comes from the LOCAL name and extra lengths (they differ from the central ones: zipfile's force_zip64 writes
+ *               a 20-byte local extra and no central one), sizes and CRC-32 always from the directory (general-purpose bit 3, the
+ *               data descriptor, leaves zeros in the local header).  A flagged entry is still listed, with its name.
+ *   d_info->status   0; Z_DATA_ERROR (-3) for NOEOCD / BOUNDS / CHAIN / COUNT / ZIP64; Z_VERSION_ERROR (-6) for MULTIDISK; detail = the
+ *               ZMI_ZA_* case in its low 8 bits.  The 22-byte empty archive has status 0 and no entries.  With a status from the end
+ *               record (all but CHAIN / COUNT and an entry's disk field) nothing is walked: n_entries = n_listed = 0.
+ *   Scratch of the context: 8 bytes per entry of cap and 32 bytes per 16 KiB of in_len.  cap 0 (d_entries may be NULL) counts the entries.
+ *
+ * zmi_zip_inflate_dev     slot j reads entry d_sel[j] of the table d_entries[0 .. n_entries) (d_sel NULL: slot j = entry j); duplicates
+ *               are allowed; an index >= n_entries -- the table lives on the device -- and an entry whose data leaves d_in or whose
+ *               method and sizes no directory call would pass (a table not made from this buffer) get ZMI_E_ARG in the slot's status.
+ *   Plan        d_out_off[j] = the sum of the usize of the readable slots in front, each rounded up to out_align (a power of two,
+ *               1 .. 4096, otherwise ZMI_E_ARG); d_out_off[n_sel] = the room the selection needs, exact whether or not it fitted:
+ *               the plan of zmi_inflate_batch_packed_dev fed from the directory instead of the size pass, and its rules for out_cap:
+ *               slots that end at or before out_cap are decoded and right, the others report Z_BUF_ERROR / ZMI_ZE_OUT, nothing at or
+ *               behind d_out + out_cap and nothing in the alignment gaps is written, a bitmap that cannot be reserved is ZMI_E_NOMEM.
+ *   Reading     deflated slots go through the batch decoder with ZMI_WRAP_RAW and capacity usize, stored slots through the range
+ *               copy; the CRC-32 kernel runs over every region; one verify kernel writes the slot's words:
+ *   d_status / d_detail   0 / 0                       length and CRC-32 both match
+ *               Z_DATA_ERROR / ZMI_ZE_DATA            a corrupt block
+ *               Z_DATA_ERROR / ZMI_ZE_LENGTH          the decoded length is not usize, or the deflate stream does not end at byte csize
+ *                                                     exactly (it wants more input, or ends early)
+ *               Z_DATA_ERROR / ZMI_ZE_CHECK           CRC-32 mismatch
+ *               Z_BUF_ERROR / ZMI_ZE_OUT              the region does not fit out_cap
+ *               Z_VERSION_ERROR / the entry's ZMI_ZE_*    the directory flagged the entry: a region of 0 bytes
+ *   d_out_len[j] = usize with status 0, 0 with every other status.  Never status 0 with wrong bytes; one bad entry does not touch its
+ *   neighbours' status or bytes.  n_sel 0 writes d_out_off[0] = 0.  Bytes and words do not depend on the alignment of d_in, on the
+ *   decode-kernel selection or on n_sel.  Scratch of the context: 32 bytes per slot, and the decoder's.
+ *   Event timing: 5 = directory / tables and plan, 3 / 6 = decode, resolve, 0 = CRC-32, 4 = verify, 7 = stored copies. */
+#define ZMI_ZA_NOEOCD 1     /* no end record that ends the file (Z_DATA_ERROR) */
+#define ZMI_ZA_BOUNDS 2     /* directory size and offset do not fit in front of the end structure (Z_DATA_ERROR) */
+#define ZMI_ZA_CHAIN 3      /* the directory chain breaks (Z_DATA_ERROR); index = the first bad entry */
+#define ZMI_ZA_COUNT 4      /* the entries walked are not the count the end structure names (Z_DATA_ERROR) */
+#define ZMI_ZA_ZIP64 5      /* a locator without a version-1 ZIP64 record of 56 bytes in front of it (Z_DATA_ERROR) */
+#define ZMI_ZA_MULTIDISK 6  /* a non-zero disk number (Z_VERSION_ERROR) */
+#define ZMI_ZE_LOCAL 1      /* local signature wrong; local header or data leave the file or reach into the directory; local method != central */
+#define ZMI_ZE_METHOD 2     /* method not 0 / 8 */
+#define ZMI_ZE_CRYPT 3      /* general-purpose bit 0 or bit 6 */
+#define ZMI_ZE_BIG 4        /* a size of 4 GiB or more: the field reads 0xFFFFFFFF */
+#define ZMI_ZE_EXTRA 5      /* a 32-bit field is 0xFFFFFFFF and the ZIP64 extra is missing, cut or too short */
+#define ZMI_ZE_STORED 6     /* stored with csize != usize */
+#define ZMI_ZE_DATA 7       /* slots only, from here on: a corrupt block */
+#define ZMI_ZE_LENGTH 8
+#define ZMI_ZE_CHECK 9
+#define ZMI_ZE_OUT 10
+typedef struct zmi_zip_entry {      /* 48 bytes */
+    uint64_t data_off;   /* first data byte of the entry in d_in: behind ITS LOCAL header (30 + the local name / extra lengths); 0 where
+                            the local header could not be read */
+    uint64_t name_off;   /* first byte of its name in d_in (inside the central directory), name_len bytes */
+    uint32_t csize, usize;            /* 0xFFFFFFFF together with ZMI_ZE_BIG when 4 GiB or more */
+    uint32_t crc32, dos_time /* date << 16 | time */, ext_attr;
+    uint16_t method, flags, name_len, reserved /* 0 */;
+    int32_t  status;     /* 0: readable by zmi_zip_inflate_dev; otherwise the ZMI_ZE_* reason, known from the directory alone (the first
+                            that holds of EXTRA, BIG, LOCAL, CRYPT, METHOD, STORED) */
+} zmi_zip_entry;
+typedef struct zmi_zip_info {       /* 48 bytes */
+    uint64_t n_entries, n_listed, cd_off, cd_size, base;
+    int32_t status, detail;
+} zmi_zip_info;
+uint32_t zmi_zip_walk_tile(void);   /* bytes of directory one window of the chain walk holds (for tests that place entries around it) */
+int zmi_zip_directory_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, zmi_zip_entry* d_entries, uint32_t cap, zmi_zip_info* d_info,
+                          void* stream);
+int zmi_zip_inflate_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, const zmi_zip_entry* d_entries, uint32_t n_entries,
+                        const uint32_t* d_sel, uint32_t n_sel, uint32_t out_align, void* d_out, uint64_t out_cap,
+                        uint64_t* d_out_off /* n_sel + 1 */, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, void* stream);
+
 /* ---- host-buffer convenience wrappers: copy in, run the batch on the GPU, copy back ---- */
 int zmi_deflate_batch(zmi_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_shards,
                       int level, int strategy, int wrap, uint8_t* out, uint64_t out_stride, uint32_t* out_len,

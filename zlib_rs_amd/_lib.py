@@ -71,6 +71,11 @@ def lib():
     L.zmi_bgzf_bound.argtypes = [u64, u32]
     L.zmi_bgzf_blocks_dev.argtypes = [vp, vp, vp, vp, u32, u32, i32, i32, vp, u64, vp, vp, vp, vp]
     L.zmi_bgzf_deflate_dev.argtypes = [vp, vp, u64, u32, i32, i32, vp, u64, vp, vp, vp, vp]
+    # reading ZIP archives: the directory, then a batch inflate of entries checked against it (csrc/pack.hip, zmi_api.hip)
+    L.zmi_zip_walk_tile.restype = u32
+    L.zmi_zip_walk_tile.argtypes = []
+    L.zmi_zip_directory_dev.argtypes = [vp, vp, u64, vp, u32, vp, vp]
+    L.zmi_zip_inflate_dev.argtypes = [vp, vp, u64, vp, u32, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp]
     # the multi-GPU stitch (csrc/exchange.hip); RCCL itself is loaded by the library on first use
     L.zmi_comm_unique_id.argtypes = [vp]
     L.zmi_comm_create.argtypes = [C.POINTER(vp), vp, i32, i32, vp]

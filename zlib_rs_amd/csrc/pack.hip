@@ -14,6 +14,7 @@
 // the chip.
 #include "zmi_device.h"
 #include "zmi_kernels.h"
+#include "../../include/zmi355.h"   // zmi_zip_entry, zmi_zip_info, ZMI_ZA_* / ZMI_ZE_*
 
 #define PK_T 256u
 #define PK_TILE 4096u
@@ -481,5 +482,409 @@ extern "C" int zmi_launch_bgzf_pack(const uint8_t* d_in, const uint64_t* d_in_of
 extern "C" int zmi_launch_bgzf_close(uint8_t* d_out, uint64_t out_cap, const uint64_t* d_blocks_end, uint32_t eof, uint64_t* d_out_len,
                                      int32_t* d_status, hipStream_t stream) {
     ZMI_LAUNCH(zmi_bgzf_close_kernel, dim3(1), dim3(1), 0, stream, d_out, out_cap, d_blocks_end, eof, d_out_len, d_status);
+    return 0;
+}
+
+// ---- ZIP archives (zmi_zip_directory_dev, zmi_zip_inflate_dev; the format rules: include/zmi355.h) ------------------
+// A ZIP is a batch of raw-deflate (or stored) streams whose size table and CRC-32s stand in the central directory at the end of the
+// file.  Three kernels read the directory -- locate (the end record, the ZIP64 record, the base), walk (the chain of directory entries:
+// an entry's length stands inside it), parse (one thread per entry: the fixed fields, the ZIP64 extra, the local header) -- and two
+// frame the batch decoder: prep (the tables of the selected slots) and verify (length, consumed input and CRC-32 against the table).
+#define ZIP_T 256u
+#define ZIP_TILE 16384u        // bytes of directory one window of the walk holds
+#define ZIP_EOCD 22u
+#define ZIP_TAIL 65557u        // 22 + the longest archive comment
+#define ZIP_CEN 46u
+#define ZIP_VERSION_ERROR (-6)
+#define ZIP_E_ARG (-103)       // ZMI_E_ARG, in a slot's status word
+
+static __device__ __forceinline__ uint32_t zip_u16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
+static __device__ __forceinline__ uint32_t zip_u32(const uint8_t* p) { return zip_u16(p) | (zip_u16(p + 2) << 16); }
+static __device__ __forceinline__ uint64_t zip_u64(const uint8_t* p) { return (uint64_t)zip_u32(p) | ((uint64_t)zip_u32(p + 4) << 32); }
+
+// w[0] the count the end structure names, w[1] != 0: that count is the 16-bit field (compared modulo 65536), w[2] / w[3] the first byte
+// of the directory and the first byte behind it, as offsets in the input
+#define ZIP_W_COUNT 0
+#define ZIP_W_COUNT16 1
+#define ZIP_W_DIR 2
+#define ZIP_W_END 3
+
+// One workgroup.  Every position p of the last <= 65557 bytes is tested for 50 4b 05 06 with the 16-byte lines of mm_line (a lane owns
+// the 16 positions of its line and sees three bytes of the next one); a hit counts if its comment length ends the file exactly, the
+// highest one wins (a maximum over 1 + p - lo, which fits 32 bits).  Thread 0 then parses the end record and, behind a locator, the
+// ZIP64 record.
+__global__ void __launch_bounds__(1024) zmi_zip_locate_kernel(const uint8_t* __restrict__ line0, uint32_t head, uint64_t n,
+                                                               zmi_zip_info* __restrict__ info, uint64_t* __restrict__ w) {
+    __shared__ uint32_t wbest[16];
+    const uint32_t t = threadIdx.x;
+    const uint8_t* in = line0 + head;
+    const uint64_t lo = n > ZIP_TAIL ? n - ZIP_TAIL : 0ull;
+    uint32_t best = 0;
+    if (n >= ZIP_EOCD) {
+        const uint64_t li0 = (lo + head) >> 4, li1 = (n - 1u + head) >> 4;
+        for (uint64_t b = li0; b <= li1; b += 1024u) {   // (the same trip count in every lane: the lines talk through DPP)
+            const uint64_t li = b + t;
+            const zmi_b16 c = mm_line(line0, li, head, n);
+            uint32_t fill = 0;
+            if (zmi_lane() == 63u) fill = mm_line(line0, li + 1u, head, n).w[0];
+            const uint32_t nx = zmi_lane_down1(c.w[0], fill);
+#pragma unroll
+            for (uint32_t i = 0; i < 16u; ++i) {
+                const uint32_t l = c.w[i >> 2], h = (i >> 2) == 3u ? nx : c.w[(i >> 2) + 1u];
+                const uint32_t v = (i & 3u) ? (l >> (8u * (i & 3u))) | (h << (32u - 8u * (i & 3u))) : l;
+                if (v != 0x06054B50u) continue;
+                const uint64_t q = li * 16u + i;             // (bytes in front of the input read as zero: q >= head here)
+                const uint64_t p = q - head;
+                if (p < lo || p + ZIP_EOCD > n) continue;
+                if (p + ZIP_EOCD + zip_u16(in + p + 20u) == n) best = (uint32_t)(p - lo) + 1u;
+            }
+        }
+    }
+    best = zmi_wave_max(best);
+    if (zmi_lane() == 0u) wbest[zmi_wave()] = best;
+    __syncthreads();
+    if (t != 0) return;
+    for (uint32_t k = 1; k < 16u; ++k) best = wbest[k] > best ? wbest[k] : best;
+    uint64_t cd_off = 0, cd_size = 0, base = 0, count = 0, count16 = 1, dir = 0, end = 0;
+    int32_t st = 0, det = 0;
+    if (best == 0u) { st = ZMI_DATA_ERROR; det = ZMI_ZA_NOEOCD; }
+    else {
+        const uint64_t p = lo + best - 1u;
+        const uint8_t* e = in + p;
+        uint32_t disks = zip_u16(e + 4) | zip_u16(e + 6);
+        count = zip_u16(e + 10);
+        cd_size = zip_u32(e + 12);
+        cd_off = zip_u32(e + 16);
+        end = p;
+        if (p >= 20u && zip_u32(e - 20) == 0x07064B50u) {   // the locator: the 56-byte record stands in front of it
+            if (p < 76u || zip_u32(e - 76) != 0x06064B50u || zip_u64(e - 72) != 44ull) { st = ZMI_DATA_ERROR; det = ZMI_ZA_ZIP64; }
+            else {
+                const uint8_t* r = e - 76;
+                disks = zip_u32(r + 16) | zip_u32(r + 20) | zip_u32(e - 16) | (zip_u32(e - 4) > 1u ? 1u : 0u);
+                if (zip_u16(e + 4) != 0xFFFFu) disks |= zip_u16(e + 4);
+                if (zip_u16(e + 6) != 0xFFFFu) disks |= zip_u16(e + 6);
+                count = zip_u64(r + 32);
+                cd_size = zip_u64(r + 40);
+                cd_off = zip_u64(r + 48);
+                count16 = 0;
+                end = p - 76u;
+            }
+        }
+        if (st == 0 && disks != 0u) { st = ZIP_VERSION_ERROR; det = ZMI_ZA_MULTIDISK; }
+        if (st == 0) {
+            if (cd_size > end || cd_off > end - cd_size) { st = ZMI_DATA_ERROR; det = ZMI_ZA_BOUNDS; }
+            else { base = end - cd_size - cd_off; dir = end - cd_size; }
+        }
+    }
+    info->n_entries = 0;
+    info->n_listed = 0;
+    info->cd_off = cd_off;
+    info->cd_size = cd_size;
+    info->base = base;
+    info->status = st;
+    info->detail = det;
+    w[ZIP_W_COUNT] = count;
+    w[ZIP_W_COUNT16] = count16;
+    w[ZIP_W_DIR] = dir;
+    w[ZIP_W_END] = end;
+}
+
+// tile[mis + k] = in[p0 + k] for every k with mis + k < span, where span = min(want, mis + the bytes from p0 to `end`): aligned 16-byte
+// loads from the line at or below in + p0, the first and last line byte-wise, so nothing outside [p0, end) is read.  Returns mis.
+static __device__ __forceinline__ uint32_t zip_load_window(uint8_t* tile, const uint8_t* __restrict__ in, uint64_t p0, uint64_t end, uint32_t want,
+                                                           uint32_t t, uint32_t* span_out) {
+    const uint32_t mis = (uint32_t)((uintptr_t)(in + p0) & 15u);
+    const uint8_t* line0 = in + p0 - mis;
+    const uint64_t left = end - p0 + mis;
+    const uint32_t span = left < want ? (uint32_t)left : want;
+    for (uint32_t c = t * 16u; c < span; c += ZIP_T * 16u) {
+        if (c + 16u <= span && (c >= 16u || mis == 0u)) {
+            *(uint4*)(tile + c) = *(const uint4*)(line0 + c);
+        } else {
+            for (uint32_t j = 0; j < 16u; ++j)
+                if (c + j >= mis && c + j < span) tile[c + j] = line0[c + j];
+        }
+    }
+    *span_out = span;
+    return mis;
+}
+
+// One step of the chain at `pos`, whose 46 header bytes stand at tile[o ..): the entry's length, or 0 where the chain breaks (wrong
+// signature, or the entry would end behind the directory)
+static __device__ __forceinline__ uint64_t zip_chain_step(const uint8_t* tile, uint32_t o, uint64_t pos, uint64_t end) {
+    const uint32_t sig = zmi_load32u(tile, o), ne = zmi_load32u(tile, o + 28u), cl = zmi_load32u(tile, o + 32u) & 0xFFFFu;
+    const uint64_t len = (uint64_t)ZIP_CEN + (ne & 0xFFFFu) + (ne >> 16) + cl;
+    return (sig != 0x02014B50u || len > end - pos) ? 0ull : len;
+}
+
+// The chain is serial -- an entry's length stands inside it -- and one lane following it through LDS takes about 0.2 us an entry (measured:
+// 19.6 ms of a 100 000-entry archive).  So the directory is cut into segments of ZIP_TILE bytes and every segment is followed on its own,
+// one workgroup each, from a GUESS of where the chain enters it: the first position in the segment that holds 50 4b 01 02 (the chain's
+// first entry in a segment holds it, so the guess is wrong only when a name, extra or comment in front of it spells the signature).
+// seg[4k ..] = the guess q, the position x the segment's chase stopped at (the first chain position at or behind the segment's end, or
+// where the chain broke or ended), the entries n in between, and a word the walk fills in.  The walk kernel below then only stitches: where
+// the chain enters segment k at q exactly it takes (x, n) for the whole segment; where it does not, it follows the chain itself.
+// pass 1, behind the walk: the segments the walk took write their positions at the rank the walk gave them (seg[4k + 3]).
+// A header that starts in a segment may end up to 45 bytes behind it: the window holds 48 bytes more.
+#define ZIP_SEG_NONE 0xFFFFFFFFFFFFFFFFull
+__global__ void __launch_bounds__(ZIP_T) zmi_zip_segment_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ w, uint64_t* __restrict__ seg, uint64_t* __restrict__ chain,
+                                                               uint32_t cap, uint32_t pass) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[ZIP_TILE + 96];
+    __shared__ uint32_t s_q;
+    const uint32_t t = threadIdx.x;
+    const uint64_t dir = w[ZIP_W_DIR], end = w[ZIP_W_END];
+    const uint64_t lo = dir + (uint64_t)blockIdx.x * ZIP_TILE;
+    if (lo >= end) return;       // (the whole workgroup; an end record that gave no directory left dir = end = 0.  info->status is
+                                 // not asked: behind the walk it may say CHAIN or COUNT, and the entries in front stay listed)
+    uint64_t* sg = seg + 4ull * blockIdx.x;
+    if (pass == 1u && sg[3] == ZIP_SEG_NONE) return;
+    const uint64_t hi = end - lo < ZIP_TILE ? end : lo + ZIP_TILE;
+    if (t == 0) s_q = 0xFFFFFFFFu;
+    uint32_t span;
+    const uint32_t mis = zip_load_window(tile, in, lo, end, ZIP_TILE + 64u, t, &span);
+    __syncthreads();
+    if (pass == 0u) {
+        for (uint32_t i = t; i < (uint32_t)(hi - lo); i += ZIP_T)
+            if (end - (lo + i) >= ZIP_CEN && zmi_load32u(tile, mis + i) == 0x02014B50u) { atomicMin(&s_q, i); break; }
+        __syncthreads();
+    }
+    if (t != 0) return;
+    uint64_t pos = pass == 0u ? (s_q == 0xFFFFFFFFu ? ZIP_SEG_NONE : lo + s_q) : sg[0];
+    uint64_t n = 0, at = pass == 1u ? sg[3] : 0ull;
+    const uint64_t q = pos;
+    if (pos != ZIP_SEG_NONE) {
+        while (pos < hi && end - pos >= ZIP_CEN) {
+            const uint64_t len = zip_chain_step(tile, (uint32_t)(pos - lo) + mis, pos, end);
+            if (len == 0ull) break;
+            if (pass == 1u && at + n < cap) chain[at + n] = pos;
+            ++n;
+            pos += len;
+        }
+    }
+    if (pass == 0u) { sg[0] = q; sg[1] = pos; sg[2] = n; sg[3] = ZIP_SEG_NONE; }
+}
+
+// One workgroup stitches.  Thread 0 keeps the chain's position: where it stands on a segment's guess it takes the segment whole and
+// notes the rank of the segment's first entry; elsewhere the workgroup loads a window of ZIP_TILE bytes that starts at the 16-byte line
+// of THAT position (aligned 16-byte loads, the first and last line byte-wise) and thread 0 follows the chain through it -- signature,
+// the three lengths, 46 + name + extra + comment -- writing every entry's position, until the next header does not lie whole inside
+// the window.  A window starts at the chain's position wherever it is: a header never straddles a window it is read from, and the
+// tiles an entry of up to 46 + 3 x 65535 bytes spans are never loaded.
+__global__ void __launch_bounds__(ZIP_T) zmi_zip_walk_kernel(const uint8_t* __restrict__ in, zmi_zip_info* info, const uint64_t* __restrict__ w,
+                                                            uint64_t* __restrict__ seg, uint64_t nseg_max, uint64_t* __restrict__ chain, uint32_t cap) {
+    __shared__ __attribute__((aligned(16))) uint8_t tile[ZIP_TILE + 16];
+    __shared__ uint64_t s_pos;
+    __shared__ uint32_t s_state;   // 0 the chain goes on, 1 it ended on the directory's end, 2 it broke, 3 there is no directory
+    const uint32_t t = threadIdx.x;
+    const uint64_t dir = w[ZIP_W_DIR], end = w[ZIP_W_END];
+    if (t == 0) { s_pos = dir; s_state = info->status != 0 ? 3u : 0u; }
+    __syncthreads();
+    if (s_state == 3u) return;   // (the whole workgroup: the end record gave no directory)
+    uint64_t count = 0;
+    for (;;) {
+        if (t == 0) {
+            uint64_t pos = s_pos;
+            while (pos < end) {                              // whole segments, where the chain enters them at their guess
+                const uint64_t k = (pos - dir) / ZIP_TILE;
+                if (k >= nseg_max || seg[4u * k] != pos || seg[4u * k + 1u] == pos) break;
+                seg[4u * k + 3u] = count;
+                count += seg[4u * k + 2u];
+                pos = seg[4u * k + 1u];
+            }
+            s_pos = pos;
+            s_state = pos == end ? 1u : (end - pos < ZIP_CEN ? 2u : 0u);
+        }
+        __syncthreads();
+        if (s_state != 0u) break;
+        const uint64_t p0 = s_pos;
+        uint32_t span;
+        const uint32_t mis = zip_load_window(tile, in, p0, end, ZIP_TILE, t, &span);
+        __syncthreads();
+        if (t == 0) {
+            uint64_t pos = p0;
+            uint32_t state = 0;
+            const uint64_t bound = dir + ((p0 - dir) / ZIP_TILE + 1u) * ZIP_TILE;   // the next segment may have guessed right again
+            for (;;) {
+                if (pos == end) { state = 1u; break; }
+                if (end - pos < ZIP_CEN) { state = 2u; break; }
+                if (pos >= bound) break;
+                const uint64_t o64 = pos - p0 + mis;
+                if (o64 + ZIP_CEN > span) break;             // the header is not whole in this window: the next one starts at it
+                const uint64_t len = zip_chain_step(tile, (uint32_t)o64, pos, end);
+                if (len == 0ull) { state = 2u; break; }
+                if (count < cap) chain[count] = pos;
+                ++count;
+                pos += len;
+            }
+            s_pos = pos;
+            s_state = state;
+        }
+        __syncthreads();
+        if (s_state != 0u) break;
+    }
+    if (t != 0) return;
+    info->n_entries = count;
+    info->n_listed = count < cap ? count : cap;
+    if (s_state == 2u) { info->status = ZMI_DATA_ERROR; info->detail = (int32_t)(ZMI_ZA_CHAIN | ((uint32_t)count << 8)); return; }
+    const uint64_t want = w[ZIP_W_COUNT];
+    if (w[ZIP_W_COUNT16] ? (count & 0xFFFFull) != want : count != want) { info->status = ZMI_DATA_ERROR; info->detail = ZMI_ZA_COUNT; }
+}
+
+// One thread per listed entry: the fixed fields of the directory entry, the values of its ZIP64 extra, its local header.
+__global__ void __launch_bounds__(256) zmi_zip_parse_kernel(const uint8_t* __restrict__ in, zmi_zip_info* info, const uint64_t* __restrict__ w,
+                                                            const uint64_t* __restrict__ chain, zmi_zip_entry* __restrict__ ent, uint32_t cap) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= cap || (uint64_t)i >= info->n_listed) return;
+    const uint64_t dir = w[ZIP_W_DIR], base = info->base, at = chain[i];
+    const uint8_t* h = in + at;
+    const uint32_t flags = zip_u16(h + 8), method = zip_u16(h + 10), nl = zip_u16(h + 28), el = zip_u16(h + 30);
+    uint64_t csize = zip_u32(h + 20), usize = zip_u32(h + 24), lho = zip_u32(h + 42);
+    int32_t st = 0;
+    if (zip_u16(h + 34) != 0u && atomicCAS(&info->status, 0, ZIP_VERSION_ERROR) == 0) info->detail = ZMI_ZA_MULTIDISK;
+    if (csize == 0xFFFFFFFFull || usize == 0xFFFFFFFFull || lho == 0xFFFFFFFFull) {
+        // the ZIP64 extra: 8-byte values for exactly those of usize, csize, offset (in that order) whose field is all ones
+        const uint8_t* x = h + ZIP_CEN + nl;
+        st = ZMI_ZE_EXTRA;
+        for (uint32_t a = 0; a + 4u <= el;) {
+            const uint32_t id = zip_u16(x + a), sz = zip_u16(x + a + 2u);
+            if (a + 4u + sz > el) break;
+            if (id == 1u) {
+                const uint32_t need = 8u * ((usize == 0xFFFFFFFFull) + (csize == 0xFFFFFFFFull) + (lho == 0xFFFFFFFFull));
+                if (sz >= need) {
+                    const uint8_t* q = x + a + 4u;
+                    if (usize == 0xFFFFFFFFull) { usize = zip_u64(q); q += 8; }
+                    if (csize == 0xFFFFFFFFull) { csize = zip_u64(q); q += 8; }
+                    if (lho == 0xFFFFFFFFull) lho = zip_u64(q);
+                    st = 0;
+                }
+                break;
+            }
+            a += 4u + sz;
+        }
+    }
+    const bool big = st == 0 && (csize > 0xFFFFFFFFull || usize > 0xFFFFFFFFull);
+    uint64_t data_off = 0;
+    bool local_ok = false;
+    if (st == 0 && lho <= dir - base && base + lho + 30u <= dir) {
+        const uint8_t* l = in + base + lho;
+        if (zip_u32(l) == 0x04034B50u && zip_u16(l + 8) == method) {
+            data_off = base + lho + 30u + zip_u16(l + 26) + zip_u16(l + 28);   // the LOCAL name and extra lengths
+            local_ok = data_off <= dir && csize <= dir - data_off;
+        }
+    }
+    if (st == 0) {
+        if (big) st = ZMI_ZE_BIG;
+        else if (!local_ok) st = ZMI_ZE_LOCAL;
+        else if (flags & 0x41u) st = ZMI_ZE_CRYPT;
+        else if (method != 0u && method != 8u) st = ZMI_ZE_METHOD;
+        else if (method == 0u && csize != usize) st = ZMI_ZE_STORED;
+    }
+    zmi_zip_entry e;
+    e.data_off = data_off;
+    e.name_off = at + ZIP_CEN;
+    e.csize = csize > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)csize;
+    e.usize = usize > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)usize;
+    e.crc32 = zip_u32(h + 16);
+    e.dos_time = (zip_u16(h + 14) << 16) | zip_u16(h + 12);
+    e.ext_attr = zip_u32(h + 38);
+    e.method = (uint16_t)method;
+    e.flags = (uint16_t)flags;
+    e.name_len = (uint16_t)nl;
+    e.reserved = 0;
+    e.status = st;
+    ent[i] = e;
+}
+
+// What slot j reads: 0 a deflated entry, 1 a stored one, 2 an entry the directory flagged, 3 nothing the table allows (an index that
+// is not in it, or data that leaves the input: the table was not made from this buffer)
+static __device__ __forceinline__ uint32_t zip_slot_kind(const zmi_zip_entry* __restrict__ ent, uint32_t n_entries, const uint32_t* __restrict__ sel,
+                                                         uint32_t j, uint64_t in_len, zmi_zip_entry* e) {
+    const uint32_t k = sel ? sel[j] : j;
+    if (k >= n_entries) return 3u;
+    *e = ent[k];
+    if (e->status != 0) return 2u;
+    if (e->data_off > in_len || e->csize > in_len - e->data_off) return 3u;
+    if (e->method == 8u) return 0u;
+    return e->method == 0u && e->csize == e->usize ? 1u : 3u;
+}
+
+// the tables of the selection: what the plan, the batch decoder (deflated slots; the others hand it no input) and the range copy
+// (stored slots) take
+__global__ void __launch_bounds__(256) zmi_zip_prep_kernel(const zmi_zip_entry* __restrict__ ent, uint32_t n_entries, const uint32_t* __restrict__ sel,
+                                                           uint32_t n_sel, uint64_t in_len, uint64_t* __restrict__ in_off,
+                                                           uint32_t* __restrict__ in_n, uint32_t* __restrict__ size, uint32_t* __restrict__ slen) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n_sel) return;
+    zmi_zip_entry e;
+    const uint32_t kind = zip_slot_kind(ent, n_entries, sel, j, in_len, &e);
+    in_off[j] = kind <= 1u ? e.data_off : 0ull;
+    in_n[j] = kind == 0u ? e.csize : 0u;
+    size[j] = kind <= 1u ? e.usize : 0u;
+    slen[j] = kind == 1u ? e.usize : 0u;
+}
+
+// One thread per slot, behind the decode, the stored copies and the CRC-32 of every region (cap[j] bytes: the planned size where the
+// region fits out_cap, else 0): the slot's final words.  Every status but 0 reports length 0.
+__global__ void __launch_bounds__(256) zmi_zip_verify_kernel(const zmi_zip_entry* __restrict__ ent, uint32_t n_entries, const uint32_t* __restrict__ sel,
+                                                             uint32_t n_sel, uint64_t in_len, const uint64_t* __restrict__ out_off, uint64_t out_cap,
+                                                             const uint32_t* __restrict__ used, const uint32_t* __restrict__ crc,
+                                                             uint32_t* __restrict__ out_len, int32_t* __restrict__ status, int32_t* __restrict__ detail) {
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= n_sel) return;
+    zmi_zip_entry e;
+    const uint32_t kind = zip_slot_kind(ent, n_entries, sel, j, in_len, &e);
+    int32_t st = 0, det = 0;
+    if (kind == 3u) st = ZIP_E_ARG;
+    else if (kind == 2u) { st = ZIP_VERSION_ERROR; det = e.status; }
+    else if (out_off[j] + (uint64_t)e.usize > out_cap) { st = ZMI_BUF_ERROR; det = ZMI_ZE_OUT; }
+    else {
+        if (kind == 0u) {
+            const int32_t ds = status[j];
+            if (ds == ZMI_OK) { if (out_len[j] != e.usize || used[j] != e.csize) { st = ZMI_DATA_ERROR; det = ZMI_ZE_LENGTH; } }
+            else if (ds == ZMI_BUF_ERROR) { st = ZMI_DATA_ERROR; det = ZMI_ZE_LENGTH; }   // the stream wants more input than csize, or more room than usize
+            else if (ds == ZMI_DATA_ERROR) { st = ZMI_DATA_ERROR; det = ZMI_ZE_DATA; }
+            else st = ds;
+        }
+        if (st == 0 && crc[j] != e.crc32) { st = ZMI_DATA_ERROR; det = ZMI_ZE_CHECK; }
+    }
+    status[j] = st;
+    detail[j] = det;
+    out_len[j] = st == 0 ? e.usize : 0u;
+}
+
+extern "C" uint32_t zmi_zip_walk_tile(void) { return ZIP_TILE; }
+// segments a directory inside in_len bytes can have (its size is a device word: the launch covers the bound, the others return)
+extern "C" uint64_t zmi_zip_segments(uint64_t in_len) { return in_len / ZIP_TILE + 1u; }
+// d_w: four words, d_chain: u64[cap], d_seg: four words per segment of zmi_zip_segments(in_len).  stages 1: locate, 2: and the chain
+// (segments, walk, segments' positions), 3: and the parse (the probe's split of the directory time)
+extern "C" int zmi_launch_zip_directory(const uint8_t* d_in, uint64_t in_len, zmi_zip_entry* d_entries, uint32_t cap, zmi_zip_info* d_info,
+                                        uint64_t* d_w, uint64_t* d_chain, uint64_t* d_seg, uint32_t stages, hipStream_t stream) {
+    const uint32_t head = (uint32_t)((uintptr_t)d_in & 15u);
+    ZMI_LAUNCH(zmi_zip_locate_kernel, dim3(1), dim3(1024), 0, stream, d_in - head, head, in_len, d_info, d_w);
+    if (stages < 2u) return 0;
+    const uint64_t nseg = zmi_zip_segments(in_len);
+    const uint32_t grid = nseg > 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)nseg;
+    ZMI_LAUNCH(zmi_zip_segment_kernel, dim3(grid), dim3(ZIP_T), 0, stream, d_in, (const uint64_t*)d_w, d_seg, d_chain, cap, 0u);
+    ZMI_LAUNCH(zmi_zip_walk_kernel, dim3(1), dim3(ZIP_T), 0, stream, d_in, d_info, (const uint64_t*)d_w, d_seg, (uint64_t)grid, d_chain, cap);
+    if (cap == 0u) return 0;
+    ZMI_LAUNCH(zmi_zip_segment_kernel, dim3(grid), dim3(ZIP_T), 0, stream, d_in, (const uint64_t*)d_w, d_seg, d_chain, cap, 1u);
+    if (stages < 3u) return 0;
+    ZMI_LAUNCH(zmi_zip_parse_kernel, dim3((cap + 255u) / 256u), dim3(256), 0, stream, d_in, d_info, (const uint64_t*)d_w, (const uint64_t*)d_chain,
+               d_entries, cap);
+    return 0;
+}
+extern "C" int zmi_launch_zip_prep(const zmi_zip_entry* d_entries, uint32_t n_entries, const uint32_t* d_sel, uint32_t n_sel, uint64_t in_len,
+                                   uint64_t* d_in_off, uint32_t* d_in_n, uint32_t* d_size, uint32_t* d_slen, hipStream_t stream) {
+    if (n_sel == 0) return 0;
+    ZMI_LAUNCH(zmi_zip_prep_kernel, dim3((n_sel + 255u) / 256u), dim3(256), 0, stream, d_entries, n_entries, d_sel, n_sel, in_len, d_in_off, d_in_n,
+               d_size, d_slen);
+    return 0;
+}
+extern "C" int zmi_launch_zip_verify(const zmi_zip_entry* d_entries, uint32_t n_entries, const uint32_t* d_sel, uint32_t n_sel, uint64_t in_len,
+                                     const uint64_t* d_out_off, uint64_t out_cap, const uint32_t* d_used, const uint32_t* d_crc,
+                                     uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, hipStream_t stream) {
+    if (n_sel == 0) return 0;
+    ZMI_LAUNCH(zmi_zip_verify_kernel, dim3((n_sel + 255u) / 256u), dim3(256), 0, stream, d_entries, n_entries, d_sel, n_sel, in_len, d_out_off,
+               out_cap, d_used, d_crc, d_out_len, d_status, d_detail);
     return 0;
 }

@@ -115,6 +115,7 @@ struct zmi_ctx {
     zmi_buf si_scan;                    // zmi_stream_find_blocks_dev: one window's survivor slots and validated list
     zmi_buf mm_scan, mm_meta;           // zmi_gzip_find_members_dev: segment counts and offsets; zmi_inflate_members_dev: its tables
     zmi_buf pk;                         // zmi_inflate_batch_packed_dev: size[n] cap[n] (the size pass's result, the planned capacity table)
+    zmi_buf zip_dir, zip_sel;           // zmi_zip_directory_dev: four words, the chain positions, four words per segment; zmi_zip_inflate_dev: the slots' tables
     zmi_buf dict;                       // the shared-dictionary batch calls: layout words and DICTID | deflate image | inflate image (zmi_sd_*)
 };
 
@@ -173,6 +174,8 @@ extern "C" int zmi_ctx_destroy(zmi_ctx* c) {
     if (c->si_scan.p) (void)hipFree(c->si_scan.p);
     if (c->dict.p) (void)hipFree(c->dict.p);
     if (c->pk.p) (void)hipFree(c->pk.p);
+    if (c->zip_dir.p) (void)hipFree(c->zip_dir.p);
+    if (c->zip_sel.p) (void)hipFree(c->zip_sel.p);
     if (c->mm_scan.p) (void)hipFree(c->mm_scan.p);
     if (c->mm_meta.p) (void)hipFree(c->mm_meta.p);
     for (int k = 0; k < 2; ++k) if (c->st_pin[k].p) (void)hipHostFree(c->st_pin[k].p);
@@ -1203,6 +1206,36 @@ extern "C" int zmi_inflate_sizes_dev(zmi_ctx* c, const void* d_in, const uint64_
     return ZMI_E_OK;
 }
 
+// What the packed call does behind its size pass, shared with zmi_zip_inflate_dev (which takes the sizes from the directory): the plan
+// -- d_out_off, and d_cap[i] = d_size[i] where the region ends at or before out_cap, else 0 -- the decode with the planned tables under
+// a bitmap sized from out_cap, and the mark of the streams that did not fit.  plan_timer: the event-timing slot of the plan, -1 none.
+static int zmi_inflate_packed_body(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n, int wrap,
+                                   const void* d_dict, uint32_t dict_len, const uint32_t* d_size, uint32_t* d_cap, uint32_t out_align,
+                                   void* d_out, uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status,
+                                   uint32_t* d_in_used, int32_t* d_detail, int plan_timer, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (plan_timer >= 0) {
+        zmi_scope_timer tm(c, plan_timer, stream);
+        zmi_launch_inflate_pack_plan(d_size, n, out_align, out_cap, d_out_off, d_cap, stream);
+    } else {
+        zmi_launch_inflate_pack_plan(d_size, n, out_align, out_cap, d_out_off, d_cap, stream);
+    }
+    // the bitmap scratch covers what the planned capacities can sum to: out_cap (no stream holds more than 2^32 - 1 bytes)
+    const uint64_t most = (uint64_t)n * 0xFFFFFFFFull;
+    const uint64_t saved_limit = c->inflate_out_limit;
+    c->inflate_out_limit = (out_cap < most ? out_cap : most) + (1ull << 16);
+    c->inf_limit_exact = true;
+    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; c->inf_limit_exact = false; } } restore_limit{c, saved_limit};
+    int rc;
+    if (d_dict) rc = zmi_inflate_batch_shared_dict_dev(c, d_in, d_in_off, d_in_len, n, wrap, d_dict, dict_len, d_out, d_out_off, d_cap, d_out_len,
+                                                       d_status, d_in_used, d_detail, stream_);
+    else rc = zmi_inflate_impl(c, d_in, d_in_off, d_in_len, n, wrap, d_out, d_out_off, d_cap, nullptr, d_out_len, d_status, d_in_used, d_detail,
+                               nullptr, nullptr, stream_);
+    if (rc) return rc;
+    zmi_launch_inflate_pack_mark(d_size, d_out_off, n, out_cap, d_out_len, d_status, d_in_used, d_detail, stream);
+    return ZMI_E_OK;
+}
+
 extern "C" int zmi_inflate_batch_packed_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
                                             int wrap, const void* d_dict, uint32_t dict_len, uint32_t size_limit, uint32_t out_align,
                                             void* d_out, uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status,
@@ -1230,24 +1263,83 @@ extern "C" int zmi_inflate_batch_packed_dev(zmi_ctx* c, const void* d_in, const 
     rc = zmi_inflate_sizes_impl(c, d_in, d_in_off, d_in_len, n, wrap, dict ? (dict_len < 32768u ? dict_len : 32768u) : 0u, size_limit, d_size,
                                 d_status, d_in_used, d_detail, stream);
     if (rc) return rc;
-    zmi_launch_inflate_pack_plan(d_size, n, out_align, out_cap, d_out_off, d_cap, stream);
-    // the bitmap scratch covers what the planned capacities can sum to: out_cap (no stream holds more than 2^32 - 1 bytes)
-    const uint64_t most = (uint64_t)n * 0xFFFFFFFFull;
-    const uint64_t saved_limit = c->inflate_out_limit;
-    c->inflate_out_limit = (out_cap < most ? out_cap : most) + (1ull << 16);
-    c->inf_limit_exact = true;
-    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; c->inf_limit_exact = false; } } restore_limit{c, saved_limit};
-    if (dict) rc = zmi_inflate_batch_shared_dict_dev(c, d_in, d_in_off, d_in_len, n, wrap, d_dict, dict_len, d_out, d_out_off, d_cap, d_out_len,
-                                                     d_status, d_in_used, d_detail, stream_);
-    else rc = zmi_inflate_impl(c, d_in, d_in_off, d_in_len, n, wrap, d_out, d_out_off, d_cap, nullptr, d_out_len, d_status, d_in_used, d_detail,
-                               nullptr, nullptr, stream_);
+    rc = zmi_inflate_packed_body(c, d_in, d_in_off, d_in_len, n, wrap, dict ? d_dict : nullptr, dict_len, d_size, d_cap, out_align, d_out, out_cap,
+                                 d_out_off, d_out_len, d_status, d_in_used, d_detail, -1, stream_);
     if (rc) return rc;
-    zmi_launch_inflate_pack_mark(d_size, d_out_off, n, out_cap, d_out_len, d_status, d_in_used, d_detail, stream);
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;
 }
 
-// ---------------- host-buffer wrappers ----------------
+// ---- ZIP archives (include/zmi355.h; kernels in pack.hip) ----
+extern "C" int zmi_zip_directory_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, zmi_zip_entry* d_entries, uint32_t cap, zmi_zip_info* d_info,
+                                     void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (!d_info || (in_len && !d_in) || (cap && !d_entries)) return zmi_fail(ZMI_E_ARG, "null argument");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    const uint64_t nseg = zmi_zip_segments(in_len);
+    int rc = zmi_reserve(c->zip_dir, 32u + (size_t)cap * 8u + (size_t)nseg * 32u);
+    if (rc) return rc;
+    uint32_t stages = 3u;
+    if (const char* sv = zmi_tune("ZMI_ZIP_STAGES")) stages = (uint32_t)atoi(sv);   // (the probe: locate / walk / parse timed apart)
+    {
+        zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
+        uint64_t* d_w = (uint64_t*)c->zip_dir.p;
+        zmi_launch_zip_directory((const uint8_t*)d_in, in_len, d_entries, cap, d_info, d_w, d_w + 4, d_w + 4 + cap, stages, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+extern "C" int zmi_zip_inflate_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, const zmi_zip_entry* d_entries, uint32_t n_entries,
+                                   const uint32_t* d_sel, uint32_t n_sel, uint32_t out_align, void* d_out, uint64_t out_cap,
+                                   uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (out_align == 0u || out_align > 4096u || (out_align & (out_align - 1u)) != 0u)
+        return zmi_fail(ZMI_E_ARG, "out_align must be a power of two, 1 .. 4096");
+    if (!d_out_off) return zmi_fail(ZMI_E_ARG, "d_out_off is required");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    if (n_sel == 0) {
+        ZMI_HIP(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), stream));
+        return ZMI_E_OK;
+    }
+    if (!d_out_len || !d_status || !d_detail) return zmi_fail(ZMI_E_ARG, "d_out_len, d_status and d_detail are required");
+    if ((n_entries && !d_entries) || (in_len && !d_in) || (out_cap && !d_out)) return zmi_fail(ZMI_E_ARG, "null argument");
+    int rc = zmi_reserve(c->zip_sel, (size_t)n_sel * 32u);
+    if (rc) return rc;
+    uint64_t* d_in_off = (uint64_t*)c->zip_sel.p;                 // the entry's first data byte
+    uint32_t* d_in_n = (uint32_t*)(d_in_off + n_sel);            // csize of a deflated slot, 0 for every other
+    uint32_t* d_size = d_in_n + n_sel;                           // usize of a readable slot: the plan's sizes
+    uint32_t* d_slen = d_size + n_sel;                           // usize of a stored slot: the copy's lengths
+    uint32_t* d_cap = d_slen + n_sel;                            // the planned size where the region fits out_cap, else 0
+    uint32_t* d_used = d_cap + n_sel;
+    uint32_t* d_crc = d_used + n_sel;
+    {
+        zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
+        zmi_launch_zip_prep(d_entries, n_entries, d_sel, n_sel, in_len, d_in_off, d_in_n, d_size, d_slen, stream);
+    }
+    rc = zmi_inflate_packed_body(c, d_in, d_in_off, d_in_n, n_sel, ZMI_WRAP_RAW, nullptr, 0u, d_size, d_cap, out_align, d_out, out_cap, d_out_off,
+                                 d_out_len, d_status, d_used, d_detail, ZMI_K_PARSE, stream_);
+    if (rc) return rc;
+    {
+        // stored slots: a range that would end behind out_cap is skipped by the copy itself; max_len only shapes the launch
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_copy_ranges((const uint8_t*)d_in, d_in_off, 0u, d_slen, n_sel, (uint8_t*)d_out, d_out_off, out_cap,
+                               in_len > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)in_len, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_CHECKSUM, stream);
+        zmi_launch_checksum((const uint8_t*)d_out, d_out_off, d_cap, n_sel, 2u, nullptr, d_crc, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_zip_verify(d_entries, n_entries, d_sel, n_sel, in_len, d_out_off, out_cap, d_used, d_crc, d_out_len, d_status, d_detail, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
 static int zmi_host_pipeline_init(zmi_ctx* c) {   // three streams (in / kernels / out) and the events of the two slots
     if (c->hb_live) return 0;
     ZMI_HIP(hipStreamCreateWithFlags(&c->hs_in, hipStreamNonBlocking));

@@ -59,6 +59,9 @@ struct zmi_enc_params {
 #define ZMI_DATA_ERROR (-3)
 #define ZMI_BUF_ERROR (-5)
 
+struct zmi_zip_entry;   // include/zmi355.h
+struct zmi_zip_info;
+
 extern "C" {
 int zmi_launch_gen(uint8_t* d_out, uint64_t seed, uint32_t first_shard, uint32_t n_shards, uint32_t shard_bytes,
                    hipStream_t stream);
@@ -223,4 +226,16 @@ int zmi_launch_mm_final(const uint64_t* d_starts, uint32_t n, uint32_t* d_tab, u
                         const uint32_t* lr_used, const int32_t* lr_det, const uint32_t* chk_trailer, const uint32_t* chk_crc,
                         uint64_t* d_out_len, uint64_t* d_in_used, uint32_t* d_members, uint64_t* d_member_off, int32_t* d_status,
                         int32_t* d_detail, hipStream_t stream);
+// ZIP archives (pack.hip): the directory -- locate, the chain (segments followed side by side, the stitching walk), parse; d_w four
+// words, d_chain u64[cap], d_seg four words per segment of zmi_zip_segments(in_len), stages 1 .. 3 = how many of the three run -- and
+// the two kernels around the batch decoder: the tables of the selected slots, and the slots' final words
+uint32_t zmi_zip_walk_tile(void);
+uint64_t zmi_zip_segments(uint64_t in_len);
+int zmi_launch_zip_directory(const uint8_t* d_in, uint64_t in_len, zmi_zip_entry* d_entries, uint32_t cap, zmi_zip_info* d_info, uint64_t* d_w,
+                             uint64_t* d_chain, uint64_t* d_seg, uint32_t stages, hipStream_t stream);
+int zmi_launch_zip_prep(const zmi_zip_entry* d_entries, uint32_t n_entries, const uint32_t* d_sel, uint32_t n_sel, uint64_t in_len,
+                        uint64_t* d_in_off, uint32_t* d_in_n, uint32_t* d_size, uint32_t* d_slen, hipStream_t stream);
+int zmi_launch_zip_verify(const zmi_zip_entry* d_entries, uint32_t n_entries, const uint32_t* d_sel, uint32_t n_sel, uint64_t in_len,
+                          const uint64_t* d_out_off, uint64_t out_cap, const uint32_t* d_used, const uint32_t* d_crc, uint32_t* d_out_len,
+                          int32_t* d_status, int32_t* d_detail, hipStream_t stream);
 }

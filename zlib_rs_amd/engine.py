@@ -18,6 +18,10 @@ GEN_SEED = 0x5A4C4942
 SI_CUT, SI_PIECE, SI_OUT = 3, 4, 9
 BGZF_BLOCK_MAX, BGZF_HEADER, BGZF_EOF = 65280, 18, 28   # ZMI_BGZF_* (include/zmi355.h)
 MM_HEADER, MM_TRUNC, MM_DATA, MM_CHECK, MM_LENGTH, MM_OUT, MM_BIG, MM_AGAIN = 1, 2, 3, 4, 5, 6, 7, 8   # ZMI_MM_* (include/zmi355.h)
+# zmi_zip_directory_dev / zmi_zip_inflate_dev (include/zmi355.h ZMI_ZA_* / ZMI_ZE_*)
+ZA_NOEOCD, ZA_BOUNDS, ZA_CHAIN, ZA_COUNT, ZA_ZIP64, ZA_MULTIDISK = 1, 2, 3, 4, 5, 6
+ZE_LOCAL, ZE_METHOD, ZE_CRYPT, ZE_BIG, ZE_EXTRA, ZE_STORED, ZE_DATA, ZE_LENGTH, ZE_CHECK, ZE_OUT = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
+ZIP_ENTRY_BYTES = 48
 
 
 def _stream_ptr():
@@ -134,6 +138,70 @@ class BgzfIndex:
         else:
             off = [0]
         return cls(torch.tensor(off, dtype=torch.int64, device=torch.device(device)), block_bytes, n)
+
+
+class ZipDirectory:
+    """The central directory of a ZIP archive as zmi_zip_directory_dev lists it (include/zmi355.h).  entries: uint8 [n_listed, 48], the
+    device table of zmi_zip_entry records; info: the host copy of zmi_zip_info as a dict; data: the archive on the device.  The int32
+    views below are slices of the table: usize / csize / crc32 are uint32 words and read negative from 2 GiB on."""
+
+    def __init__(self, data, entries, info):
+        self.data, self.entries, self.info = data, entries, info
+        self._names = None
+
+    @property
+    def n_entries(self):
+        return int(self.entries.shape[0])
+
+    def _word(self, k):
+        return self.entries.view(torch.int32)[:, k]
+
+    @property
+    def csize(self):
+        return self._word(4)
+
+    @property
+    def usize(self):
+        return self._word(5)
+
+    @property
+    def crc32(self):
+        return self._word(6)
+
+    @property
+    def status(self):
+        """int32 [n]: 0 = readable, else the ZE_* reason the directory gives"""
+        return self._word(11)
+
+    @property
+    def readable(self):
+        return self.status == 0
+
+    def names(self):
+        """The names, decoded as UTF-8 where general-purpose bit 11 is set and as cp437 elsewhere: one device-to-host copy of the
+        directory's bytes and one of the table."""
+        if self._names is None:
+            n = self.n_entries
+            if n == 0:
+                self._names = []
+                return self._names
+            lo = int(self.info["base"] + self.info["cd_off"])
+            cd = self.data[lo:lo + int(self.info["cd_size"])].cpu().numpy().tobytes()
+            host = self.entries.cpu().numpy()
+            name_off = host[:, 8:16].copy().view("<u8")[:, 0]
+            flags = host[:, 38:40].copy().view("<u2")[:, 0]
+            name_len = host[:, 40:42].copy().view("<u2")[:, 0]
+            self._names = [cd[int(o) - lo:int(o) - lo + int(l)].decode("utf-8" if f & 0x800 else "cp437")
+                           for o, l, f in zip(name_off, name_len, flags)]
+        return self._names
+
+    def index(self, name):
+        """the index of the LAST entry of that name (the one zipfile's getinfo returns); KeyError if there is none"""
+        names = self.names()
+        for k in range(len(names) - 1, -1, -1):
+            if names[k] == name:
+                return k
+        raise KeyError(name)
 
 
 class Engine:
@@ -749,6 +817,92 @@ class Engine:
             self.inflate_batch(data, offsets, lengths, out, out_offsets, sizes, wrap=wrap, out_len=out_len, status=status,
                                zdict=zdict if zdict is not None and zdict.numel() else None, in_used=in_used, detail=detail)
         return out, out_offsets, out_len, status
+
+    # ---- ZIP archives ----
+    def _zip_data(self, data):
+        if isinstance(data, torch.Tensor):
+            if data.dtype != torch.uint8 or data.device != self.device or not data.is_contiguous():
+                raise ValueError("data must be a contiguous uint8 tensor on %s" % (self.device,))
+            return data
+        import numpy as np
+        host = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data).view(np.uint8)
+        return torch.from_numpy(host.reshape(-1).copy()).to(self.device)
+
+    def zip_directory(self, data, cap=None):
+        """The directory of the ZIP archive `data` (a uint8 device tensor, or bytes / numpy, which are uploaded) -> ZipDirectory.  cap:
+        entries to make room for; the default, min((len - 22) // 76, 65536), holds any archive of up to 65 536 entries (an entry costs at
+        least 30 + 46 bytes), and a larger archive is listed again with the count the first call reports.  One synchronisation per call:
+        reading zmi_zip_info.  An archive the call refuses (ZA_*) raises; flagged entries (ZE_*) are listed and do not."""
+        data = self._zip_data(data)
+        n = int(data.numel())
+        grow = cap is None
+        if grow:
+            cap = min(max(0, (n - 22) // 76), 65536)
+        while True:
+            entries = torch.empty((cap, ZIP_ENTRY_BYTES), dtype=torch.uint8, device=self.device)
+            meta = torch.zeros(6, dtype=torch.int64, device=self.device)
+            _lib.check(self.L.zmi_zip_directory_dev(self._ctx, data.data_ptr() if n else None, n, entries.data_ptr() if cap else None, int(cap),
+                                                    meta.data_ptr(), _stream_ptr()), "zmi_zip_directory_dev")
+            n_entries, n_listed, cd_off, cd_size, base, sd = meta.tolist()
+            st = sd & 0xFFFFFFFF
+            info = {"n_entries": n_entries, "n_listed": n_listed, "cd_off": cd_off, "cd_size": cd_size, "base": base,
+                    "status": st - (1 << 32) if st >= 1 << 31 else st, "detail": (sd >> 32) & 0xFFFFFFFF}
+            if info["status"] != 0:
+                raise RuntimeError("zmi_zip_directory_dev: status %d (case %d, index %d)" % (info["status"], info["detail"] & 0xFF,
+                                                                                             info["detail"] >> 8))
+            if n_entries <= cap or not grow:
+                return ZipDirectory(data, entries[:n_listed], info)
+            cap = n_entries
+
+    def zip_read(self, data, directory=None, names=None, indices=None, align=1, out=None):
+        """Entries of a ZIP archive, inflated (or copied, where stored) densely into one buffer and checked against the directory's
+        lengths and CRC-32s -> (out, out_off int64 [n_sel + 1], out_len int32 [n_sel], status int32 [n_sel]).  Slot j stands at
+        out[out_off[j] : out_off[j] + out_len[j]]; out_off[-1] is the room the selection needs.  names or indices (a list or an int32
+        device tensor) select; neither: every listed entry.  status 0: length and CRC-32 match; every other status (Z_DATA_ERROR,
+        Z_BUF_ERROR where `out` was too small, Z_VERSION_ERROR for an entry the directory flagged) has length 0 -- nothing is raised for
+        an entry.  last_zip_detail keeps the ZE_* tensor.  out=None allocates the sum of the selected usize and reads ONE word,
+        out_off[-1], to check the guess (it is exact unless a selected entry is flagged)."""
+        data = self._zip_data(data)
+        d = directory if directory is not None else self.zip_directory(data)
+        if align < 1 or align > 4096 or align & (align - 1):
+            raise ValueError("align must be a power of two, 1 .. 4096")
+        if names is not None:
+            indices = [d.index(nm) for nm in names]
+        sel = None
+        if indices is not None:
+            sel = indices if isinstance(indices, torch.Tensor) else torch.tensor(list(indices), dtype=torch.int32, device=self.device)
+            sel = sel.to(device=self.device, dtype=torch.int32).contiguous()
+        n_sel = int(sel.numel()) if sel is not None else d.n_entries
+        out_off = torch.zeros(n_sel + 1, dtype=torch.int64, device=self.device)
+        out_len = torch.zeros(n_sel, dtype=torch.int32, device=self.device)
+        status = torch.zeros(n_sel, dtype=torch.int32, device=self.device)
+        detail = torch.zeros(n_sel, dtype=torch.int32, device=self.device)
+        self.last_zip_detail = detail
+
+        def call(buf):
+            _lib.check(self.L.zmi_zip_inflate_dev(self._ctx, data.data_ptr() if data.numel() else None, int(data.numel()),
+                                                  d.entries.data_ptr() if d.n_entries else None, d.n_entries,
+                                                  sel.data_ptr() if sel is not None and n_sel else None, n_sel, int(align),
+                                                  buf.data_ptr() if buf.numel() else None, int(buf.numel()), out_off.data_ptr(),
+                                                  out_len.data_ptr(), status.data_ptr(), detail.data_ptr(), _stream_ptr()),
+                       "zmi_zip_inflate_dev")
+
+        if out is not None:
+            call(out)
+            return out, out_off, out_len, status
+        if n_sel == 0:
+            return torch.empty(0, dtype=torch.uint8, device=self.device), out_off, out_len, status
+        usize = d.usize.to(torch.int64) & 0xFFFFFFFF
+        if sel is not None:
+            usize = usize[sel.to(torch.int64).clamp(0, max(0, d.n_entries - 1))] if d.n_entries else usize[:0]
+        guess = int((((usize + (align - 1)) // align) * align).sum().item())
+        out = torch.empty(guess, dtype=torch.uint8, device=self.device)
+        call(out)
+        need = int(out_off[n_sel].item())
+        if need > guess:      # (cannot happen: flagged entries and bad indices take no room)
+            out = torch.empty(need, dtype=torch.uint8, device=self.device)
+            call(out)
+        return out[:need], out_off, out_len, status
 
     # ---- checksums ----
     def checksums(self, data, offsets, lengths, adler=True, crc=True, out_adler=None, out_crc=None):

@@ -598,7 +598,7 @@ int zmi_bgzf_deflate_dev(zmi_ctx* ctx, const void* d_in, uint64_t n, uint32_t bl
  * central directory at its end -- the input shape of zmi_inflate_batch_dev_ex, which checks nothing on a raw stream.  Two calls, both
  * asynchronous on `stream`, neither synchronises with the host, every result is a device word.  Positions are 64-bit, d_in may stand at
  * any alignment.  Not read: encrypted entries, methods other than 0 and 8, multi-disk archives, entries of 4 GiB or more (the batch
- * decoder's lengths are uint32_t) -- they are listed and flagged.
+ * decoder's lengths are uint32_t) -- they are listed and flagged.  The archives themselves are made by zmi_zip_write_dev, below.
  *
  * zmi_zip_directory_dev   d_in[0 .. in_len) is the whole file.
  *   End record  the HIGHEST offset p in [max(0, in_len - 65557), in_len - 22] with in[p .. p + 4) = 50 4b 05 06 AND
@@ -687,6 +687,74 @@ int zmi_zip_directory_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, zmi_z
 int zmi_zip_inflate_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, const zmi_zip_entry* d_entries, uint32_t n_entries,
                         const uint32_t* d_sel, uint32_t n_sel, uint32_t out_align, void* d_out, uint64_t out_cap,
                         uint64_t* d_out_off /* n_sel + 1 */, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, void* stream);
+
+/* ---- writing ZIP archives: entries from device memory into a .zip / .npz / .whl / .jar, directory and ZIP64 forms included -------------
+ * Entry i = d_in[d_in_off[i] .. + d_in_len[i]), any layout; its name = d_names[d_name_off[i] .. d_name_off[i + 1]), bytes the caller promises
+ * to be UTF-8 (nothing validates them).  d_out[0] stands at file position `base` -- the bytes already written in front, a self-extractor
+ * stub -- and every position written INTO the archive is absolute, base + its place in d_out: local-header offsets, the directory offset,
+ * the ZIP64 record's offset in the locator (the form zmi_zip_directory_dev computes a base of 0 for).  Every byte is fixed:
+ *   local header    50 4b 03 04 | need u16 | flags u16 | method u16 | time u16 | date u16 | crc32 | csize u32 | usize u32 | name_len u16 |
+ *                   00 00 | name           (30 + name bytes, never an extra field; sizes and CRC-32 stand here: no data descriptor, bit 3
+ *                   clear).  method 8 / need 20 at levels 1 .. 9, method 0 / need 10 at level 0 for EVERY entry: the payload is then
+ *                   the raw bytes (a stored entry, not deflate stored blocks; the encoder does not run).  flags = 0x0800 where the
+ *                   name holds a byte >= 0x80, else 0.  No per-entry fallback to method 0 at levels 1 .. 9 (incompressible data has
+ *                   csize > usize); an empty entry there is 03 00, csize 2 -- both as Python's zipfile does.
+ *   payload         levels 1 .. 9: the entry is cut into pieces of piece_bytes (the last may be shorter), each compressed as an independent
+ *                   piece of ONE raw stream, as zmi_deflate_pieces_dev(ZMI_STREAM_INDEPENDENT) does with max_len = piece_bytes: every
+ *                   piece but the entry's last ends with the flush marker, the last ends the stream.  An entry's bytes are a function
+ *                   of (its bytes, piece_bytes, level, strategy) alone -- not of n_entries, its index, the alignment, the scratch limit,
+ *                   in_bytes or the launch grouping.  (Pieces are independent: smaller piece_bytes costs ratio, as documented for
+ *                   zmi_deflate_stream_dev; and a piece_bytes shard is encoded in up to 16 regions, so entries far smaller than
+ *                   piece_bytes pay for a large piece_bytes too -- choose it near the typical entry when the entries are small.)
+ *   central record  50 4b 01 02 | made_by u16 = 0x0300 | need | need u16 | flags | method | time | date | crc32 | csize | usize | name_len |
+ *                   extra_len u16 | comment_len 0 | disk 0 | int_attr 0 | ext_attr u32 | offset u32 | name [| 01 00 08 00 | offset u64]
+ *                   (46 + name (+ 12) bytes).  Where the absolute local-header offset is >= 0xFFFFFFFF the field is all ones, the 12-byte
+ *                   ZIP64 extra carries the offset and need is 45 (in this record; the local header keeps 20 / 10).  Sizes never need
+ *                   the extra: see ZMI_ZIP_ENTRY_MAX.
+ *   end             the ZIP64 form where n_entries >= 0xFFFF, or the directory's size >= 0xFFFFFFFF, or its absolute offset >= 0xFFFFFFFF:
+ *                   50 4b 06 06 | 44 u64 | 0x032D u16 | 45 u16 | 0 u32 | 0 u32 | n u64 | n u64 | cd_size u64 | cd_off u64   (56 bytes), then
+ *                   50 4b 06 07 | 0 u32 | that record's offset u64 | 1 u32                                                  (20 bytes);
+ *                   then always 50 4b 05 06 | 0 u16 | 0 u16 | min(n, 0xFFFF) u16 x 2 | min(cd_size, 0xFFFFFFFF) u32 |
+ *                   min(cd_off, 0xFFFFFFFF) u32 | 00 00 (22 bytes).  No comments anywhere.
+ *   d_dos_time      one uint32_t per entry, date << 16 | time as in zmi_zip_entry; NULL: 0x00210000 (1980-01-01 00:00:00), which gives
+ *                   reproducible archives.  d_ext_attr: one uint32_t per entry; NULL: 0x81A40000 (a regular file, 0644).
+ *
+ * zmi_zip_bound       room that always suffices for n_entries entries whose names are names_bytes and whose data is in_bytes in all
+ *                     (not tight); piece_bytes 0: 0.
+ * zmi_zip_write_dev   asynchronous on `stream`, never synchronises with the host, every result is a device word.
+ *   Arguments   piece_bytes 1 .. 2^30, level -1 .. 9, strategy 0 .. 4, n_entries <= 2^31 - 1, otherwise ZMI_E_ARG as the return value.
+ *               in_bytes is the caller's bound on the sum of d_in_len, normally the size of the buffer the entries lie in: it sizes the
+ *               piece table, n_entries + in_bytes / piece_bytes places (more than 2^31 - 1: ZMI_E_ARG) -- the host cannot know the
+ *               true count, the lengths live on the device.  A larger sum is ZMI_E_ARG in *d_status and no entry is written: the
+ *               result is the 22-byte empty archive.
+ *   Per entry   (the tables are device data) a length above ZMI_ZIP_ENTRY_MAX becomes an empty entry, a name longer than 65 535 bytes is
+ *               cut to its first 65 535, either with ZMI_E_ARG in *d_status.  Every piece adds a flush marker and a block header to
+ *               its entry, so hundreds of MB of incompressible bytes cut into pieces of a few bytes can pass 2^32 compressed bytes:
+ *               such an entry is ZMI_E_ARG in *d_status too, its size fields are all ones and the archive is not a valid one.
+ *               *d_status is otherwise 0, or the first encoder status.
+ *   Capacity    an archive longer than out_cap: *d_status = Z_BUF_ERROR (-5; behind an earlier status that one stays).  *d_out_len is
+ *               always the archive's length -- the room it needs when it does not fit.  Payloads and records (a local header with
+ *               its name, a central record, each of the three end records) that end at or before out_cap are right, one that crosses
+ *               it is not written, nothing at or behind d_out + out_cap is.
+ *   d_entries   NULL, or n_entries rows: the table zmi_zip_directory_dev would list for the finished archive -- every field, name_off
+ *               pointing into the written directory, status 0; positions are places in d_out.  d_info: NULL, or the matching
+ *               zmi_zip_info, with cd_off the directory's place in d_out and base 0 (at base 0 exactly what the reader reports).
+ *   n_entries 0 gives the 22-byte empty archive.
+ *   Launch groups as in zmi_deflate_stream_dev: a group's slots and match scratch stay within the scratch limit, the running offset
+ *   stays in a device word, an entry may lie across groups; the bytes do not depend on the grouping.  A slot holds one piece of
+ *   min(piece_bytes, in_bytes) bytes, so one large entry beside many small ones costs slots of piece_bytes, not of the entry.
+ *   Event timing: 0 = CRC-32 (pieces, then the fold per entry), 1 / 5 / 2 = match search, parse, encode, 7 = layout, sizes, scans,
+ *   pack, headers, directory and close.
+ *   Scratch of the context: 36 bytes per entry, 40 bytes and 1 bit per place of the piece table, and one group's slots of
+ *   zmi_deflate_pieces_stride(min(piece_bytes, in_bytes)) bytes each (pieces below ~17 KiB under a piece_bytes above 64 KiB: up to
+ *   2.2 KiB more, the room of that geometry's regions). */
+#define ZMI_ZIP_ENTRY_MAX 0xF0000000u   /* most bytes per entry: the encoder's worst case of it (stored blocks) still fits 32 bits */
+uint64_t zmi_zip_bound(uint32_t n_entries, uint64_t names_bytes, uint64_t in_bytes, uint32_t piece_bytes, int level);
+int zmi_zip_write_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_entries,
+                      uint64_t in_bytes, const void* d_names, const uint64_t* d_name_off /* n_entries + 1 */,
+                      const uint32_t* d_dos_time /* NULL */, const uint32_t* d_ext_attr /* NULL */, uint32_t piece_bytes, int level,
+                      int strategy, uint64_t base, void* d_out, uint64_t out_cap, uint64_t* d_out_len,
+                      zmi_zip_entry* d_entries /* NULL or n_entries */, zmi_zip_info* d_info /* NULL */, int32_t* d_status, void* stream);
 
 /* ---- host-buffer convenience wrappers: copy in, run the batch on the GPU, copy back ---- */
 int zmi_deflate_batch(zmi_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_shards,

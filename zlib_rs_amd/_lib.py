@@ -76,6 +76,10 @@ def lib():
     L.zmi_zip_walk_tile.argtypes = []
     L.zmi_zip_directory_dev.argtypes = [vp, vp, u64, vp, u32, vp, vp]
     L.zmi_zip_inflate_dev.argtypes = [vp, vp, u64, vp, u32, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp]
+    # writing ZIP archives: entries, directory, ZIP64 (csrc/pack.hip, checksum.hip, zmi_api.hip)
+    L.zmi_zip_bound.restype = u64
+    L.zmi_zip_bound.argtypes = [u32, u64, u64, u32, i32]
+    L.zmi_zip_write_dev.argtypes = [vp, vp, vp, vp, u32, u64, vp, vp, vp, vp, u32, i32, i32, u64, vp, u64, vp, vp, vp, vp, vp]
     # the multi-GPU stitch (csrc/exchange.hip); RCCL itself is loaded by the library on first use
     L.zmi_comm_unique_id.argtypes = [vp]
     L.zmi_comm_create.argtypes = [C.POINTER(vp), vp, i32, i32, vp]

@@ -363,3 +363,60 @@ extern "C" int zmi_launch_checksum_combine(const uint32_t* d_check, const uint32
                (const uint64_t*)d_pl, nb, 1u, nb, nb, adler, d_out_check, d_out_len);
     return 0;
 }
+
+// ---- the CRC-32 of every entry of a piece table (zmi_zip_write_dev) ----------------------------------------------------------------------
+// Segment e < *n_live (a device word, at most the n the launch covers) is the pieces [first[e], first[e + 1]) of the (check, len)
+// tables; out[e] = their fold, a copy of the word where the segment
+// is one piece.  One thread per segment folds up to ZMI_SEG_SERIAL pieces in order -- an archive of small files is all such segments,
+// and a wave per segment would be 64 lanes for one multiplication.  A longer segment (a 1 GiB entry in 1 MiB pieces: 1024 dependent
+// combines, ~0.1 ms on one lane) is folded by the whole wave afterwards, one such segment at a time: every lane a run of consecutive
+// pieces, then the ordered butterfly of zmi_combine_kernel.
+#define ZMI_SEG_SERIAL 64u
+__global__ void __launch_bounds__(256) zmi_combine_segments_kernel(const uint32_t* __restrict__ check, const uint32_t* __restrict__ len,
+                                                                  const uint64_t* __restrict__ first, const uint32_t* __restrict__ n_live,
+                                                                  uint32_t* __restrict__ out) {
+    __shared__ uint32_t pw[64];
+    const uint32_t t = threadIdx.x;
+    if (t < 64u) pw[t] = kXpowTab.v[t];
+    __syncthreads();
+    const uint64_t gi = (uint64_t)blockIdx.x * 256u + t;
+    const bool live = gi < *n_live;
+    const uint64_t p0 = live ? first[gi] : 0ull, cnt = live ? first[gi + 1u] - p0 : 0ull;
+    if (live && cnt <= ZMI_SEG_SERIAL) {
+        uint32_t c = 0;
+        uint64_t l = 0;
+        for (uint64_t p = p0; p < p0 + cnt; ++p) zmi_combine_pair(false, pw, c, l, check[p], (uint64_t)len[p]);
+        out[gi] = c;
+    }
+    const uint32_t lane = zmi_lane();
+    for (uint64_t big = __ballot(cnt > ZMI_SEG_SERIAL); big; big &= big - 1u) {   // (the same trips in every lane of the wave)
+        const int src = __ffsll((unsigned long long)big) - 1;
+        const uint64_t q0 = ((uint64_t)__shfl((uint32_t)(p0 >> 32), src) << 32) | __shfl((uint32_t)p0, src);
+        const uint64_t qn = ((uint64_t)__shfl((uint32_t)(cnt >> 32), src) << 32) | __shfl((uint32_t)cnt, src);
+        const uint64_t per = (qn + 63u) / 64u;
+        uint32_t c = 0;
+        uint64_t l = 0;
+        for (uint64_t p = lane * per; p < (lane + 1u) * per && p < qn; ++p) zmi_combine_pair(false, pw, c, l, check[q0 + p], (uint64_t)len[q0 + p]);
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t oc = __shfl_xor(c, (int)d);
+            const uint32_t olo = __shfl_xor((uint32_t)l, (int)d), ohi = __shfl_xor((uint32_t)(l >> 32), (int)d);
+            const uint64_t ol = ((uint64_t)ohi << 32) | olo;
+            if (lane & d) {
+                uint32_t c2 = oc;
+                uint64_t l2 = ol;
+                zmi_combine_pair(false, pw, c2, l2, c, l);
+                c = c2;
+                l = l2;
+            } else {
+                zmi_combine_pair(false, pw, c, l, oc, ol);
+            }
+        }
+        if (lane == 0u) out[gi - lane + (uint32_t)src] = c;   // (lane 0's gi is the wave's first segment)
+    }
+}
+extern "C" int zmi_launch_combine_segments(const uint32_t* d_check, const uint32_t* d_len, const uint64_t* d_first, uint32_t n,
+                                           const uint32_t* d_n_live, uint32_t* d_out, hipStream_t stream) {
+    if (n == 0) return 0;
+    ZMI_LAUNCH(zmi_combine_segments_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_check, d_len, d_first, d_n_live, d_out);
+    return 0;
+}

@@ -841,7 +841,9 @@ __global__ void __launch_bounds__(64) ENC_OCC zmi_encode_kernel_t(const uint8_t*
     if (pend > n) pend = n;
     const bool is_first = piece == 0u;
     // the piece that ends the deflate stream (BFINAL + trailer); in chained mode only the last shard's
-    const bool ends_stream = prm.chain_mode == 0u || (prm.chain_mode == 1u && s == prm.last_shard);
+    // (chain mode 2 with a bitmap: the shards whose bit is set -- the pieces of many streams in one table, zmi_zip_write_dev)
+    const bool ends_stream = prm.chain_mode == 0u || (prm.chain_mode == 1u && s == prm.last_shard) ||
+                             (prm.chain_mode == 2u && prm.ends && ((prm.ends[s >> 5] >> (s & 31u)) & 1u));
     const bool is_last = piece + 1u == npieces && ends_stream;
     if (piece >= npieces) {
         if (lane == 0) piece_len[(uint64_t)s * pieces + piece] = 0u;

@@ -888,3 +888,303 @@ extern "C" int zmi_launch_zip_verify(const zmi_zip_entry* d_entries, uint32_t n_
                out_cap, d_used, d_crc, d_out_len, d_status, d_detail);
     return 0;
 }
+
+// ---- writing ZIP archives (zmi_zip_write_dev; every byte of the format: include/zmi355.h) ----------------------------
+// An entry is cut into pieces of piece_bytes, the pieces of all entries form ONE table the independent-piece encoder works through in
+// launch groups (a piece that is its entry's last ends a stream: the bitmap of chain mode 2, encode.hip); a piece's place in the
+// archive is its compressed size, plus the hole of 30 + name bytes in front of an entry's first piece.  layout / pieces make the table,
+// sizes / pack place and copy one group behind the device word the group before ended at, headers fills the holes and writes the
+// directory once every offset is known, close writes the end structure.
+#define ZW_E_ARG (-103)        // ZMI_E_ARG, in the call's status word
+#define ZW_VOID 0xFFFFFFFFu    // head[] of a piece behind the true piece count
+#define ZW_G 16u               // threads that share an entry in the headers kernel
+#define ZW_LOC 30u
+
+// per entry: the checked length (above ZMI_ZIP_ENTRY_MAX: empty, ZMI_E_ARG), the checked name length (cut at 65 535, ZMI_E_ARG) and
+// the piece count max(1, ceil(len / piece_bytes)).  *sum (zeroed by the caller) receives the sum of the checked lengths, one atomic per
+// wave, for the in_bytes check of the pieces kernel.
+__global__ void __launch_bounds__(256) zmi_zip_layout_kernel(const uint32_t* __restrict__ in_len, const uint64_t* __restrict__ name_off, uint32_t n,
+                                                             uint32_t piece_bytes, uint32_t* __restrict__ elen, uint32_t* __restrict__ nlen,
+                                                             uint32_t* __restrict__ npc, unsigned long long* sum, int32_t* status) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    uint32_t l = 0u;                                     // (no early return: the wave's lanes meet in the shuffles below)
+    if (i < n) {
+        l = in_len[i];
+        uint64_t nl = name_off[i + 1u] - name_off[i];
+        if (l > ZMI_ZIP_ENTRY_MAX) { l = 0u; atomicCAS(status, 0, ZW_E_ARG); }
+        if (nl > 65535ull) { nl = 65535ull; atomicCAS(status, 0, ZW_E_ARG); }
+        elen[i] = l;
+        nlen[i] = (uint32_t)nl;
+        npc[i] = l ? (uint32_t)(((uint64_t)l + piece_bytes - 1u) / piece_bytes) : 1u;
+    }
+    unsigned long long w = l;
+    for (uint32_t d = 1u; d < 64u; d <<= 1) w += __shfl_xor(w, (int)d);
+    if ((threadIdx.x & 63u) == 0u && w) atomicAdd(sum, w);
+}
+
+// per piece of the table's `cap` places: first[] (the scan of the piece counts, n + 1 entries) names its entry, by bisection; piece k of
+// an entry is [k * piece_bytes, + min(piece_bytes, len - k * piece_bytes)) of it.  head[i] = 30 + name bytes where it is its entry's
+// first, 0 elsewhere, ZW_VOID behind the true count first[n].  The bit of an entry's last piece is set in `ends` (zeroed by the caller),
+// which holds `wpg` words for every launch group of `group` pieces, so that every group's bits start at a word.  *sum > in_bytes -- the
+// caller's bound on the lengths does not hold, the table may not have room for the pieces -- makes every piece void and the archive
+// an empty one: *n_eff = 0, else n.
+__global__ void __launch_bounds__(256) zmi_zip_pieces_kernel(const uint64_t* __restrict__ in_off, const uint32_t* __restrict__ elen,
+                                                             const uint32_t* __restrict__ nlen, const uint64_t* __restrict__ first,
+                                                             const unsigned long long* __restrict__ sum, uint32_t n, uint64_t in_bytes,
+                                                             uint32_t piece_bytes, uint32_t cap, uint32_t group, uint32_t wpg,
+                                                             uint64_t* __restrict__ p_off, uint32_t* __restrict__ p_len,
+                                                             uint32_t* __restrict__ head, uint32_t* ends, uint32_t* __restrict__ n_eff,
+                                                             int32_t* status) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool bad = *sum > in_bytes;
+    if (i == 0u) {
+        *n_eff = bad ? 0u : n;
+        if (bad) atomicCAS(status, 0, ZW_E_ARG);
+    }
+    if (i >= cap) return;
+    if (bad || (uint64_t)i >= first[n]) { p_off[i] = 0ull; p_len[i] = 0u; head[i] = ZW_VOID; return; }
+    uint32_t lo = 0u, hi = n;                   // first[lo] <= i < first[hi]
+    while (hi - lo > 1u) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (first[mid] <= (uint64_t)i) lo = mid; else hi = mid;
+    }
+    const uint32_t k = i - (uint32_t)first[lo], l = elen[lo];
+    const uint64_t o = (uint64_t)k * piece_bytes;
+    p_off[i] = in_off[lo] + o;
+    p_len[i] = l - o < piece_bytes ? (uint32_t)(l - o) : piece_bytes;
+    head[i] = k == 0u ? ZW_LOC + nlen[lo] : 0u;
+    if ((uint64_t)i + 1u == first[lo + 1u]) {
+        const uint32_t j = i % group;
+        atomicOr(&ends[(uint64_t)(i / group) * wpg + (j >> 5)], 1u << (j & 31u));
+    }
+}
+
+// size[i] = the piece's place in the archive: its payload (the encoder's olen; at level 0 the caller passes the raw lengths and no
+// statuses) plus the hole in front of an entry's first piece; 0 for a void piece.  The first encoder status lands in *status.
+__global__ void __launch_bounds__(256) zmi_zip_sizes_kernel(const uint32_t* __restrict__ head, const uint32_t* __restrict__ olen,
+                                                            const int32_t* __restrict__ st, uint32_t n, uint32_t* __restrict__ size, int32_t* status) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t h = head[i];
+    if (h == ZW_VOID) { size[i] = 0u; return; }
+    size[i] = h + olen[i];
+    if (st && st[i] != 0) atomicCAS(status, 0, st[i]);
+}
+
+// n * split jobs as in zmi_copy_ranges_kernel: the payload of piece b / split goes behind its hole, from its slot or (slots NULL:
+// level 0) from the raw input.  The holes are left alone; a payload that crosses out_cap is not written at all.
+__global__ void __launch_bounds__(PK_T) zmi_zip_pack_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ p_off,
+                                                            const uint32_t* __restrict__ head, const uint8_t* __restrict__ slots,
+                                                            uint64_t slot_stride, const uint32_t* __restrict__ olen, uint8_t* __restrict__ out,
+                                                            const uint64_t* __restrict__ pos, uint64_t out_cap, uint32_t split, uint32_t jobs) {
+    __shared__ __attribute__((aligned(16))) uint8_t stage[PK_TILE + 32];
+    const uint32_t t = threadIdx.x;
+  for (uint32_t job = blockIdx.x; job < jobs; job += gridDim.x) {
+    const uint32_t r = job / split, part = job % split;
+    const uint32_t h = head[r];
+    if (h == ZW_VOID) continue;
+    const uint32_t l = olen[r];
+    const uint64_t d0 = pos[r] + h;
+    if (d0 + l > out_cap) continue;   // does not fit: the call's status says so
+    pk_copy_tiles(stage, slots ? slots + (uint64_t)r * slot_stride : in + p_off[r], l, out, d0, part, split, t);
+  }
+}
+
+// what the local header and the central record of entry e say
+struct zw_entry {
+    uint64_t lho, data_off, abs_off;   // the local header and the first payload byte in d_out; base + lho
+    uint32_t nl, csize, usize, crc, dos, ext;
+    bool sat;                          // abs_off does not fit the 32-bit field: the ZIP64 extra carries it
+    bool big;                          // the compressed size does not fit its 32-bit field (csize is then all ones): ZMI_E_ARG
+};
+static __device__ __forceinline__ zw_entry zw_entry_of(uint32_t e, const uint32_t* __restrict__ elen, const uint32_t* __restrict__ nlen,
+                                                       const uint64_t* __restrict__ first, const uint64_t* __restrict__ pos,
+                                                       const uint32_t* __restrict__ crc, const uint32_t* __restrict__ dos_time,
+                                                       const uint32_t* __restrict__ ext_attr, uint64_t base) {
+    zw_entry z;
+    z.nl = nlen[e];
+    z.lho = pos[first[e]];
+    z.data_off = z.lho + ZW_LOC + z.nl;
+    const uint64_t cs = pos[first[e + 1u]] - z.data_off;
+    z.big = cs >= 0xFFFFFFFFull;       // (only pieces of a few bytes get there: every piece adds its flush marker and block header)
+    z.csize = z.big ? 0xFFFFFFFFu : (uint32_t)cs;
+    z.usize = elen[e];
+    z.crc = crc[e];
+    z.dos = dos_time ? dos_time[e] : 0x00210000u;
+    z.ext = ext_attr ? ext_attr[e] : 0x81A40000u;
+    z.abs_off = base + z.lho;
+    z.sat = z.abs_off >= 0xFFFFFFFFull;
+    return z;
+}
+// byte k of a record given as little-endian 64-bit words
+static __device__ __forceinline__ uint8_t zw_byte(const uint64_t* w, uint32_t k) { return (uint8_t)(w[k >> 3] >> (8u * (k & 7u))); }
+
+// ZW_G threads per entry, behind the last group.  pass 0: the local header and the name into the entry's hole, and the size of its
+// central record (46 + name + the 12 bytes of the ZIP64 extra where base + offset needs them; 0 for the entries of a call whose
+// in_bytes check failed) for the scan that places the directory.  pass 1: the central record at cen_off[e] and the row of d_entries.
+// An entry whose compressed size does not fit 32 bits puts ZMI_E_ARG into *status (pass 0), its size fields are all ones.
+// Either copies the name from the caller's blob -- the threads of the entry take its bytes in turn and learn on the way whether one
+// is >= 0x80 (general-purpose bit 11) -- and writes the fixed bytes one per thread and round.  A record that crosses out_cap is not
+// written.
+__global__ void __launch_bounds__(256) zmi_zip_headers_kernel(const uint32_t* __restrict__ elen, const uint32_t* __restrict__ nlen,
+                                                              const uint64_t* __restrict__ first, const uint64_t* __restrict__ pos,
+                                                              const uint32_t* __restrict__ crc, const uint8_t* __restrict__ names,
+                                                              const uint64_t* __restrict__ name_off, const uint32_t* __restrict__ dos_time,
+                                                              const uint32_t* __restrict__ ext_attr, uint32_t n, const uint32_t* __restrict__ n_eff,
+                                                              uint32_t method, uint64_t base, uint8_t* __restrict__ out, uint64_t out_cap,
+                                                              uint32_t* __restrict__ cen_size, const uint64_t* __restrict__ cen_off,
+                                                              zmi_zip_entry* __restrict__ ent, uint32_t pass, int32_t* status) {
+    const uint64_t gi = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    const uint32_t g = (uint32_t)(gi % ZW_G);
+    const bool live = gi / ZW_G < (uint64_t)n;           // (no early return: the group's threads meet in the shuffles below)
+    const uint32_t e = live ? (uint32_t)(gi / ZW_G) : 0u;
+    const bool listed = live && e < *n_eff;
+    if (live && !listed && pass == 0u && g == 0u) cen_size[e] = 0u;
+    zw_entry z = {};
+    if (listed) z = zw_entry_of(e, elen, nlen, first, pos, crc, dos_time, ext_attr, base);
+    const uint32_t cen = ZIP_CEN + z.nl + (z.sat ? 12u : 0u);
+    const uint64_t at = pass == 0u ? z.lho : (listed ? cen_off[e] : 0ull);
+    const bool fits = listed && at + (pass == 0u ? ZW_LOC + z.nl : cen) <= out_cap;
+    const uint8_t* nm = names + (listed ? name_off[e] : 0ull);
+    uint8_t* nd = out + at + (pass == 0u ? ZW_LOC : ZIP_CEN);
+    uint32_t hi = 0u;
+    if (listed)
+        for (uint32_t k = g; k < z.nl; k += ZW_G) {
+            const uint8_t b = nm[k];
+            hi |= b;
+            if (fits) nd[k] = b;
+        }
+    for (uint32_t d = 1u; d < ZW_G; d <<= 1) hi |= __shfl_xor(hi, (int)d);
+    if (!listed) return;
+    const uint64_t flags = hi & 0x80u ? 0x0800u : 0u;
+    const uint64_t need = z.sat && pass == 1u ? 45u : (method ? 20u : 10u);
+    const uint64_t time = z.dos & 0xFFFFu, date = z.dos >> 16;
+    if (pass == 0u) {
+        if (g == 0u) cen_size[e] = cen;
+        if (g == 0u && z.big) atomicCAS(status, 0, ZW_E_ARG);
+        if (!fits) return;
+        const uint64_t w[4] = {0x04034B50ull | need << 32 | flags << 48,
+                               (uint64_t)method | time << 16 | date << 32 | (uint64_t)(z.crc & 0xFFFFu) << 48,
+                               (uint64_t)(z.crc >> 16) | (uint64_t)z.csize << 16 | (uint64_t)(z.usize & 0xFFFFu) << 48,
+                               (uint64_t)(z.usize >> 16) | (uint64_t)z.nl << 16};
+        for (uint32_t k = g; k < ZW_LOC; k += ZW_G) out[at + k] = zw_byte(w, k);
+        return;
+    }
+    if (g == 0u && ent) {
+        zmi_zip_entry r;
+        r.data_off = z.data_off;
+        r.name_off = at + ZIP_CEN;
+        r.csize = z.csize;
+        r.usize = z.usize;
+        r.crc32 = z.crc;
+        r.dos_time = z.dos;
+        r.ext_attr = z.ext;
+        r.method = (uint16_t)method;
+        r.flags = (uint16_t)flags;
+        r.name_len = (uint16_t)z.nl;
+        r.reserved = 0;
+        r.status = 0;
+        ent[e] = r;
+    }
+    if (!fits) return;
+    const uint64_t off32 = z.sat ? 0xFFFFFFFFull : z.abs_off;
+    const uint64_t w[6] = {0x02014B50ull | (0x0300ull | need) << 32 | need << 48,
+                           flags | (uint64_t)method << 16 | time << 32 | date << 48,
+                           (uint64_t)z.crc | (uint64_t)z.csize << 32,
+                           (uint64_t)z.usize | (uint64_t)z.nl << 32 | (z.sat ? 12ull : 0ull) << 48,
+                           (uint64_t)(z.ext & 0xFFFFu) << 48,
+                           (uint64_t)(z.ext >> 16) | off32 << 16};
+    for (uint32_t k = g; k < ZIP_CEN; k += ZW_G) out[at + k] = zw_byte(w, k);
+    if (z.sat && g < 12u) {
+        const uint64_t x[2] = {0x00080001ull | z.abs_off << 32, z.abs_off >> 32};
+        out[at + ZIP_CEN + z.nl + g] = zw_byte(x, g);
+    }
+}
+
+// One thread: the end structure behind the directory [*pay_end, *cd_end) -- the ZIP64 record and its locator where the count, the
+// directory's size or its absolute offset saturates a field, then the end record, each written where it ends at or before out_cap --,
+// *out_len, d_info, and Z_BUF_ERROR for an archive that does not fit.
+__global__ void zmi_zip_close_kernel(uint8_t* __restrict__ out, uint64_t out_cap, const uint64_t* __restrict__ pay_end,
+                                     const uint64_t* __restrict__ cd_end, const uint32_t* __restrict__ n_eff, uint64_t base,
+                                     uint64_t* __restrict__ out_len, zmi_zip_info* __restrict__ info, int32_t* status) {
+    const uint64_t dir = *pay_end, end = *cd_end, n = *n_eff;
+    const uint64_t cd_size = end - dir, cd_off = base + dir;
+    const bool z64 = n >= 0xFFFFull || cd_size >= 0xFFFFFFFFull || cd_off >= 0xFFFFFFFFull;
+    uint64_t at = end;
+    if (z64) {
+        const uint64_t r[7] = {0x06064B50ull | 44ull << 32, 0x032Dull << 32 | 45ull << 48, 0ull, n, n, cd_size, cd_off};
+        if (at + 56u <= out_cap) for (uint32_t k = 0; k < 56u; ++k) out[at + k] = zw_byte(r, k);
+        const uint64_t rec = base + at;
+        at += 56u;
+        const uint64_t l[3] = {0x07064B50ull, rec, 1ull};
+        if (at + 20u <= out_cap) for (uint32_t k = 0; k < 20u; ++k) out[at + k] = zw_byte(l, k);
+        at += 20u;
+    }
+    const uint64_t n16 = n < 0xFFFFull ? n : 0xFFFFull;
+    const uint64_t s32 = cd_size < 0xFFFFFFFFull ? cd_size : 0xFFFFFFFFull, o32 = cd_off < 0xFFFFFFFFull ? cd_off : 0xFFFFFFFFull;
+    const uint64_t w[3] = {0x06054B50ull, n16 | n16 << 16 | s32 << 32, o32};
+    if (at + ZIP_EOCD <= out_cap) for (uint32_t k = 0; k < ZIP_EOCD; ++k) out[at + k] = zw_byte(w, k);
+    at += ZIP_EOCD;
+    *out_len = at;
+    if (at > out_cap) atomicCAS(status, 0, ZMI_BUF_ERROR);
+    if (info) {
+        info->n_entries = n;
+        info->n_listed = n;
+        info->cd_off = dir;
+        info->cd_size = cd_size;
+        info->base = 0;
+        info->status = 0;
+        info->detail = 0;
+    }
+}
+
+extern "C" int zmi_launch_zip_layout(const uint32_t* d_in_len, const uint64_t* d_name_off, uint32_t n, uint32_t piece_bytes, uint32_t* d_elen,
+                                     uint32_t* d_nlen, uint32_t* d_npc, uint64_t* d_sum, int32_t* d_status, hipStream_t stream) {
+    if (n == 0) return 0;
+    ZMI_LAUNCH(zmi_zip_layout_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_in_len, d_name_off, n, piece_bytes, d_elen, d_nlen, d_npc,
+               (unsigned long long*)d_sum, d_status);
+    return 0;
+}
+extern "C" int zmi_launch_zip_pieces(const uint64_t* d_in_off, const uint32_t* d_elen, const uint32_t* d_nlen, const uint64_t* d_first,
+                                     const uint64_t* d_sum, uint32_t n, uint64_t in_bytes, uint32_t piece_bytes, uint32_t cap, uint32_t group,
+                                     uint32_t wpg, uint64_t* d_p_off, uint32_t* d_p_len, uint32_t* d_head, uint32_t* d_ends, uint32_t* d_n_eff,
+                                     int32_t* d_status, hipStream_t stream) {
+    if (n == 0 || cap == 0) return 0;
+    ZMI_LAUNCH(zmi_zip_pieces_kernel, dim3((cap + 255u) / 256u), dim3(256), 0, stream, d_in_off, d_elen, d_nlen, d_first,
+               (const unsigned long long*)d_sum, n, in_bytes,
+               piece_bytes, cap, group, wpg, d_p_off, d_p_len, d_head, d_ends, d_n_eff, d_status);
+    return 0;
+}
+extern "C" int zmi_launch_zip_sizes(const uint32_t* d_head, const uint32_t* d_olen, const int32_t* d_st, uint32_t n, uint32_t* d_size,
+                                    int32_t* d_status, hipStream_t stream) {
+    if (n == 0) return 0;
+    ZMI_LAUNCH(zmi_zip_sizes_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_head, d_olen, d_st, n, d_size, d_status);
+    return 0;
+}
+extern "C" int zmi_launch_zip_pack(const uint8_t* d_in, const uint64_t* d_p_off, const uint32_t* d_head, const uint8_t* d_slots,
+                                   uint64_t slot_stride, const uint32_t* d_olen, uint32_t n, uint32_t max_len, uint8_t* d_out,
+                                   const uint64_t* d_pos, uint64_t out_cap, hipStream_t stream) {
+    if (n == 0) return 0;
+    uint32_t split = 1;
+    const uint32_t tiles = (max_len + PK_TILE - 1u) / PK_TILE;
+    while ((uint64_t)n * split < 4096u && split < tiles) split <<= 1;
+    ZMI_LAUNCH(zmi_zip_pack_kernel, dim3(n * split), dim3(PK_T), 0, stream, d_in, d_p_off, d_head, d_slots, slot_stride, d_olen, d_out, d_pos,
+               out_cap, split, n * split);
+    return 0;
+}
+extern "C" int zmi_launch_zip_headers(const uint32_t* d_elen, const uint32_t* d_nlen, const uint64_t* d_first, const uint64_t* d_pos,
+                                      const uint32_t* d_crc, const uint8_t* d_names, const uint64_t* d_name_off, const uint32_t* d_dos_time,
+                                      const uint32_t* d_ext_attr, uint32_t n, const uint32_t* d_n_eff, uint32_t method, uint64_t base,
+                                      uint8_t* d_out, uint64_t out_cap, uint32_t* d_cen_size, const uint64_t* d_cen_off, zmi_zip_entry* d_entries,
+                                      uint32_t pass, int32_t* d_status, hipStream_t stream) {
+    if (n == 0) return 0;
+    const uint32_t per = 256u / ZW_G;
+    ZMI_LAUNCH(zmi_zip_headers_kernel, dim3((n + per - 1u) / per), dim3(256), 0, stream, d_elen, d_nlen, d_first, d_pos, d_crc, d_names, d_name_off,
+               d_dos_time, d_ext_attr, n, d_n_eff, method, base, d_out, out_cap, d_cen_size, d_cen_off, d_entries, pass, d_status);
+    return 0;
+}
+extern "C" int zmi_launch_zip_close(uint8_t* d_out, uint64_t out_cap, const uint64_t* d_pay_end, const uint64_t* d_cd_end, const uint32_t* d_n_eff,
+                                    uint64_t base, uint64_t* d_out_len, zmi_zip_info* d_info, int32_t* d_status, hipStream_t stream) {
+    ZMI_LAUNCH(zmi_zip_close_kernel, dim3(1), dim3(1), 0, stream, d_out, out_cap, d_pay_end, d_cd_end, d_n_eff, base, d_out_len, d_info, d_status);
+    return 0;
+}

@@ -425,13 +425,38 @@ extern "C" int zmi_pack_slab_dev(zmi_ctx* c, const void* d_slots, uint64_t slot_
     return zmi_copy_ranges_dev(c, d_slots, nullptr, slot_stride, d_len, n, max_len, d_slab, d_off, slab_cap, stream);
 }
 
+// The encoder's worst case for one of `pieces` regions of a shard of max_len bytes: every block stored (5 header bytes + byte
+// alignment); a block holds at least one sub-block of block_tokens tokens (>= as many input bytes), stored sub-blocks are cut at 32 KiB
+static uint64_t zmi_enc_region_worst(uint64_t max_len, uint32_t pieces, uint32_t block_tokens, bool dictid) {
+    const uint64_t psize = ((max_len + pieces - 1u) / pieces + 63u) & ~63ull;
+    const uint64_t min_block = block_tokens < 32768u ? block_tokens : 32768u;
+    return psize + 6u * (psize / min_block + 3u) + 32u + (dictid ? 4u : 0u);   // (the DICTID in the first piece)
+}
+// The regions a shard's slot is cut into (the encoder runs one wave per region: byte-aligned sub-streams, concatenated afterwards): one
+// per block_span of max_len, at most 16, fewer where a region of out_stride / pieces could not hold its worst case
+static uint32_t zmi_enc_regions(uint32_t max_len, uint64_t out_stride, uint32_t block_span, uint32_t block_tokens, bool dictid) {
+    uint32_t pieces = (max_len + block_span - 1u) / block_span;
+    if (pieces < 1u) pieces = 1u;
+    if (pieces > 16u) pieces = 16u;
+    const char* pieces_env = zmi_tune("ZMI_PIECES");
+    if (pieces_env && atoi(pieces_env) >= 1 && atoi(pieces_env) <= 64) pieces = (uint32_t)atoi(pieces_env);
+    // every piece region must hold its worst case (stored blocks + marker) and stay 16-byte aligned
+    while (pieces > 1u && ((out_stride / pieces) & ~15ull) < zmi_enc_region_worst(max_len, pieces, block_tokens, dictid)) --pieces;
+    return pieces;
+}
+
 // carry: -1 = what chain_mode implies, 0 = segments forget history (independent pieces of one stream), 1 = window carry-over.
+// ends: chain mode 2 only, the device bitmap of the shards that end a stream (zmi_enc_params).  geom_len (0: max_len): the max_len whose
+// region geometry the shards get -- that of a call with max_len = geom_len and the slots of zmi_deflate_pieces_stride(geom_len) --
+// while scratch and slots are sized by the smaller max_len the shards really have (zmi_zip_write_dev: bytes that depend on piece_bytes
+// alone, slots that follow the data); out_stride must then hold that geometry's regions for max_len.
 // launch_n: the number of segments the small-launch rule below judges (0: n) -- the whole stream's when a stream is compressed in
 // several launch groups, so that the bytes do not depend on the grouping.
 static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
                             uint32_t max_len, int level, int strategy, int wrap, uint32_t chain_mode, uint32_t dict_len,
                             uint32_t window_bits, void* d_out, uint64_t out_stride, uint32_t* d_out_len, int32_t* d_status,
-                            void* stream_, int carry = -1, uint64_t launch_n = 0, const zmi_sd_deflate* sd = nullptr);
+                            void* stream_, int carry = -1, uint64_t launch_n = 0, const zmi_sd_deflate* sd = nullptr,
+                            const uint32_t* ends = nullptr, uint32_t geom_len = 0);
 
 extern "C" int zmi_deflate_batch_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
                                      uint32_t n, uint32_t max_len, int level, int strategy, int wrap, void* d_out,
@@ -508,7 +533,7 @@ extern "C" int zmi_deflate_chain_window_dev(zmi_ctx* c, const void* d_in, const 
 static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
                             uint32_t max_len, int level, int strategy, int wrap, uint32_t chain_mode, uint32_t dict_len,
                             uint32_t window_bits, void* d_out, uint64_t out_stride, uint32_t* d_out_len, int32_t* d_status,
-                            void* stream_, int carry, uint64_t launch_n, const zmi_sd_deflate* sd) {
+                            void* stream_, int carry, uint64_t launch_n, const zmi_sd_deflate* sd, const uint32_t* ends, uint32_t geom_len) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (level == -1) level = 6;
     if (level < 0 || level > 9) return zmi_fail(ZMI_E_ARG, "level must be -1..9");
@@ -578,6 +603,7 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     ep.strategy = (uint32_t)strategy;
     ep.chain_mode = chain_mode;
     ep.last_shard = n - 1u;
+    ep.ends = chain_mode == 2u ? ends : nullptr;
     ep.dictid = (sd && wrap == ZMI_WRAP_ZLIB) ? sd->dictid : nullptr;
     if (level == 0) ep.strategy = 100u;           // stored blocks only (deflate_stored)
     ep.cost_parse = (level >= 3 && strategy != 2) ? 1u : 0u;
@@ -650,23 +676,11 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     rc = zmi_reserve(c->match, (size_t)(group * (per_shard + dec_bytes)));
     if (rc) return rc;
     uint32_t* const d_dec = ep.cost_parse ? (uint32_t*)((uint8_t*)c->match.p + group * per_shard) : nullptr;
-    // the encoder runs `pieces` waves per shard (byte-aligned sub-streams, concatenated afterwards):
-    // one piece per block_span of input, at most 16
-    uint32_t pieces = (max_len + ep.block_span - 1u) / ep.block_span;
-    if (pieces < 1u) pieces = 1u;
-    if (pieces > 16u) pieces = 16u;
-    const char* pieces_env = zmi_tune("ZMI_PIECES");
-    if (pieces_env && atoi(pieces_env) >= 1 && atoi(pieces_env) <= 64) pieces = (uint32_t)atoi(pieces_env);
-    // every piece region must hold its worst case (stored blocks + marker) and stay 16-byte aligned
-    while (pieces > 1u) {
-        uint64_t region = (out_stride / pieces) & ~15ull;
-        uint64_t psize = (((uint64_t)max_len + pieces - 1u) / pieces + 63u) & ~63ull;
-        // worst case: every block stored (5 header bytes + byte alignment); a block holds at least one sub-block of
-        // block_tokens tokens (>= as many input bytes), stored sub-blocks are cut at 32 KiB
-        const uint64_t min_block = ep.block_tokens < 32768u ? ep.block_tokens : 32768u;
-        uint64_t worst = psize + 6u * (psize / min_block + 3u) + 32u + (sd ? 4u : 0u);   // (the DICTID in the first piece)
-        if (region >= worst) break;
-        --pieces;
+    uint32_t pieces = zmi_enc_regions(max_len, out_stride, ep.block_span, ep.block_tokens, sd != nullptr);
+    if (geom_len) {
+        pieces = zmi_enc_regions(geom_len, zmi_deflate_pieces_stride(geom_len), ep.block_span, ep.block_tokens, sd != nullptr);
+        if (((out_stride / pieces) & ~15ull) < zmi_enc_region_worst(max_len, pieces, ep.block_tokens, sd != nullptr))
+            return zmi_fail(ZMI_E_ARG, "out_stride does not hold the regions of geom_len");
     }
     rc = zmi_reserve(c->pieces, (size_t)n * pieces * 4u);
     if (rc) return rc;
@@ -985,6 +999,133 @@ extern "C" int zmi_bgzf_deflate_dev(zmi_ctx* c, const void* d_in, uint64_t n, ui
     {
         zmi_scope_timer tm(c, ZMI_K_PACK, stream);
         zmi_launch_bgzf_close((uint8_t*)d_out, out_cap, d_boff + nb, 1u, d_out_len, d_status, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+// ---- writing ZIP archives (include/zmi355.h; the kernels: pack.hip, checksum.hip) ---------------------------------
+// The pieces of all entries are one table of at most n_entries + in_bytes / piece_bytes places (the lengths live on the device: places
+// behind the true count are void, length 0, and take no room in the archive).  The table goes through the independent-piece encoder in
+// the launch groups of zmi_bgzf_body -- chain mode 2 with the bitmap of the pieces that end an entry's stream --, every group is placed
+// behind the device word the group before ended at, so an entry may lie across groups; headers, directory and end structure are
+// written once the last payload is in place.
+extern "C" uint64_t zmi_zip_bound(uint32_t n_entries, uint64_t names_bytes, uint64_t in_bytes, uint32_t piece_bytes, int level) {
+    if (piece_bytes == 0) return 0;
+    // local header + central record with its ZIP64 extra + the name twice; the ZIP64 record, its locator, the end record
+    uint64_t b = (uint64_t)n_entries * (30u + 46u + 12u) + 2u * names_bytes + 56u + 20u + 22u + in_bytes;
+    if (level != 0) b += (in_bytes >> 3) + ((uint64_t)n_entries + in_bytes / piece_bytes) * 48u;   // zmi_deflate_pieces_stride per piece
+    return b;
+}
+
+extern "C" int zmi_zip_write_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n, uint64_t in_bytes,
+                                 const void* d_names, const uint64_t* d_name_off, const uint32_t* d_dos_time, const uint32_t* d_ext_attr,
+                                 uint32_t piece_bytes, int level, int strategy, uint64_t base, void* d_out, uint64_t out_cap,
+                                 uint64_t* d_out_len, zmi_zip_entry* d_entries, zmi_zip_info* d_info, int32_t* d_status, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (piece_bytes == 0 || piece_bytes > (1u << 30)) return zmi_fail(ZMI_E_ARG, "piece_bytes must be 1 .. 2^30");
+    int rc = zmi_bgzf_check_args(level, strategy);
+    if (rc) return rc;
+    if (n > 0x7FFFFFFFu) return zmi_fail(ZMI_E_ARG, "zmi_zip_write_dev: more than 2^31 - 1 entries");
+    if (!d_out_len || !d_status || (out_cap && !d_out) || (n && (!d_in_off || !d_in_len || !d_name_off || (in_bytes && !d_in))))
+        return zmi_fail(ZMI_E_ARG, "null argument");
+    const uint64_t np64 = n ? (uint64_t)n + in_bytes / piece_bytes : 0u;
+    if (np64 > 0x7FFFFFFFull) return zmi_fail(ZMI_E_ARG, "zmi_zip_write_dev: more than 2^31 - 1 pieces");
+    const uint32_t np = (uint32_t)np64;
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+
+    // launch groups: one group's output slots and the encoder's match scratch together stay within the scratch limit.  A slot holds a
+    // piece of max_len = min(piece_bytes, in_bytes) bytes in the regions of a piece_bytes shard (zmi_deflate_impl, geom_len): those of
+    // zmi_deflate_pieces_stride(max_len), more only where sixteen regions' worst cases do not fit that (pieces of a few KiB)
+    const uint32_t max_len = in_bytes < piece_bytes ? (uint32_t)in_bytes : piece_bytes;
+    uint64_t stride = 0, group = np;
+    if (level != 0) {
+        const uint32_t regions = zmi_enc_regions(piece_bytes, zmi_deflate_pieces_stride(piece_bytes), 65536u, kLevels[level].tok, false);
+        const uint64_t hold = (uint64_t)regions * ((zmi_enc_region_worst(max_len, regions, kLevels[level].tok, false) + 15u) & ~15ull);
+        stride = zmi_deflate_pieces_stride(max_len);
+        if (stride < hold) stride = hold;
+        const uint64_t match_per = ((((uint64_t)max_len + 63u) & ~63ull) ? (((uint64_t)max_len + 63u) & ~63ull) : 64u) * 4u;
+        group = c->scratch_limit / (stride + match_per + match_per / 16u);
+    }
+    if (const char* gv = zmi_tune("ZMI_STREAM_GROUP")) if (atoll(gv) > 0) group = (uint64_t)atoll(gv);
+    if (np && group == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one piece");
+    if (group > np) group = np;   // (no entries: no pieces, no group; what follows writes the end record alone)
+    if (level != 0) {
+        rc = zmi_reserve(c->sd_slots, (size_t)(group * stride));
+        if (rc) return rc;
+    }
+    const uint32_t wpg = (uint32_t)((group + 31u) / 32u);                       // bitmap words per group
+    const uint64_t n_groups = group ? (np + group - 1u) / group : 0u;
+    const size_t bm_words = (size_t)(n_groups * wpg);
+
+    // tables, 36 bytes per entry and 40 bytes + 1 bit per piece: u64 first piece [n + 1] | central offsets [n + 1] | piece input
+    // offsets [np] | piece places [np + 1] | four words (the count that is listed; the sum of the lengths, u64) | u32 checked lengths,
+    // name lengths, piece counts, CRC-32 values, central sizes [n each] | piece lengths, holes, encoder sizes, statuses, CRC-32
+    // values, places' sizes [np each] | the bitmap
+    rc = zmi_reserve(c->sd_meta, ((size_t)n + 1u) * 16u + (size_t)np * 16u + 8u + 16u + (size_t)n * 20u + (size_t)np * 24u + bm_words * 4u + 16u);
+    if (rc) return rc;
+    uint64_t* d_first = (uint64_t*)c->sd_meta.p;
+    uint64_t* d_coff = d_first + n + 1u;
+    uint64_t* d_poff = d_coff + n + 1u;
+    uint64_t* d_pos = d_poff + np;
+    uint32_t* d_neff = (uint32_t*)(d_pos + np + 1u);
+    uint64_t* d_sum = (uint64_t*)(d_neff + 2u);       // the sum of the checked lengths (zmi_zip_layout_kernel)
+    uint32_t* d_elen = d_neff + 4u;
+    uint32_t* d_nlen = d_elen + n;
+    uint32_t* d_npc = d_nlen + n;
+    uint32_t* d_ecrc = d_npc + n;
+    uint32_t* d_csz = d_ecrc + n;
+    uint32_t* d_plen = d_csz + n;
+    uint32_t* d_head = d_plen + np;
+    uint32_t* d_olen = d_head + np;
+    int32_t* d_st = (int32_t*)(d_olen + np);
+    uint32_t* d_pcrc = (uint32_t*)(d_st + np);
+    uint32_t* d_psz = d_pcrc + np;
+    uint32_t* d_ends = d_psz + np;
+
+    ZMI_HIP(hipMemsetAsync(d_status, 0, 4, stream));
+    ZMI_HIP(hipMemsetAsync(d_pos, 0, 8, stream));     // where the first group's pack starts
+    ZMI_HIP(hipMemsetAsync(d_neff, 0, 16, stream));
+    if (bm_words) ZMI_HIP(hipMemsetAsync(d_ends, 0, bm_words * 4u, stream));
+    {
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_zip_layout(d_in_len, d_name_off, n, piece_bytes, d_elen, d_nlen, d_npc, d_sum, d_status, stream);
+        zmi_launch_scan_sizes(d_npc, n, d_first, stream);
+        zmi_launch_zip_pieces(d_in_off, d_elen, d_nlen, d_first, d_sum, n, in_bytes, piece_bytes, np, (uint32_t)group, wpg, d_poff, d_plen,
+                              d_head, d_ends, d_neff, d_status, stream);
+    }
+    rc = zmi_piece_checks(c, d_in, d_poff, d_plen, np, ZMI_WRAP_GZIP, d_pcrc, stream);
+    if (rc) return rc;
+    for (uint64_t first = 0; first < np; first += group) {
+        const uint32_t cnt = (uint32_t)(np - first < group ? np - first : group);
+        if (level != 0) {
+            rc = zmi_deflate_impl(c, d_in, d_poff + first, d_plen + first, cnt, max_len, level, strategy, ZMI_WRAP_RAW, 2u, 0u, 15u, c->sd_slots.p,
+                                  stride, d_olen + first, d_st + first, stream_, 0, 0u, nullptr, d_ends + (first / group) * wpg, piece_bytes);
+            if (rc) return rc;
+        }
+        // the group's pieces go behind the previous group's, the running offset never leaves the device
+        const uint32_t* d_pay = level != 0 ? d_olen + first : d_plen + first;
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_zip_sizes(d_head + first, d_pay, level != 0 ? d_st + first : nullptr, cnt, d_psz + first, d_status, stream);
+        zmi_launch_scan_sizes_base(d_psz + first, cnt, d_pos + first, d_pos + first, stream);
+        zmi_launch_zip_pack((const uint8_t*)d_in, d_poff + first, d_head + first, level != 0 ? (const uint8_t*)c->sd_slots.p : nullptr, stride, d_pay,
+                            cnt, level != 0 ? (stride > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)stride) : max_len, (uint8_t*)d_out, d_pos + first,
+                            out_cap, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_CHECKSUM, stream);
+        zmi_launch_combine_segments(d_pcrc, d_plen, d_first, n, d_neff, d_ecrc, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        const uint32_t method = level != 0 ? 8u : 0u;
+        zmi_launch_zip_headers(d_elen, d_nlen, d_first, d_pos, d_ecrc, (const uint8_t*)d_names, d_name_off, d_dos_time, d_ext_attr, n, d_neff, method,
+                               base, (uint8_t*)d_out, out_cap, d_csz, d_coff, nullptr, 0u, d_status, stream);
+        zmi_launch_scan_sizes_base(d_csz, n, d_coff, d_pos + np, stream);
+        zmi_launch_zip_headers(d_elen, d_nlen, d_first, d_pos, d_ecrc, (const uint8_t*)d_names, d_name_off, d_dos_time, d_ext_attr, n, d_neff, method,
+                               base, (uint8_t*)d_out, out_cap, d_csz, d_coff, d_entries, 1u, d_status, stream);
+        zmi_launch_zip_close((uint8_t*)d_out, out_cap, d_pos + np, d_coff + n, d_neff, base, d_out_len, d_info, d_status, stream);
     }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;

@@ -45,8 +45,11 @@ struct zmi_enc_params {
                           // their limits from the codes of the block before (enc_far_limits)
     uint32_t chain_mode;  // 0: every shard is its own stream; 1: the shards of the batch are consecutive
                           // segments of ONE raw deflate stream, only shard `last_shard` ends it (BFINAL);
-                          // 2: as 1 but nothing ends the stream (Z_SYNC_FLUSH / Z_FULL_FLUSH output)
+                          // 2: as 1 but nothing ends the stream (Z_SYNC_FLUSH / Z_FULL_FLUSH output) -- or, with `ends`,
+                          // the shards named there do
     uint32_t last_shard;
+    const uint32_t* ends; // chain mode 2 only, null = none: device bitmap, bit s set = shard s of the call (first_shard included)
+                          // ends a stream; the next shard starts another one
     uint32_t cost_parse;  // 1: tokens are chosen by a backward cost parse over the matches (levels 3-9, csrc/parse.hip);
                           // 0: by the lazy rule (levels 1, 2 -- greedy -- and Z_HUFFMAN_ONLY / level 0, which have no matches)
     const uint32_t* dictid; // wrap 1 only, null = none: device word holding the Adler-32 of a preset dictionary; the zlib header
@@ -203,6 +206,29 @@ int zmi_launch_bgzf_pack(const uint8_t* d_in, const uint64_t* d_in_off, const ui
                          uint32_t max_len, uint8_t* d_out, const uint64_t* d_boff, uint64_t out_cap, hipStream_t stream);
 int zmi_launch_bgzf_close(uint8_t* d_out, uint64_t out_cap, const uint64_t* d_blocks_end, uint32_t eof, uint64_t* d_out_len,
                           int32_t* d_status, hipStream_t stream);
+// writing ZIP archives (pack.hip, checksum.hip): the entries' checked lengths and piece counts; the piece table (d_first: the scan of
+// the counts, *d_sum: the sum of the lengths, d_ends: the bitmap of chain mode 2, wpg words per launch group of `group` pieces);
+// one group's places and payload copies; the CRC-32 of every entry from its pieces'; the local headers and the sizes of the central
+// records (pass 0), the central records and d_entries (pass 1); the end structure, *d_out_len, d_info and Z_BUF_ERROR
+int zmi_launch_zip_layout(const uint32_t* d_in_len, const uint64_t* d_name_off, uint32_t n, uint32_t piece_bytes, uint32_t* d_elen,
+                          uint32_t* d_nlen, uint32_t* d_npc, uint64_t* d_sum, int32_t* d_status, hipStream_t stream);
+int zmi_launch_zip_pieces(const uint64_t* d_in_off, const uint32_t* d_elen, const uint32_t* d_nlen, const uint64_t* d_first,
+                          const uint64_t* d_sum, uint32_t n, uint64_t in_bytes, uint32_t piece_bytes, uint32_t cap, uint32_t group,
+                          uint32_t wpg, uint64_t* d_p_off, uint32_t* d_p_len, uint32_t* d_head, uint32_t* d_ends, uint32_t* d_n_eff,
+                          int32_t* d_status, hipStream_t stream);
+int zmi_launch_zip_sizes(const uint32_t* d_head, const uint32_t* d_olen, const int32_t* d_st, uint32_t n, uint32_t* d_size, int32_t* d_status,
+                         hipStream_t stream);
+int zmi_launch_zip_pack(const uint8_t* d_in, const uint64_t* d_p_off, const uint32_t* d_head, const uint8_t* d_slots, uint64_t slot_stride,
+                        const uint32_t* d_olen, uint32_t n, uint32_t max_len, uint8_t* d_out, const uint64_t* d_pos, uint64_t out_cap,
+                        hipStream_t stream);
+int zmi_launch_combine_segments(const uint32_t* d_check, const uint32_t* d_len, const uint64_t* d_first, uint32_t n, const uint32_t* d_n_live,
+                                uint32_t* d_out, hipStream_t stream);
+int zmi_launch_zip_headers(const uint32_t* d_elen, const uint32_t* d_nlen, const uint64_t* d_first, const uint64_t* d_pos, const uint32_t* d_crc,
+                           const uint8_t* d_names, const uint64_t* d_name_off, const uint32_t* d_dos_time, const uint32_t* d_ext_attr, uint32_t n,
+                           const uint32_t* d_n_eff, uint32_t method, uint64_t base, uint8_t* d_out, uint64_t out_cap, uint32_t* d_cen_size,
+                           const uint64_t* d_cen_off, zmi_zip_entry* d_entries, uint32_t pass, int32_t* d_status, hipStream_t stream);
+int zmi_launch_zip_close(uint8_t* d_out, uint64_t out_cap, const uint64_t* d_pay_end, const uint64_t* d_cd_end, const uint32_t* d_n_eff,
+                         uint64_t base, uint64_t* d_out_len, zmi_zip_info* d_info, int32_t* d_status, hipStream_t stream);
 // multi-member gzip files: proposals of member starts (pack.hip: count, scan, gather) and the plan / verify / repair steps of
 // zmi_inflate_members_dev (inflate.hip).  d_tab: eight u32[n] tables, d_off: u64[n + 1], d_w: sixteen words
 uint32_t zmi_mm_scan_segments(uint64_t in_len, uint32_t head);

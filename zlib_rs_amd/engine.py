@@ -904,6 +904,95 @@ class Engine:
             call(out)
         return out[:need], out_off, out_len, status
 
+    # ---- writing ZIP archives (include/zmi355.h) ----
+    def zip_bound(self, n_entries, names_bytes, in_bytes, piece_bytes=1 << 20, level=6):
+        return int(self.L.zmi_zip_bound(int(n_entries), int(names_bytes), int(in_bytes), int(piece_bytes), int(level)))
+
+    def _zip_names(self, names):
+        """list of str (encoded as UTF-8) or (blob uint8, offsets int64 [n + 1]) -> the pair on the device and the blob's size"""
+        if isinstance(names, (tuple, list)) and len(names) == 2 and isinstance(names[0], torch.Tensor):
+            blob, off = names
+            blob = blob.to(device=self.device, dtype=torch.uint8).contiguous().view(-1)
+            return blob, off.to(device=self.device, dtype=torch.int64).contiguous(), int(blob.numel())
+        import numpy as np
+        enc = [nm.encode("utf-8") if isinstance(nm, str) else bytes(nm) for nm in names]
+        off = np.zeros(len(enc) + 1, dtype=np.int64)
+        np.cumsum([len(b) for b in enc], out=off[1:])
+        blob = torch.from_numpy(np.frombuffer(b"".join(enc) + b"\0", dtype=np.uint8).copy()).to(self.device)
+        return blob, torch.from_numpy(off).to(self.device), int(off[-1])
+
+    def zip_write(self, data, offsets, lengths, names, level=6, strategy=0, piece_bytes=1 << 20, base=0, dos_time=None, ext_attr=None,
+                  directory=False, out=None):
+        """The entries data[offsets[i] : + lengths[i]] (uint8 device tensor, int64 / int32 tables) as a ZIP archive -> a uint8 view of
+        exactly the archive, and with directory=True also its ZipDirectory, made from the writer's own table and info: names(), index()
+        and zip_read work on it without parsing anything again.  names: a list of str, or a (blob, offsets) pair of tensors.  level 0
+        stores; dos_time / ext_attr: int32 tensors, one word per entry (None: 1980-01-01 and a regular file, 0644).  base: the file
+        position the archive will stand at.  One synchronisation, for the length; a non-zero status raises.  Tables and the names blob
+        on another device, of another integer type or not contiguous are converted; data must be a contiguous uint8 tensor on the
+        engine's device (it is never copied), as must out."""
+        for what, t in (("data", data), ("out", out)):
+            if t is not None and (t.dtype != torch.uint8 or t.device != self.device or not t.is_contiguous()):
+                raise ValueError("zip_write: %s must be a contiguous uint8 tensor on %s" % (what, self.device))
+        offsets = offsets.to(device=self.device, dtype=torch.int64).contiguous()
+        lengths = lengths.to(device=self.device, dtype=torch.int32).contiguous()
+        n = int(lengths.numel())
+        if int(offsets.numel()) < n:
+            raise ValueError("zip_write: %d lengths need %d offsets" % (n, n))
+        blob, name_off, names_bytes = self._zip_names(names)
+        if int(name_off.numel()) != n + 1:
+            raise ValueError("names: %d entries need %d offsets" % (n, n + 1))
+        in_bytes = int(data.numel())
+        if out is None:
+            out = torch.empty(self.zip_bound(n, names_bytes, in_bytes, piece_bytes, level), dtype=torch.uint8, device=self.device)
+        meta = torch.zeros(8, dtype=torch.int64, device=self.device)     # length | status (int32) | zmi_zip_info
+        entries = torch.empty((n, ZIP_ENTRY_BYTES), dtype=torch.uint8, device=self.device) if directory else None
+        words = [None if t is None else t.to(device=self.device, dtype=torch.int32).contiguous() for t in (dos_time, ext_attr)]
+        _lib.check(self.L.zmi_zip_write_dev(self._ctx, data.data_ptr() if in_bytes else None, offsets.data_ptr() if n else None,
+                                            lengths.data_ptr() if n else None, n, in_bytes, blob.data_ptr(), name_off.data_ptr(),
+                                            words[0].data_ptr() if words[0] is not None and n else None,
+                                            words[1].data_ptr() if words[1] is not None and n else None, int(piece_bytes), int(level),
+                                            int(strategy), int(base), out.data_ptr() if out.numel() else None, int(out.numel()), meta.data_ptr(),
+                                            entries.data_ptr() if directory and n else None, meta.data_ptr() + 16 if directory else None,
+                                            meta.data_ptr() + 8, _stream_ptr()), "zmi_zip_write_dev")
+        host = meta.tolist()
+        length, st = host[0], host[1] & 0xFFFFFFFF
+        status = st - (1 << 32) if st >= 1 << 31 else st
+        if status != 0:
+            raise RuntimeError("zmi_zip_write_dev: status %d (archive of %d bytes, room for %d)" % (status, length, out.numel()))
+        if not directory:
+            return out[:length]
+        info = {"n_entries": host[2], "n_listed": host[3], "cd_off": host[4], "cd_size": host[5], "base": host[6], "status": 0, "detail": 0}
+        return out[:length], ZipDirectory(out[:length], entries, info)
+
+    _NPY_DESCR = {torch.bool: "|b1", torch.uint8: "|u1", torch.int8: "|i1", torch.int16: "<i2", torch.int32: "<i4", torch.int64: "<i8",
+                  torch.float16: "<f2", torch.float32: "<f4", torch.float64: "<f8"}
+
+    def save_npz(self, arrays, level=6, piece_bytes=1 << 20):
+        """arrays: dict of name -> device tensor -> the bytes of an .npz numpy.load opens (level 0: what numpy.savez writes, stored;
+        otherwise savez_compressed's layout).  The version-1.0 .npy headers are made on the host, padded to 64 bytes; headers and
+        payloads become one buffer with one torch.cat and one archive with one zip_write.  dtypes: those with a NumPy twin (bool, uint8,
+        int8, int16, int32, int64, float16, float32, float64); any other, bfloat16 included, is a TypeError."""
+        import numpy as np
+        parts, offs, lens, names, at = [], [], [], [], 0
+        for name, t in arrays.items():
+            if t.dtype not in self._NPY_DESCR:
+                raise TypeError("save_npz: %r has dtype %s, which has no NumPy twin" % (name, t.dtype))
+            shape = "(%d,)" % t.shape[0] if t.dim() == 1 else "(%s)" % ", ".join("%d" % d for d in t.shape)
+            head = "{'descr': '%s', 'fortran_order': False, 'shape': %s, }" % (self._NPY_DESCR[t.dtype], shape)
+            head += " " * (-(10 + len(head) + 1) % 64) + "\n"
+            head = b"\x93NUMPY\x01\x00" + len(head).to_bytes(2, "little") + head.encode("latin1")
+            body = t.to(self.device).contiguous().view(-1)
+            body = body.view(torch.uint8) if body.numel() else torch.empty(0, dtype=torch.uint8, device=self.device)
+            parts += [torch.from_numpy(np.frombuffer(head, dtype=np.uint8).copy()).to(self.device), body]
+            offs.append(at)
+            lens.append(len(head) + int(body.numel()))
+            names.append(name + ".npy")
+            at += lens[-1]
+        data = torch.cat(parts) if parts else torch.empty(0, dtype=torch.uint8, device=self.device)
+        out = self.zip_write(data, torch.tensor(offs, dtype=torch.int64, device=self.device),
+                             torch.tensor(lens, dtype=torch.int32, device=self.device), names, level=level, piece_bytes=piece_bytes)
+        return out.cpu().numpy().tobytes()
+
     # ---- checksums ----
     def checksums(self, data, offsets, lengths, adler=True, crc=True, out_adler=None, out_crc=None):
         """(adler int32 [n], crc int32 [n]); the array of a checksum that was not asked for is left as it is (zeros when

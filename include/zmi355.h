@@ -128,7 +128,11 @@ int zmi_deflate_chain_window_dev(zmi_ctx* ctx, const void* d_in, const uint64_t*
                                  uint32_t dict_len, uint32_t window_bits, void* d_out, uint64_t out_stride,
                                  uint32_t* d_out_len, int32_t* d_status, void* stream);
 /* As zmi_inflate_batch_dev, additionally reporting the consumed input bytes and why a stream
- * stopped (d_detail: 0 done/error, 1 needs more input, 2 needs more output space). */
+ * stopped (d_detail: 0 done/error, 1 needs more input, 2 needs more output space; a data error inside the deflate data: 16 + k,
+ * k the index of the reference's message).  d_in_used of a stream that fails inside its deflate data is the reference's
+ * total_in: all of the input when it ran out, otherwise the bytes up to the last bit read (the end of the token, repeat or
+ * header field that is wrong; an invalid code counts with the bits of its table entry: one bit for the unused half of a
+ * single-code form).  zmi_inflate_resume_dev and the calls built on it report the same count. */
 int zmi_inflate_batch_dev_ex(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
                              uint32_t n_streams, int wrap, void* d_out, const uint64_t* d_out_off,
                              const uint32_t* d_out_cap, uint32_t* d_out_len, int32_t* d_status, uint32_t* d_in_used,

@@ -172,6 +172,7 @@ typedef struct {
     uint16_t count[16];
     uint16_t sym[320];
     int nsym_coded;
+    int maxlen;
 } zo_huff;
 
 /* returns 0 ok, -1 over-subscribed, +1 incomplete (caller applies the reference's rule:
@@ -184,6 +185,7 @@ static int zo_huff_build(zo_huff* h, const uint8_t* lens, int n, int* maxlen) {
     int mx = 15;
     while (mx > 0 && h->count[mx] == 0) --mx;
     *maxlen = mx;
+    h->maxlen = mx;
     int left = 1;
     for (int l = 1; l <= 15; ++l) {
         left <<= 1;
@@ -205,6 +207,10 @@ static int zo_huff_decode(zo_bits* b, const zo_huff* h) {
         code |= (int)zo_take(b, 1);
         int c = h->count[l];
         if (code - c < first) return h->sym[index + (code - first)];
+        /* past the longest code nothing can match: the reference's table holds an invalid entry of that length -- for the
+         * unused half of a one-symbol code and for a code with no symbol an entry of ONE bit (inflate/inftrees.rs:61-67,
+         * :230-241), which its lookup loop reports with one bit in hand (inflate.rs:640-652, :747-758) */
+        if (l >= (h->maxlen > 1 ? h->maxlen : 1)) return -1;
         index += c;
         first += c;
         first <<= 1;
@@ -297,8 +303,10 @@ int zo_inflate(const uint8_t* in, size_t in_len, uint8_t* out, size_t out_cap, i
         if (type == 1) { /* inflate.rs:1309-1317, inflate/inffixed_tbl.rs */
             for (int i = 0; i < 288; ++i) lens[i] = (uint8_t)(i < 144 ? 8 : (i < 256 ? 9 : (i < 280 ? 7 : 8)));
             zo_huff_build(&lh, lens, 288, &mx);
-            for (int i = 0; i < 30; ++i) lens[i] = 5;
-            zo_huff_build(&dh, lens, 30, &mx);
+            /* 32 distance codes: 30 and 31 are codes of 5 bits that stand for no distance (inflate/inffixed_tbl.rs:538,554:
+             * op 64, bits 5), so they are an error with 5 bits in hand, not holes that need 15 */
+            for (int i = 0; i < 32; ++i) lens[i] = 5;
+            zo_huff_build(&dh, lens, 32, &mx);
         } else { /* inflate.rs:1604-1777 */
             static const uint8_t order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
             if (!zo_need(&b, 14)) ZO_FAIL(ZO_BUF_ERROR, NULL);

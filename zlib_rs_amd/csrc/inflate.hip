@@ -244,7 +244,9 @@ static __device__ __noinline__ uint32_t inf_build(InfShared* S_, uint32_t kind, 
     const uint32_t maxl = zmi_uniform(S->misc[1]);
     const uint32_t ncoded = zmi_uniform(S->misc[2]);
     const uint32_t rsize = 1u << root;
-    for (uint32_t i = lane; i < rsize; i += 64u) tab[i] = INF_ENTRY(0, INF_OP_BAD, 0);
+    // (what no code overwrites is the reference's entry for the unused half of a one-symbol code and for a code with no symbol at
+    // all: an invalid code of ONE bit, zlib-rs/src/inflate/inftrees.rs:61-67 and :230-241 -- a complete code leaves none)
+    for (uint32_t i = lane; i < rsize; i += 64u) tab[i] = INF_ENTRY(0, INF_OP_BAD, 1);
     zmi_wave_sync();
     if (lane == 0u) S->misc[3] = rsize;   // entries this table occupies (the root alone so far); inflateCodesUsed sums them
     if (maxl == 0u) return 0u;  // no codes at all: every lookup reports an invalid code
@@ -316,7 +318,7 @@ static __device__ __noinline__ uint32_t inf_build(InfShared* S_, uint32_t kind, 
     }
     if (used > cap) return 2u;
     if (lane == 0u) S->misc[3] = used;
-    for (uint32_t j = rsize + lane; j < used; j += 64u) tab[j] = INF_ENTRY(0, INF_OP_BAD, 0);
+    for (uint32_t j = rsize + lane; j < used; j += 64u) tab[j] = INF_ENTRY(0, INF_OP_BAD, 1);   // (all overwritten: the code is complete)
     zmi_wave_sync();
     for (uint32_t base = 0; base < nlong; base += 64u) {
         if (base + lane < nlong) {
@@ -343,7 +345,8 @@ static __device__ __noinline__ uint32_t inf_build(InfShared* S_, uint32_t kind, 
 // second-level lookups: selects cost two VALU instructions, a divergent branch costs exec-mask bookkeeping on
 // the scalar unit, which is the busier one.
 struct InfTok {
-    uint32_t tw;     // bits 0-5 token length in bits; above 63 it stops the chain walk: 64 = end of block, 128 / 256 = error
+    uint32_t tw;     // bits 0-5 token length in bits; above 63 it stops the chain walk: 64 = end of block, 128 / 256 = error (more input /
+                     // invalid), and an error word carries above bit 16 the bits the reference has read from the token's first bit
     uint32_t kind;   // 0 literal, 1 back-reference, 2 end of block
     uint32_t val;    // literal byte | match length
     uint32_t dist;
@@ -355,7 +358,7 @@ static __device__ __forceinline__ InfTok inf_tok(const InfShared* S, uint32_t lo
         e = S->ltab[(e >> 16) + ((lo >> INF_LROOT) & ((1u << sb) - 1u))];
     }
     const uint32_t bits = e & 0xFFu, op = (e >> 8) & 0xFFu;
-    const bool bad = op == INF_OP_BAD || bits == 0u;                  // "invalid literal/length code"
+    const bool bad = op == INF_OP_BAD;                                 // "invalid literal/length code"
     const bool is_eob = op == INF_OP_EOB;
     const bool is_len = (op & INF_OP_BASE) != 0u;
     const uint32_t xb = is_len ? (op & 0x0Fu) : 0u;
@@ -363,7 +366,7 @@ static __device__ __forceinline__ InfTok inf_tok(const InfShared* S, uint32_t lo
     InfTok T;
     T.val = (e >> 16) + ((lo >> bits) & ((1u << xb) - 1u));
     // distance code: skipped by a scalar branch when no lane holds a length code (literal-only data)
-    uint32_t dlen = 0;
+    uint32_t dlen = 0, dbits_of_bad = 0;
     bool dbad = false;
     T.dist = 0;
     if (__ballot(is_len)) {
@@ -374,17 +377,24 @@ static __device__ __forceinline__ InfTok inf_tok(const InfShared* S, uint32_t lo
             d = S->dtab[(d >> 16) + ((rest >> INF_DROOT) & ((1u << sb) - 1u))];
         }
         const uint32_t dbits = d & 0xFFu, dop = (d >> 8) & 0xFFu;
-        dbad = dop == INF_OP_BAD || dbits == 0u || !(dop & INF_OP_BASE);   // "invalid distance code"
+        dbad = dop == INF_OP_BAD || !(dop & INF_OP_BASE);                  // "invalid distance code"
         const uint32_t dxb = dop & 0x0Fu;
         T.dist = (d >> 16) + ((rest >> dbits) & ((1u << dxb) - 1u));
         dlen = dbits + dxb;
+        dbits_of_bad = dbits;
     }
     const uint32_t t = is_len ? used + dlen : bits;                     // <= 48
     T.kind = is_len ? 1u : (is_eob ? 2u : 0u);
-    // 1: more input needed, 2: invalid data (the reference decides by the bits that are left)
-    const uint32_t err_len = (int32_t)used > rem ? 1u : (dbad ? ((rem - (int32_t)used) < 15 ? 1u : 2u) : ((int32_t)t > rem ? 1u : 0u));
-    const uint32_t err = bad ? (rem < 15 ? 1u : 2u) : ((int32_t)bits > rem ? 1u : (is_len ? err_len : 0u));
-    T.tw = err ? (err << 7) : (t | (is_eob ? 64u : 0u));
+    // 1: more input needed, 2: invalid data (the reference decides by the bits that are left).  Every invalid pattern is a table entry
+    // with a length -- the codes of the fixed tables that stand for no symbol (286, 287, distance 30, 31), and the one-bit entry for
+    // the unused half of a single-code form (inf_build) -- and is an error as soon as its own bits are there: the reference breaks out
+    // of its lookup loop with here.bits <= bits_in_buffer (zlib-rs/src/inflate.rs:640-652, :689, :747-758, :784)
+    const int32_t drem = rem - (int32_t)used;
+    const uint32_t err_len = (int32_t)used > rem ? 1u : (dbad ? ((int32_t)dbits_of_bad > drem ? 1u : 2u) : ((int32_t)t > rem ? 1u : 0u));
+    const uint32_t err = (int32_t)bits > rem ? 1u : (bad ? 2u : (is_len ? err_len : 0u));
+    // (an error word also carries, above bit 16, the bits the reference has read from the token's first bit when it gives up)
+    const uint32_t eb = bad ? bits : used + dbits_of_bad;
+    T.tw = err ? ((err << 7) | (eb << 16)) : (t | (is_eob ? 64u : 0u));
     return T;
 }
 // walk the token chain through one 64-position window: sets the bit of every token start in M, leaves in w the
@@ -1163,6 +1173,11 @@ __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __r
     }
 
     // ---- blocks ----
+    // d_in_used of a stream that fails inside its deflate data is the reference's count (total_in: the bytes it has pulled, zlib-rs
+    // pull_byte / need_bits, inflate.rs:640-652): all of the input when it ran out, otherwise up to the last bit it read -- err_bits,
+    // where the failing token or repeat ends (~0: the serial reader's own position says it)
+    const bool in_blocks = st == ZMI_OK;
+    uint64_t err_bits = ~0ull;
     uint32_t last = 0;
     while (st == ZMI_OK && !last) {
         inf_refill(B);
@@ -1283,7 +1298,7 @@ __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __r
                     const uint64_t ends = __ballot(on && have + incl == total);
                     const uint32_t kb = badrep ? (uint32_t)__ffsll((unsigned long long)badrep) - 1u : 64u;
                     const uint32_t ke = ends ? (uint32_t)__ffsll((unsigned long long)ends) - 1u : 64u;
-                    if (kb < 64u && kb <= ke) { st = ZMI_DERR(DE_BIT_LENGTH_REPEAT); break; }
+                    if (kb < 64u && kb <= ke) { st = ZMI_DERR(DE_BIT_LENGTH_REPEAT); err_bits = P + kb + zmi_readlane(t, kb); break; }
                     if (ke < 64u) {   // the token in lane ke completes the header; nothing behind it belongs to it
                         M &= (2ull << ke) - 1ull;
                         on = (M >> lane) & 1ull;
@@ -1458,6 +1473,7 @@ __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __r
                     } else rst = (w & 128u) ? ZMI_BUF_ERROR : ZMI_DERR(DE_CODE);
                 }
                 if (inB) pos += 64u;   // bits consumed
+                if (rst <= ZMI_DERR(1)) err_bits = P + pos + (w >> 16);
 
                 // place the outputs
                 bool onA = (MA >> lane) & 1ull, onB = (MB >> lane) & 1ull;
@@ -1484,12 +1500,14 @@ __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __r
                         MB = 0;
                         tot = zmi_readlane(exclA, k);
                         pos = k;
+                        err_bits = fb ? P + k + (zmi_readlane(TA.tw, k) & 63u) : ~0ull;
                     } else {
                         const uint32_t k = (uint32_t)__ffsll((unsigned long long)cutB) - 1u;
                         fb = (uint32_t)((__ballot(farB) >> k) & 1ull);
                         MB &= (1ull << k) - 1ull;
                         tot = zmi_readlane(exclB, k);
                         pos = 64u + k;
+                        err_bits = fb ? P + 64u + k + (zmi_readlane(TB.tw, k) & 63u) : ~0ull;
                     }
                     onA = (MA >> lane) & 1ull;
                     onB = (MB >> lane) & 1ull;
@@ -1517,6 +1535,8 @@ __global__ void __launch_bounds__(64 * NW) zmi_inflate_kernel(const uint8_t* __r
             }
         }
     }
+    if (in_blocks && st == ZMI_BUF_ERROR) B.ipos = B.n;
+    else if (st <= ZMI_DERR(1)) B.ipos = err_bits != ~0ull ? (uint32_t)((err_bits + 7ull) >> 3) : B.ipos - (B.nbits >> 3);
     // ---- trailer ----
     uint32_t chk = 0;
     if (st == ZMI_OK) {
@@ -2626,7 +2646,8 @@ __global__ void __launch_bounds__(256) zmi_si_verify_kernel(const uint64_t* __re
     const bool last = g + 1u == n_cuts;
     uint32_t kind = 0, idx = g;
     if (in_n[i] == 0u) { kind = SI_D_CUT; idx = g + 1u < n_cuts ? g + 1u : g; }
-    else if (st[i] == ZMI_DATA_ERROR) kind = SI_D_DATA;
+    // (a piece's own decode finds a distance too far back only where no window stands in front of it: the stream's start)
+    else if (st[i] == ZMI_DATA_ERROR) kind = det[i] == 16 + DE_TOO_FAR_BACK ? SI_D_FAR : SI_D_DATA;
     else if (st[i] == ZMI_BUF_ERROR && det[i] == 2) kind = SI_D_PIECE;
     else if (olen[i] > cap) kind = SI_D_PIECE;
     else if (st[i] != ZMI_OK && st[i] != ZMI_BUF_ERROR) kind = SI_D_DATA;
@@ -2679,7 +2700,8 @@ __global__ void __launch_bounds__(256) zmi_si_verify_bits_kernel(const uint64_t*
     const bool last = g + 1u == n_cuts;
     uint32_t kind = 0, idx = g, L = olen[i];
     if (in_n[i] == 0u) { kind = SI_D_CUT; idx = g + 1u < n_cuts ? g + 1u : g; }
-    else if (st[i] == ZMI_DATA_ERROR) kind = SI_D_DATA;
+    // (a piece's own decode finds a distance too far back only where no window stands in front of it: the stream's start)
+    else if (st[i] == ZMI_DATA_ERROR) kind = det[i] == 16 + DE_TOO_FAR_BACK ? SI_D_FAR : SI_D_DATA;
     else if (st[i] == ZMI_BUF_ERROR && det[i] == 2) kind = SI_D_PIECE;
     else if (olen[i] > cap) kind = SI_D_PIECE;
     else if (st[i] != ZMI_OK && st[i] != ZMI_BUF_ERROR) kind = SI_D_DATA;

@@ -7,8 +7,10 @@ zmi_inflate_batch_dev_ex given ample room, which tests/parity_checks.py pins on 
 
 A target offers (streams: list of bytes; every call places stream i `shifts[i]` bytes behind a 16-byte boundary)
     sizes(streams, wrap, hist=0, limit=0, shifts=None)              -> [Word(size, status, in_used, detail)]
-    batch(streams, wrap, caps, zdict=None, align=1)                 -> Decoded: zmi_inflate_batch_dev_ex (zdict: the shared-dictionary
-                                                                       call) with out_off = the aligned scan of caps
+    batch(streams, wrap, caps, zdict=None, align=1, set_limit=True) -> Decoded: zmi_inflate_batch_dev_ex (zdict: the shared-dictionary
+                                                                       call) with out_off = the aligned scan of caps, under an
+                                                                       inflate-out limit set for these caps (set_limit=False: under
+                                                                       the context's limit as set_out_limit(nbytes) left it)
     packed(streams, wrap, out_cap, align=1, zdict=None, limit=0)    -> Decoded of ONE zmi_inflate_batch_packed_dev call
     rc_sizes(wrap=1, hist=0, null_ctx=False, n=1), rc_packed(wrap=1, align=1, zdict=None, null_ctx=False, n=1)  -> the return code
     own(shards, level, wrap)                                        -> what the library's deflate makes of the shards
@@ -25,7 +27,7 @@ from members_checks import text
 
 RAW, ZLIB, GZIP, AUTO = 0, 1, 2, 3
 WBITS = {RAW: -15, ZLIB: 15, GZIP: 31}
-Z_NEED_DICT, Z_DATA_ERROR, Z_BUF_ERROR, E_ARG = 2, -3, -5, -103
+Z_NEED_DICT, Z_DATA_ERROR, Z_MEM_ERROR, Z_BUF_ERROR, E_ARG = 2, -3, -4, -5, -103
 GUARD = 256
 FILL = 0xC7
 AMPLE = 2 << 20
@@ -410,6 +412,41 @@ def arguments(target):
     return 17
 
 
+# ---- 8. the context's inflate-out limit belongs to the caller -----------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def limit_batch():
+    """twelve zlib streams of 128 KiB: under the smallest limit the setter accepts, 1 MiB, the bitmap holds the first eight"""
+    raws = [text(1 << 17, 600 + i) for i in range(12)]
+    return [deflate(r, ZLIB, 1) for r in raws], raws
+
+
+def context_limit(target, between=None):
+    """zmi_ctx_set_inflate_out_limit is the setting for calls that do not size their own scratch: calls that do (the packed call, with and
+    without a dictionary; `between`: whatever else the target can run) neither use it nor change it.  The bitmap plan is a scan in stream
+    order, so which streams a limit leaves out does not depend on the machine."""
+    streams, raws = limit_batch()
+    caps = [1 << 17] * len(raws)
+    target.set_out_limit(1 << 20)
+
+    def under_the_limit():
+        b = target.batch(streams, ZLIB, caps, set_limit=False)
+        assert b.rc == 0 and b.guard_ok
+        assert [w.status for w in b.words] == [0] * 8 + [Z_MEM_ERROR] * 4, b.words
+        assert [b.piece(i) for i in range(8)] == raws[:8]
+
+    under_the_limit()
+    if between is not None:
+        between(streams, raws)
+    zd = text(3000, 71)
+    for zdict, ss in ((None, streams), (zd, [deflate(r, ZLIB, 1, zdict=zd) for r in raws])):
+        p = target.packed(ss, ZLIB, 12 << 17, zdict=zdict)
+        assert p.rc == 0 and p.guard_ok
+        assert [w.status for w in p.words] == [0] * 12, p.words
+        assert [p.piece(i) for i in range(12)] == raws
+    under_the_limit()
+    return 4
+
+
 # ---- the target both test files build on: the C ABI through ctypes over a memory provider ---------------------------------------------
 def bind(L):
     """the ctypes signatures these checks need"""
@@ -474,7 +511,10 @@ class AbiTarget:
         host = self.mem.read(out, np.uint8).tobytes()
         return Decoded(rc, off, self._words(n, olen, st, used, det) if rc == 0 else [], host[:out_cap], host[out_cap:] == bytes([FILL]) * GUARD)
 
-    def batch(self, streams, wrap, caps, zdict=None, align=1):
+    def set_out_limit(self, nbytes):
+        assert self.L.zmi_ctx_set_inflate_out_limit(self.ctx, nbytes) == 0
+
+    def batch(self, streams, wrap, caps, zdict=None, align=1, set_limit=True):
         import numpy as np
         n, m = len(streams), self.mem
         d, off, ln = self._input(streams)
@@ -483,7 +523,8 @@ class AbiTarget:
         out = m.full(scan[-1] + GUARD, FILL)
         olen, st, used, det = (m.full(4 * n + 4, 0x77) for _ in range(4))
         zd = self._zdict(zdict)
-        self.L.zmi_ctx_set_inflate_out_limit(self.ctx, scan[-1] + (1 << 20))
+        if set_limit:
+            self.set_out_limit(scan[-1] + (1 << 20))
         if zd is not None:
             rc = self.L.zmi_inflate_batch_shared_dict_dev(self.ctx, d.ptr, off.ptr, ln.ptr, n, wrap, zd.ptr, len(zdict), out.ptr, ooff.ptr, ocap.ptr,
                                                           olen.ptr, st.ptr, used.ptr, det.ptr, m.stream)

@@ -118,3 +118,15 @@ def test_capacity(target, inf_selection, align):
 
 def test_arguments(target):
     assert K.arguments(target) == 17
+
+
+def test_context_limit_is_the_callers(target):
+    """... also across the host-buffer batch and the single-stream call, which size their own scratch too (twelve streams: both decode
+    selections are the same kernel)"""
+    def host_calls(streams, raws):
+        out, st = target.e.inflate(streams, [len(r) for r in raws], wrap=K.ZLIB)
+        assert st == [0] * len(raws) and out == raws
+        got, status, _, used, res = target.e.inflate_resume(streams[0][2:-4], cap=len(raws[0]) + 64)
+        assert (got, status, used, res[3]) == (raws[0], 0, len(streams[0]) - 6, 1)
+
+    assert K.context_limit(target, between=host_calls) == 4

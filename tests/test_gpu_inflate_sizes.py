@@ -142,6 +142,10 @@ def test_arguments(target):
     assert K.arguments(target) == 17
 
 
+def test_context_limit_is_the_callers(target):
+    assert K.context_limit(target) == 4
+
+
 def test_engine_allocates_exactly(target, inf_selection):
     """Engine.inflate_batch_packed(out=None): one buffer of exactly the planned size whose slices are the payloads; inflate_sizes agrees"""
     e, dev = target.e, target.e.device

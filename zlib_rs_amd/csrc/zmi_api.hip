@@ -17,18 +17,7 @@
 #include <string>
 #include <vector>
 
-extern "C" int zmi_launch_inflate_verify(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
-                                         uint32_t n_streams, uint32_t wrap, const uint32_t* d_check, const uint32_t* d_adler,
-                                         const uint32_t* d_crc, int32_t* d_status, int32_t* d_detail, hipStream_t stream);
-
 static thread_local std::string g_err;
-extern "C" int zmi_launch_inflate_shared_hist(uint32_t* d_hist, uint32_t n_streams, uint32_t hist, hipStream_t stream);
-extern "C" int zmi_launch_inflate_resolve_shared(uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_len, uint32_t n_streams,
-                                                 const uint64_t* d_bitmap, const uint64_t* d_bm_off, const uint32_t* d_order,
-                                                 const uint8_t* d_img, uint32_t hist, hipStream_t stream);
-extern "C" int zmi_launch_inflate_dictid(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_streams,
-                                         const uint32_t* d_dictid, int32_t* d_status, int32_t* d_detail, uint32_t* d_out_len,
-                                         hipStream_t stream);
 static int zmi_fail(int code, const char* what, hipError_t e = hipSuccess) {
     char buf[256];
     if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s", what, hipGetErrorString(e));
@@ -85,7 +74,7 @@ struct zmi_ctx {
     zmi_buf match;    // u32 per position of the current group
     zmi_buf sums;     // adler[n] crc[n]
     zmi_buf pieces;   // per shard x piece compressed length
-    zmi_buf inf_tmp;  // in_used[n] check[n] adler[n] crc[n] bm_off[n] (u64)
+    zmi_buf inf_tmp;  // inflate: the per-stream tables of one launch (zmi_inf_tables_of states the layout; callers get zmi_inf_scratch)
     zmi_buf inf_bm;   // inflate: 1 bit per output byte of the batch (where back-references start)
     zmi_buf inf_ptr;  // inflate of few streams: 4 B per output byte, the pointers of the jump resolve (resolve_jump.hip)
     zmi_buf st_in, st_out, st_meta;  // zmi_inflate_resume: staging of one host stream (kept across calls)
@@ -103,8 +92,8 @@ struct zmi_ctx {
     uint64_t pinned_limit = 10ull << 30;   // host-buffer pipelines: pinned staging this context may hold (chunk sizes follow it; env ZMI_PINNED_MB)
     std::atomic<int> hb_out_tight{-1};     // zmi_inflate_batch: did the last chunk decoded fill most of its capacity?  (-1: nothing decoded yet)
     uint32_t last_codes_used = 0;    // zmi_inflate_resume: table entries of the most recent dynamic block of the last call (inflateCodesUsed)
-    uint64_t inflate_out_limit = 0;  // output bytes one inflate batch may cover; 0 = scratch_limit
-    bool inf_limit_exact = false;    // the caller of zmi_inflate_impl sized inflate_out_limit from the capacities of THIS call (host wrappers)
+    uint64_t inflate_out_limit = 0;  // zmi_ctx_set_inflate_out_limit, written nowhere else: output bytes an inflate call that does not size
+                                     // its own scratch (zmi_inf_req::out_limit = 0) may cover; 0 = scratch_limit
     uint32_t inf_mw_max = 512u;      // inflate launches of up to this many streams give every stream a 16-wave workgroup (inflate.hip)
     hipStream_t host_stream = nullptr;  // zmi_ctx_set_stream: where the host-buffer wrappers copy and launch
     hipStream_t side = nullptr;         // deflate: the wrapper checksums run here, beside the match search (zmi_deflate_impl)
@@ -452,17 +441,21 @@ static uint32_t zmi_enc_regions(uint32_t max_len, uint64_t out_stride, uint32_t 
 // alone, slots that follow the data); out_stride must then hold that geometry's regions for max_len.
 // launch_n: the number of segments the small-launch rule below judges (0: n) -- the whole stream's when a stream is compressed in
 // several launch groups, so that the bytes do not depend on the grouping.
-static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
-                            uint32_t max_len, int level, int strategy, int wrap, uint32_t chain_mode, uint32_t dict_len,
-                            uint32_t window_bits, void* d_out, uint64_t out_stride, uint32_t* d_out_len, int32_t* d_status,
-                            void* stream_, int carry = -1, uint64_t launch_n = 0, const zmi_sd_deflate* sd = nullptr,
-                            const uint32_t* ends = nullptr, uint32_t geom_len = 0);
+struct zmi_def_req {   // (every call site names what it passes)
+    const void* d_in = nullptr; const uint64_t* d_in_off = nullptr; const uint32_t* d_in_len = nullptr; uint32_t n = 0, max_len = 0;   // the shards
+    int level = 0, strategy = 0, wrap = ZMI_WRAP_RAW; uint32_t chain_mode = 0, dict_len = 0, window_bits = 15;
+    void* d_out = nullptr; uint64_t out_stride = 0; uint32_t* d_out_len = nullptr; int32_t* d_status = nullptr;                         // the slots
+    void* stream = nullptr;
+    int carry = -1; uint64_t launch_n = 0; const zmi_sd_deflate* sd = nullptr; const uint32_t* ends = nullptr; uint32_t geom_len = 0;   // (above)
+};
+static int zmi_deflate_impl(zmi_ctx* c, const zmi_def_req& q);
 
 extern "C" int zmi_deflate_batch_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
                                      uint32_t n, uint32_t max_len, int level, int strategy, int wrap, void* d_out,
                                      uint64_t out_stride, uint32_t* d_out_len, int32_t* d_status, void* stream_) {
-    return zmi_deflate_impl(c, d_in, d_in_off, d_in_len, n, max_len, level, strategy, wrap, 0u, 0u, 15u, d_out, out_stride,
-                            d_out_len, d_status, stream_);
+    return zmi_deflate_impl(c, {.d_in = d_in, .d_in_off = d_in_off, .d_in_len = d_in_len, .n = n, .max_len = max_len, .level = level,
+                                .strategy = strategy, .wrap = wrap, .d_out = d_out, .out_stride = out_stride, .d_out_len = d_out_len,
+                                .d_status = d_status, .stream = stream_});
 }
 
 // Every shard as deflateInit2_ + deflateSetDictionary(dict) + deflate(Z_FINISH) (zlib-rs/src/deflate.rs:499-564), one dictionary
@@ -474,9 +467,9 @@ extern "C" int zmi_deflate_batch_shared_dict_dev(zmi_ctx* c, const void* d_in, c
                                                  int32_t* d_status, void* stream_) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (wrap != ZMI_WRAP_RAW && wrap != ZMI_WRAP_ZLIB) return zmi_fail(ZMI_E_ARG, "a preset dictionary needs wrap raw or zlib (a gzip member has no dictionary field)");
-    if (!d_dict || dict_len == 0u)
-        return zmi_deflate_impl(c, d_in, d_in_off, d_in_len, n, max_len, level, strategy, wrap, 0u, 0u, 15u, d_out, out_stride, d_out_len,
-                                d_status, stream_);
+    zmi_def_req q{.d_in = d_in, .d_in_off = d_in_off, .d_in_len = d_in_len, .n = n, .max_len = max_len, .level = level, .strategy = strategy,
+                  .wrap = wrap, .d_out = d_out, .out_stride = out_stride, .d_out_len = d_out_len, .d_status = d_status, .stream = stream_};
+    if (!d_dict || dict_len == 0u) return zmi_deflate_impl(c, q);
     if (level < -1 || level > 9) return zmi_fail(ZMI_E_ARG, "level must be -1..9");
     if (strategy < 0 || strategy > 4) return zmi_fail(ZMI_E_ARG, "strategy must be 0..4");
     if (out_stride % 16u || out_stride < zmi_deflate_dict_bound(max_len, wrap))
@@ -492,8 +485,8 @@ extern "C" int zmi_deflate_batch_shared_dict_dev(zmi_ctx* c, const void* d_in, c
         sd.img_len = img_len;
         sd.dictid = (const uint32_t*)((const uint8_t*)c->dict.p + ZMI_SD_DICTID);
     }
-    return zmi_deflate_impl(c, d_in, d_in_off, d_in_len, n, max_len, level, strategy, wrap, 0u, 0u, 15u, d_out, out_stride, d_out_len,
-                            d_status, stream_, -1, 0, &sd);
+    q.sd = &sd;
+    return zmi_deflate_impl(c, q);
 }
 
 // The shards are consecutive segments of ONE raw deflate stream, contiguous in d_in (d_in_off[i+1] = d_in_off[i] +
@@ -503,8 +496,9 @@ extern "C" int zmi_deflate_batch_shared_dict_dev(zmi_ctx* c, const void* d_in, c
 extern "C" int zmi_deflate_chain_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
                                      uint32_t n, uint32_t max_len, int level, int strategy, int finish, void* d_out,
                                      uint64_t out_stride, uint32_t* d_out_len, int32_t* d_status, void* stream_) {
-    return zmi_deflate_impl(c, d_in, d_in_off, d_in_len, n, max_len, level, strategy, ZMI_WRAP_RAW, finish ? 1u : 2u, 0u, 15u,
-                            d_out, out_stride, d_out_len, d_status, stream_);
+    return zmi_deflate_impl(c, {.d_in = d_in, .d_in_off = d_in_off, .d_in_len = d_in_len, .n = n, .max_len = max_len, .level = level,
+                                .strategy = strategy, .wrap = ZMI_WRAP_RAW, .chain_mode = finish ? 1u : 2u, .d_out = d_out,
+                                .out_stride = out_stride, .d_out_len = d_out_len, .d_status = d_status, .stream = stream_});
 }
 
 // As zmi_deflate_chain_dev; additionally the dict_len bytes in front of the first segment (d_in + d_in_off[0] -
@@ -514,8 +508,9 @@ extern "C" int zmi_deflate_chain_dict_dev(zmi_ctx* c, const void* d_in, const ui
                                           uint32_t n, uint32_t max_len, int level, int strategy, int finish, uint32_t dict_len,
                                           void* d_out, uint64_t out_stride, uint32_t* d_out_len, int32_t* d_status,
                                           void* stream_) {
-    return zmi_deflate_impl(c, d_in, d_in_off, d_in_len, n, max_len, level, strategy, ZMI_WRAP_RAW, finish ? 1u : 2u, dict_len,
-                            15u, d_out, out_stride, d_out_len, d_status, stream_);
+    return zmi_deflate_impl(c, {.d_in = d_in, .d_in_off = d_in_off, .d_in_len = d_in_len, .n = n, .max_len = max_len, .level = level,
+                                .strategy = strategy, .wrap = ZMI_WRAP_RAW, .chain_mode = finish ? 1u : 2u, .dict_len = dict_len, .d_out = d_out,
+                                .out_stride = out_stride, .d_out_len = d_out_len, .d_status = d_status, .stream = stream_});
 }
 
 // The chained form for a stream opened with windowBits < 15 (deflateInit2_, zlib-rs/src/deflate.rs:252-312): no
@@ -526,25 +521,25 @@ extern "C" int zmi_deflate_chain_window_dev(zmi_ctx* c, const void* d_in, const 
                                             uint32_t window_bits, void* d_out, uint64_t out_stride, uint32_t* d_out_len,
                                             int32_t* d_status, void* stream_) {
     if (window_bits < 9u || window_bits > 15u) return zmi_fail(ZMI_E_ARG, "window_bits must be 9..15");
-    return zmi_deflate_impl(c, d_in, d_in_off, d_in_len, n, max_len, level, strategy, ZMI_WRAP_RAW, finish ? 1u : 2u, dict_len,
-                            window_bits, d_out, out_stride, d_out_len, d_status, stream_);
+    return zmi_deflate_impl(c, {.d_in = d_in, .d_in_off = d_in_off, .d_in_len = d_in_len, .n = n, .max_len = max_len, .level = level,
+                                .strategy = strategy, .wrap = ZMI_WRAP_RAW, .chain_mode = finish ? 1u : 2u, .dict_len = dict_len, .window_bits = window_bits,
+                                .d_out = d_out, .out_stride = out_stride, .d_out_len = d_out_len, .d_status = d_status, .stream = stream_});
 }
 
-static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
-                            uint32_t max_len, int level, int strategy, int wrap, uint32_t chain_mode, uint32_t dict_len,
-                            uint32_t window_bits, void* d_out, uint64_t out_stride, uint32_t* d_out_len, int32_t* d_status,
-                            void* stream_, int carry, uint64_t launch_n, const zmi_sd_deflate* sd, const uint32_t* ends, uint32_t geom_len) {
+static int zmi_deflate_impl(zmi_ctx* c, const zmi_def_req& q) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
-    if (level == -1) level = 6;
+    const int level = q.level == -1 ? 6 : q.level;
+    const uint32_t n = q.n;
+    const zmi_sd_deflate* const sd = q.sd;
     if (level < 0 || level > 9) return zmi_fail(ZMI_E_ARG, "level must be -1..9");
-    if (strategy < 0 || strategy > 4) return zmi_fail(ZMI_E_ARG, "strategy must be 0..4");
-    if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_GZIP) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip");
-    if (out_stride % 16u || out_stride < (sd ? zmi_deflate_dict_bound(max_len, wrap) : zmi_deflate_bound(max_len, wrap)))
+    if (q.strategy < 0 || q.strategy > 4) return zmi_fail(ZMI_E_ARG, "strategy must be 0..4");
+    if (q.wrap < ZMI_WRAP_RAW || q.wrap > ZMI_WRAP_GZIP) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip");
+    if (q.out_stride % 16u || q.out_stride < (sd ? zmi_deflate_dict_bound(q.max_len, q.wrap) : zmi_deflate_bound(q.max_len, q.wrap)))
         return zmi_fail(ZMI_E_ARG, sd ? "out_stride must be a multiple of 16 and >= zmi_deflate_dict_bound(max_len)"
                                       : "out_stride must be a multiple of 16 and >= zmi_deflate_bound(max_len)");
-    if (out_stride > 0xFFFFFFF0ull) return zmi_fail(ZMI_E_ARG, "shards larger than 3.5 GiB are not supported");
+    if (q.out_stride > 0xFFFFFFF0ull) return zmi_fail(ZMI_E_ARG, "shards larger than 3.5 GiB are not supported");
     if (n == 0) return ZMI_E_OK;
-    hipStream_t stream = (hipStream_t)stream_;
+    hipStream_t stream = (hipStream_t)q.stream;
     ZMI_ON_DEVICE(c);
 
     // wrapper checksums
@@ -552,7 +547,7 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     if (rc) return rc;
     uint32_t* d_adler = (uint32_t*)c->sums.p;
     uint32_t* d_crc = d_adler + n;
-    uint32_t kind = wrap == ZMI_WRAP_ZLIB ? 1u : (wrap == ZMI_WRAP_GZIP ? 2u : 0u);
+    uint32_t kind = q.wrap == ZMI_WRAP_ZLIB ? 1u : (q.wrap == ZMI_WRAP_GZIP ? 2u : 0u);
     // The checksums are needed by the encoder's trailers only: they run on a side stream beside the match search (one is
     // HBM-bound, the other instruction-bound; in a launch of a few hundred shards the checksum kernel is one workgroup per
     // shard with nothing to hide its latency behind: 4.5 ms in front of 6.4 ms of lz77 for 512 shards) and join in front of
@@ -569,7 +564,7 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
         ZMI_HIP(hipStreamWaitEvent(c->side, c->ev_fork, 0));
         {
             zmi_scope_timer tm(c, ZMI_K_CHECKSUM, c->side);
-            zmi_launch_checksum((const uint8_t*)d_in, d_in_off, d_in_len, n, kind, d_adler, d_crc, c->side);
+            zmi_launch_checksum((const uint8_t*)q.d_in, q.d_in_off, q.d_in_len, n, kind, d_adler, d_crc, c->side);
         }
         ZMI_HIP(hipEventRecord(c->ev_join, c->side));
         forked = true;
@@ -581,7 +576,7 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     lp.nice_len = L.nice;
     lp.good_len = L.good;
     lp.max_dist = 32768u;  // clamped to the ring-buffer limit by the launcher
-    if (window_bits < 15u) lp.max_dist = (1u << window_bits) - 262u;   // w_size - MIN_LOOKAHEAD (deflate.rs:1423-1425)
+    if (q.window_bits < 15u) lp.max_dist = (1u << q.window_bits) - 262u;   // w_size - MIN_LOOKAHEAD (deflate.rs:1423-1425)
     lp.hash6 = 1u;  // 6-byte-hash chain + one 4-byte probe: ~1.5x fewer chain steps than a 4-byte chain at equal ratio
     lp.claim = 64u;
     const char* claim_env = zmi_tune("ZMI_CLAIM");
@@ -596,34 +591,34 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     ep.lazy3 = 2u;
     if (const char* l3 = zmi_tune("ZMI_LAZY3")) ep.lazy3 = (uint32_t)atoi(l3);
     if (const char* l2 = zmi_tune("ZMI_LAZY2")) ep.lazy2 = (uint32_t)atoi(l2);
-    ep.wrap = (uint32_t)wrap;
+    ep.wrap = (uint32_t)q.wrap;
     ep.level = (uint32_t)level;
     ep.block_span = 65536u;    // one encoder wave per 64 KiB piece, 16 per 1 MiB shard (128 KiB pieces: +0.15 % ratio, but 137 -> 161 ms
                                // per 16 Ki shards: fewer, longer waves fill the chip worse)
-    ep.strategy = (uint32_t)strategy;
-    ep.chain_mode = chain_mode;
+    ep.strategy = (uint32_t)q.strategy;
+    ep.chain_mode = q.chain_mode;
     ep.last_shard = n - 1u;
-    ep.ends = chain_mode == 2u ? ends : nullptr;
-    ep.dictid = (sd && wrap == ZMI_WRAP_ZLIB) ? sd->dictid : nullptr;
+    ep.ends = q.chain_mode == 2u ? q.ends : nullptr;
+    ep.dictid = (sd && q.wrap == ZMI_WRAP_ZLIB) ? sd->dictid : nullptr;
     if (level == 0) ep.strategy = 100u;           // stored blocks only (deflate_stored)
-    ep.cost_parse = (level >= 3 && strategy != 2) ? 1u : 0u;
+    ep.cost_parse = (level >= 3 && q.strategy != 2) ? 1u : 0u;
     if (const char* cp = zmi_tune("ZMI_COST_PARSE")) ep.cost_parse = atoi(cp) ? 1u : 0u;
-    if (strategy == 2) { lp.max_chain = 0; lp.max_dist = 0; }   // Z_HUFFMAN_ONLY: literals only -- with no distance allowed no
+    if (q.strategy == 2) { lp.max_chain = 0; lp.max_dist = 0; } // Z_HUFFMAN_ONLY: literals only -- with no distance allowed no
                                                                  // position gets a candidate (a zero chain budget alone still
                                                                  // examines the first one)
-    if (strategy == 3) lp.max_dist = 1;           // Z_RLE: distance-1 matches only
+    if (q.strategy == 3) lp.max_dist = 1;         // Z_RLE: distance-1 matches only
     const char* chain_env = zmi_tune("ZMI_CHAIN");  // tuning aid: override the chain budget of the selected level
-    if (chain_env && atoi(chain_env) > 0 && level > 0 && strategy != 2) lp.max_chain = (uint32_t)atoi(chain_env);
+    if (chain_env && atoi(chain_env) > 0 && level > 0 && q.strategy != 2) lp.max_chain = (uint32_t)atoi(chain_env);
     const char* good_env = zmi_tune("ZMI_GOOD");
     if (good_env && atoi(good_env) > 0) lp.good_len = (uint32_t)atoi(good_env);
     const char* nice_env = zmi_tune("ZMI_NICE");
     if (nice_env && atoi(nice_env) > 0) lp.nice_len = (uint32_t)atoi(nice_env);
     const char* lazy_env = zmi_tune("ZMI_LAZY");
     if (lazy_env && atoi(lazy_env) >= 0) ep.max_lazy = (uint32_t)atoi(lazy_env);
-    lp.carry = chain_mode != 0u ? 1u : 0u;   // segments of one stream: a segment sees the window in front of it
-    lp.dict_len = chain_mode != 0u ? dict_len : 0u;
-    if (const char* cv = zmi_tune("ZMI_CARRY")) lp.carry = (chain_mode != 0u && atoi(cv)) ? 1u : 0u;
-    if (carry >= 0) lp.carry = (chain_mode != 0u && carry) ? 1u : 0u;
+    lp.carry = q.chain_mode != 0u ? 1u : 0u;   // segments of one stream: a segment sees the window in front of it
+    lp.dict_len = q.chain_mode != 0u ? q.dict_len : 0u;
+    if (const char* cv = zmi_tune("ZMI_CARRY")) lp.carry = (q.chain_mode != 0u && atoi(cv)) ? 1u : 0u;
+    if (q.carry >= 0) lp.carry = (q.chain_mode != 0u && q.carry) ? 1u : 0u;
     // hash-building waves: 1 for the deep chains (the searchers are the whole kernel there), 2 for the short ones (14 searcher
     // waves outrun one producer: budget 5 measured 227 ms with two, 273 ms with one), 3 at level 1, whose searchers do so
     // little per position that even two producers set the pace (97.1 -> 95.2 ms per 16 Ki shards; at level 3 a third
@@ -660,14 +655,14 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     // many of them a launch holds, tests/test_gpu_parity.py::test_host_batch_pipeline_on_gpu)
     // (independent pieces of a single stream, carry 0, never: a piece's bytes depend on its own input alone, whichever GPU and
     // whichever launch compresses it -- zmi_deflate_stream_dev)
-    const bool small_launch = chain_mode != 0u && carry != 0 && (launch_n ? launch_n : n) * ((max_len + 65535u) / 65536u) < 512u;
+    const bool small_launch = q.chain_mode != 0u && q.carry != 0 && (q.launch_n ? q.launch_n : n) * ((q.max_len + 65535u) / 65536u) < 512u;
     if (small_launch) ep.block_span = 8192u;
     const char* span_env = zmi_tune("ZMI_BLOCK_SPAN");
     if (span_env && atoi(span_env) >= 64) ep.block_span = (uint32_t)atoi(span_env);
 
     // match/token scratch: one u32 per position, shards padded to a multiple of 64 positions; with the cost parse two more bits
     // per position behind it (its decisions, 16 bytes per 64 positions)
-    const uint64_t stride = ((uint64_t)max_len + 63u) & ~63ull;
+    const uint64_t stride = ((uint64_t)q.max_len + 63u) & ~63ull;
     uint64_t per_shard = (stride ? stride : 64u) * 4u;
     const uint64_t dec_bytes = ep.cost_parse ? per_shard / 16u : 0u;
     uint64_t group = c->scratch_limit / (per_shard + dec_bytes);
@@ -676,10 +671,10 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     rc = zmi_reserve(c->match, (size_t)(group * (per_shard + dec_bytes)));
     if (rc) return rc;
     uint32_t* const d_dec = ep.cost_parse ? (uint32_t*)((uint8_t*)c->match.p + group * per_shard) : nullptr;
-    uint32_t pieces = zmi_enc_regions(max_len, out_stride, ep.block_span, ep.block_tokens, sd != nullptr);
-    if (geom_len) {
-        pieces = zmi_enc_regions(geom_len, zmi_deflate_pieces_stride(geom_len), ep.block_span, ep.block_tokens, sd != nullptr);
-        if (((out_stride / pieces) & ~15ull) < zmi_enc_region_worst(max_len, pieces, ep.block_tokens, sd != nullptr))
+    uint32_t pieces = zmi_enc_regions(q.max_len, q.out_stride, ep.block_span, ep.block_tokens, sd != nullptr);
+    if (q.geom_len) {
+        pieces = zmi_enc_regions(q.geom_len, zmi_deflate_pieces_stride(q.geom_len), ep.block_span, ep.block_tokens, sd != nullptr);
+        if (((q.out_stride / pieces) & ~15ull) < zmi_enc_region_worst(q.max_len, pieces, ep.block_tokens, sd != nullptr))
             return zmi_fail(ZMI_E_ARG, "out_stride does not hold the regions of geom_len");
     }
     rc = zmi_reserve(c->pieces, (size_t)n * pieces * 4u);
@@ -689,22 +684,22 @@ static int zmi_deflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
         {
             zmi_scope_timer tm(c, ZMI_K_LZ77, stream);
             int lrc = (sd && sd->img_len)
-                          ? zmi_launch_lz77_dict((const uint8_t*)d_in, d_in_off, d_in_len, (uint32_t)first, cnt, (uint32_t*)c->match.p,
+                          ? zmi_launch_lz77_dict((const uint8_t*)q.d_in, q.d_in_off, q.d_in_len, (uint32_t)first, cnt, (uint32_t*)c->match.p,
                                                  per_shard / 4u, lp, sd->img, sd->img_len, stream)
-                          : zmi_launch_lz77((const uint8_t*)d_in, d_in_off, d_in_len, (uint32_t)first, cnt, (uint32_t*)c->match.p,
+                          : zmi_launch_lz77((const uint8_t*)q.d_in, q.d_in_off, q.d_in_len, (uint32_t)first, cnt, (uint32_t*)c->match.p,
                                             per_shard / 4u, lp, stream);
             if (lrc) return zmi_fail(ZMI_E_HIP, "lz77 launch setup", (hipError_t)lrc);
         }
         if (ep.cost_parse) {
             zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
-            zmi_launch_parse(d_in_len, (uint32_t)first, cnt, max_len, (const uint32_t*)c->match.p, per_shard / 4u, d_dec, dec_bytes / 4u, pieces,
-                             (uint32_t)strategy, small_launch ? 4u : 64u, stream);
+            zmi_launch_parse(q.d_in_len, (uint32_t)first, cnt, q.max_len, (const uint32_t*)c->match.p, per_shard / 4u, d_dec, dec_bytes / 4u, pieces,
+                             (uint32_t)q.strategy, small_launch ? 4u : 64u, stream);
         }
         if (forked) { ZMI_HIP(hipStreamWaitEvent(stream, c->ev_join, 0)); forked = false; }
         zmi_scope_timer tm2(c, ZMI_K_ENCODE, stream);
-        zmi_launch_encode((const uint8_t*)d_in, d_in_off, d_in_len, (uint32_t)first, cnt, (uint32_t*)c->match.p,
-                          per_shard / 4u, d_adler, d_crc, (uint8_t*)d_out, out_stride, (uint32_t)out_stride, d_out_len,
-                          d_status, pieces, (uint32_t*)c->pieces.p, d_dec, dec_bytes / 4u, ep, stream);
+        zmi_launch_encode((const uint8_t*)q.d_in, q.d_in_off, q.d_in_len, (uint32_t)first, cnt, (uint32_t*)c->match.p,
+                          per_shard / 4u, d_adler, d_crc, (uint8_t*)q.d_out, q.out_stride, (uint32_t)q.out_stride, q.d_out_len,
+                          q.d_status, pieces, (uint32_t*)c->pieces.p, d_dec, dec_bytes / 4u, ep, stream);
     }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;
@@ -754,8 +749,9 @@ extern "C" int zmi_deflate_pieces_dev(zmi_ctx* c, const void* d_in, const uint64
     hipStream_t stream = (hipStream_t)stream_;
     int rc = zmi_piece_checks(c, d_in, d_in_off, d_in_len, n, wrap, d_check, stream);
     if (rc) return rc;
-    return zmi_deflate_impl(c, d_in, d_in_off, d_in_len, n, max_len, level, strategy, ZMI_WRAP_RAW, final_piece ? 1u : 2u, 0u, 15u, d_out,
-                            out_stride, d_out_len, d_status, stream_, indep ? 0 : 1, 0u);
+    return zmi_deflate_impl(c, {.d_in = d_in, .d_in_off = d_in_off, .d_in_len = d_in_len, .n = n, .max_len = max_len, .level = level,
+                                .strategy = strategy, .wrap = ZMI_WRAP_RAW, .chain_mode = final_piece ? 1u : 2u, .d_out = d_out, .out_stride = out_stride,
+                                .d_out_len = d_out_len, .d_status = d_status, .stream = stream_, .carry = indep ? 0 : 1});
 }
 
 extern "C" int zmi_checksum_combine_dev(zmi_ctx* c, int wrap, const uint32_t* d_check, const uint32_t* d_len, uint32_t world,
@@ -859,9 +855,10 @@ extern "C" int zmi_deflate_stream_dev(zmi_ctx* c, const void* d_in, uint64_t n, 
         // carry-over across a group boundary: the group's first piece sees the history in front of it (lz77.hip reads it as
         // dict_len bytes in front of the launch's first segment; anything beyond the window is the same as a full window)
         const uint64_t before = indep ? 0u : first * (uint64_t)piece_bytes;
-        rc = zmi_deflate_impl(c, d_in, d_off + first, d_len + first, cnt, max_len, level, strategy, ZMI_WRAP_RAW, last ? 1u : 2u,
-                              (uint32_t)(before < 65536u ? before : 65536u), 15u, c->sd_slots.p, stride, d_olen + first, d_st + first,
-                              stream_, indep ? 0 : 1, np);
+        rc = zmi_deflate_impl(c, {.d_in = d_in, .d_in_off = d_off + first, .d_in_len = d_len + first, .n = cnt, .max_len = max_len, .level = level,
+                                  .strategy = strategy, .wrap = ZMI_WRAP_RAW, .chain_mode = last ? 1u : 2u,
+                                  .dict_len = (uint32_t)(before < 65536u ? before : 65536u), .d_out = c->sd_slots.p, .out_stride = stride,
+                                  .d_out_len = d_olen + first, .d_status = d_st + first, .stream = stream_, .carry = indep ? 0 : 1, .launch_n = np});
         if (rc) return rc;
         // the group's pieces go behind the previous group's, the running offset never leaves the device
         zmi_scope_timer tm(c, ZMI_K_PACK, stream);
@@ -916,8 +913,9 @@ static int zmi_bgzf_body(zmi_ctx* c, const void* d_in, const uint64_t* d_off, co
     if (rc) return rc;
     for (uint64_t first = 0; first < n; first += group) {
         const uint32_t cnt = (uint32_t)(n - first < group ? n - first : group);
-        rc = zmi_deflate_impl(c, d_in, d_off + first, d_len + first, cnt, max_len, level, strategy, ZMI_WRAP_RAW, 0u, 0u, 15u, c->sd_slots.p,
-                              stride, d_olen + first, d_st + first, stream);
+        rc = zmi_deflate_impl(c, {.d_in = d_in, .d_in_off = d_off + first, .d_in_len = d_len + first, .n = cnt, .max_len = max_len, .level = level,
+                                  .strategy = strategy, .wrap = ZMI_WRAP_RAW, .d_out = c->sd_slots.p, .out_stride = stride,
+                                  .d_out_len = d_olen + first, .d_status = d_st + first, .stream = stream});
         if (rc) return rc;
         // the group's blocks go behind the previous group's, the running offset never leaves the device
         zmi_scope_timer tm(c, ZMI_K_PACK, stream);
@@ -1100,8 +1098,10 @@ extern "C" int zmi_zip_write_dev(zmi_ctx* c, const void* d_in, const uint64_t* d
     for (uint64_t first = 0; first < np; first += group) {
         const uint32_t cnt = (uint32_t)(np - first < group ? np - first : group);
         if (level != 0) {
-            rc = zmi_deflate_impl(c, d_in, d_poff + first, d_plen + first, cnt, max_len, level, strategy, ZMI_WRAP_RAW, 2u, 0u, 15u, c->sd_slots.p,
-                                  stride, d_olen + first, d_st + first, stream_, 0, 0u, nullptr, d_ends + (first / group) * wpg, piece_bytes);
+            rc = zmi_deflate_impl(c, {.d_in = d_in, .d_in_off = d_poff + first, .d_in_len = d_plen + first, .n = cnt, .max_len = max_len,
+                                      .level = level, .strategy = strategy, .wrap = ZMI_WRAP_RAW, .chain_mode = 2u, .d_out = c->sd_slots.p,
+                                      .out_stride = stride, .d_out_len = d_olen + first, .d_status = d_st + first, .stream = stream_, .carry = 0,
+                                      .ends = d_ends + (first / group) * wpg, .geom_len = piece_bytes});
             if (rc) return rc;
         }
         // the group's pieces go behind the previous group's, the running offset never leaves the device
@@ -1131,22 +1131,9 @@ extern "C" int zmi_zip_write_dev(zmi_ctx* c, const void* d_in, const uint64_t* d
     return ZMI_E_OK;
 }
 
-// extended form used by the zlib stream ABI: also returns consumed input bytes and why a stream stopped
-extern "C" int zmi_inflate_batch_dict_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
-                                          uint32_t n, int wrap, void* d_out, const uint64_t* d_out_off,
-                                          const uint32_t* d_out_cap, const uint32_t* d_out_hist, uint32_t* d_out_len,
-                                          int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, void* stream_);
-extern "C" int zmi_inflate_batch_dev_ex(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
-                                        uint32_t n, int wrap, void* d_out, const uint64_t* d_out_off, const uint32_t* d_out_cap,
-                                        uint32_t* d_out_len, int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail,
-                                        void* stream_) {
-    return zmi_inflate_batch_dict_dev(c, d_in, d_in_off, d_in_len, n, wrap, d_out, d_out_off, d_out_cap, nullptr, d_out_len,
-                                      d_status, d_in_used, d_detail, stream_);
-}
-
 // The per-stream tables of one zmi_inflate_impl call in c->inf_tmp (32 bytes per stream): they stay valid on the stream until the next
 // inflate call on the context.  check = the trailer's value, adler / crc = those of the produced bytes (zmi_inflate_members_dev reads
-// them to tell a wrong CRC-32 from a wrong ISIZE).
+// them to tell a wrong CRC-32 from a wrong ISIZE).  This function is the one statement of the layout.
 struct zmi_inf_tables { uint64_t* bm_off; uint32_t *used, *check, *adler, *crc, *order; };
 static zmi_inf_tables zmi_inf_tables_of(zmi_ctx* c, uint32_t n) {
     zmi_inf_tables t;
@@ -1158,18 +1145,29 @@ static zmi_inf_tables zmi_inf_tables_of(zmi_ctx* c, uint32_t n) {
     t.order = t.crc + n;
     return t;
 }
-// d_out_hist (may be null): per stream, the number of bytes directly in front of its output region that hold a
-// preset dictionary (inflateSetDictionary, zlib-rs/src/inflate.rs:2492-2536; at most 32768 are ever referenced)
-static int zmi_inflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
-                            uint32_t n, int wrap, void* d_out, const uint64_t* d_out_off,
-                            const uint32_t* d_out_cap, const uint32_t* d_out_hist, uint32_t* d_out_len,
-                            int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, const uint32_t* d_in_bit,
-                            uint32_t* d_resume, void* stream_, bool decode_only = false, const zmi_sd_inflate* sd = nullptr,
-                            bool no_jump = false) {
+// What the core laid out for one launch, for the callers that go on with it (valid as the tables above): the bitmap, every stream's first
+// word in it, and check / adler / crc (a resumable decode leaves the size of its last dynamic block's tables in `check`: inflateCodesUsed).
+struct zmi_inf_scratch { const uint64_t *bitmap = nullptr, *bm_off = nullptr; const uint32_t *check = nullptr, *adler = nullptr, *crc = nullptr; };
+// One call of the core; every call site names what it passes.  d_out_hist (may be null): per stream, the bytes directly in front of its
+// output region that hold a preset dictionary (inflateSetDictionary, zlib-rs/src/inflate.rs:2492-2536; at most 32768 are ever referenced).
+struct zmi_inf_req {
+    const void* d_in = nullptr; const uint64_t* d_in_off = nullptr; const uint32_t* d_in_len = nullptr; uint32_t n = 0; int wrap = ZMI_WRAP_RAW;
+    void* d_out = nullptr; const uint64_t* d_out_off = nullptr; const uint32_t *d_out_cap = nullptr, *d_out_hist = nullptr;   // the regions
+    uint32_t* d_out_len = nullptr; int32_t* d_status = nullptr; uint32_t* d_in_used = nullptr; int32_t* d_detail = nullptr;   // the results
+    const uint32_t* d_in_bit = nullptr; uint32_t* d_resume = nullptr;   // the resumable decode (zmi_inflate_resume_dev)
+    void* stream = nullptr; const zmi_sd_inflate* sd = nullptr;
+    bool decode_only = false;            // the caller resolves (it stitches the segments of one stream first)
+    bool no_jump = false;                // never the jump resolve (a stream that is empty in all but a few calls)
+    uint64_t out_limit = 0;              // output bytes the bitmap must cover; 0: the context's setting (zmi_ctx_set_inflate_out_limit)
+    bool limit_exact = false;            // out_limit was sized from the capacities of THIS call
+    zmi_inf_scratch* scratch = nullptr;  // (may be null) filled in for the caller
+};
+static int zmi_inflate_impl(zmi_ctx* c, const zmi_inf_req& q) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
-    if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_AUTO) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip/auto");
+    if (q.wrap < ZMI_WRAP_RAW || q.wrap > ZMI_WRAP_AUTO) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip/auto");
+    const uint32_t n = q.n;
     if (n == 0) return ZMI_E_OK;
-    hipStream_t stream = (hipStream_t)stream_;
+    hipStream_t stream = (hipStream_t)q.stream;
     ZMI_ON_DEVICE(c);
     int rc = zmi_reserve(c->inf_tmp, (size_t)n * 32u);
     if (rc) return rc;
@@ -1180,24 +1178,27 @@ static int zmi_inflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     uint32_t* d_adler = tab.adler;
     uint32_t* d_crc = tab.crc;
     uint32_t* d_order = tab.order;   // workgroup -> stream: largest compressed size first (zmi_inflate_order_kernel)
-    if (d_in_used) d_used = d_in_used;
+    if (q.d_in_used) d_used = q.d_in_used;
+    const zmi_sd_inflate* const sd = q.sd;
+    const uint32_t* d_out_hist = q.d_out_hist;
     if (sd) {   // the decode pass reads no history: all it needs is every stream's `hist` for its distance check and the FDICT branch
         uint32_t* d_hist = d_order + n;
         zmi_launch_inflate_shared_hist(d_hist, n, sd->hist, stream);
         d_out_hist = d_hist;
     }
     // bitmap scratch: 1 bit per byte of output capacity (+2 words per stream).  The capacities live on the
-    // device, so the size comes from the context's limit; streams beyond it report Z_MEM_ERROR.
-    const uint64_t out_limit = c->inflate_out_limit ? c->inflate_out_limit : c->scratch_limit;
+    // device, so the size comes from the caller's limit or the context's; streams beyond it report Z_MEM_ERROR.
+    const uint64_t out_limit = q.out_limit ? q.out_limit : (c->inflate_out_limit ? c->inflate_out_limit : c->scratch_limit);
     rc = zmi_reserve(c->inf_bm, (size_t)(out_limit / 8u) + (size_t)n * 16u);
     if (rc) return rc;
+    if (q.scratch) *q.scratch = {(const uint64_t*)c->inf_bm.p, d_bm_off, d_check, d_adler, d_crc};
     const uint64_t bm_words = ((out_limit / 8u) + (uint64_t)n * 16u) / 8u;
     uint32_t mw_max = c->inf_mw_max;
     if (const char* mv = zmi_tune("ZMI_INF_MW_MAX")) mw_max = (uint32_t)atoi(mv);   // (tests: both selections, per call)
     {
         zmi_scope_timer tm(c, ZMI_K_INFLATE, stream);
-        int lrc = zmi_launch_inflate((const uint8_t*)d_in, d_in_off, d_in_len, n, (uint32_t)wrap, (uint8_t*)d_out, d_out_off, d_out_cap,
-                                     d_out_len, d_used, d_check, d_status, (uint64_t*)c->inf_bm.p, bm_words, d_bm_off, d_out_hist, d_in_bit, d_resume,
+        int lrc = zmi_launch_inflate((const uint8_t*)q.d_in, q.d_in_off, q.d_in_len, n, (uint32_t)q.wrap, (uint8_t*)q.d_out, q.d_out_off, q.d_out_cap,
+                                     q.d_out_len, d_used, d_check, q.d_status, (uint64_t*)c->inf_bm.p, bm_words, d_bm_off, d_out_hist, q.d_in_bit, q.d_resume,
                                      d_order, mw_max, stream);
         if (lrc) return zmi_fail(ZMI_E_HIP, "inflate launch setup", (hipError_t)lrc);
     }
@@ -1207,18 +1208,18 @@ static int zmi_inflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
     // (below 256 KiB of capacity the serial pass takes less than the jump pass's two dozen launches)
     // (the pass sweeps out_limit indices whatever the streams' real capacities are -- they are device data: a limit far above what n
     // streams plausibly hold, 64 MiB each, says the caller did not size it for this call, and the serial pass is the safer choice)
-    // (callers that sized the limit from this call's capacities -- zmi_inflate_resume, the host-buffer batch -- are exact: one stream of
-    // several hundred MiB keeps the jump pass)
-    // (round 6: ONE stream whose limit was sized for this call -- a streaming inflate() of the zlib ABI, zmi_inflate_resume -- takes the
-    // jump pass from 64 KiB on: its serial pass is one wave alone on the chip, 389 us for the ~40 KiB of an open block, against a dozen
-    // launches of a few microseconds; the reference's chunk sweep at 1 / 4 / 16 / 64 KiB pieces: 0.90 / 0.248 / 0.069 / 0.020 s ->
-    // 0.59 / 0.153 / 0.046 / 0.018 s for 4 MiB, profiles/r06_eager_inflate_trace.txt)
-    const uint64_t jump_min = (n == 1u && c->inf_limit_exact) ? (64ull << 10) : (256ull << 10);
+    // (limit_exact, callers that sized the limit from this call's capacities -- zmi_inflate_resume, the packed calls, the plain host-buffer
+    // batch; not the pipelined one, sized once for its largest chunk: one stream of several hundred MiB keeps the jump pass)
+    // (round 6: ONE stream under an exact limit -- a streaming inflate() of the zlib ABI, zmi_inflate_resume -- always takes the jump pass
+    // (an exact limit is a capacity plus 64 KiB or more: jump_min never filters it): its serial pass is one wave alone on the chip, 389 us
+    // for the ~40 KiB of an open block, against a dozen launches of a few microseconds; the reference's chunk sweep at 1 / 4 / 16 / 64 KiB
+    // pieces: 0.90 / 0.248 / 0.069 / 0.020 s -> 0.59 / 0.153 / 0.046 / 0.018 s for 4 MiB, profiles/r06_eager_inflate_trace.txt)
+    const uint64_t jump_min = (n == 1u && q.limit_exact) ? (64ull << 10) : (256ull << 10);
     bool jump = n <= 16u && out_limit <= (1ull << 30) && out_limit >= jump_min &&
-                (c->inf_limit_exact || out_limit <= (uint64_t)n * (64ull << 20) + (1ull << 20));
-    if (!decode_only) {
+                (q.limit_exact || out_limit <= (uint64_t)n * (64ull << 20) + (1ull << 20));
+    if (!q.decode_only) {
     if (const char* jv = zmi_tune("ZMI_INF_JUMP")) jump = atoi(jv) != 0 && out_limit <= (1ull << 30);
-    if (no_jump) jump = false;   // (the caller's stream is empty in all but a few calls: the jump resolve would sweep the limit for nothing)
+    if (q.no_jump) jump = false;   // (the caller's stream is empty in all but a few calls: the jump resolve would sweep the limit for nothing)
     if (sd) jump = false;   // the shared dictionary is read by the one-wave-per-stream pass only (its case is many small streams)
     if (jump && zmi_reserve(c->inf_ptr, (size_t)bm_words * 256u + 512u) != 0) jump = false;   // (no room: the serial pass needs none)
     {
@@ -1227,32 +1228,49 @@ static int zmi_inflate_impl(zmi_ctx* c, const void* d_in, const uint64_t* d_in_o
         if (jump) {
             uint32_t rounds = 2u;   // ceil(log3(capacity)) + 1: a round follows two pointers (resolve_jump.hip)
             for (uint64_t span = 3u; rounds < 34u && span < out_limit; span *= 3u) ++rounds;
-            lrc = zmi_launch_resolve_jump((uint8_t*)d_out, d_out_off, d_out_len, n, (const uint64_t*)c->inf_bm.p, d_bm_off, (int32_t*)c->inf_ptr.p,
+            lrc = zmi_launch_resolve_jump((uint8_t*)q.d_out, q.d_out_off, q.d_out_len, n, (const uint64_t*)c->inf_bm.p, d_bm_off, (int32_t*)c->inf_ptr.p,
                                           bm_words * 64ull, rounds, (uint32_t*)((uint8_t*)c->inf_ptr.p + (size_t)bm_words * 256u), stream);
         } else if (sd) {
-            lrc = zmi_launch_inflate_resolve_shared((uint8_t*)d_out, d_out_off, d_out_len, n, (const uint64_t*)c->inf_bm.p, d_bm_off, d_order,
+            lrc = zmi_launch_inflate_resolve_shared((uint8_t*)q.d_out, q.d_out_off, q.d_out_len, n, (const uint64_t*)c->inf_bm.p, d_bm_off, d_order,
                                                     sd->img, sd->hist, stream);
         } else {
-            lrc = zmi_launch_inflate_resolve((uint8_t*)d_out, d_out_off, d_out_len, n, (const uint64_t*)c->inf_bm.p, d_bm_off, d_out_hist, d_order, stream);
+            lrc = zmi_launch_inflate_resolve((uint8_t*)q.d_out, q.d_out_off, q.d_out_len, n, (const uint64_t*)c->inf_bm.p, d_bm_off, d_out_hist, d_order, stream);
         }
         if (lrc) return zmi_fail(ZMI_E_HIP, "inflate resolve launch setup", (hipError_t)lrc);
     }
     }   // (decode_only: the caller resolves -- zmi_inflate_split stitches the segments of one stream first)
-    if (wrap != ZMI_WRAP_RAW) {
-        uint32_t kind = wrap == ZMI_WRAP_ZLIB ? 1u : (wrap == ZMI_WRAP_GZIP ? 2u : 3u);
+    if (q.wrap != ZMI_WRAP_RAW) {
+        uint32_t kind = q.wrap == ZMI_WRAP_ZLIB ? 1u : (q.wrap == ZMI_WRAP_GZIP ? 2u : 3u);
         zmi_scope_timer tm(c, ZMI_K_CHECKSUM, stream);
-        zmi_launch_checksum((const uint8_t*)d_out, d_out_off, d_out_len, n, kind, d_adler, d_crc, stream);
+        zmi_launch_checksum((const uint8_t*)q.d_out, q.d_out_off, q.d_out_len, n, kind, d_adler, d_crc, stream);
     }
     {
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
-        zmi_launch_inflate_verify((const uint8_t*)d_in, d_in_off, d_in_len, n, (uint32_t)wrap, d_check, d_adler, d_crc, d_status,
-                                  d_detail, stream);
+        zmi_launch_inflate_verify((const uint8_t*)q.d_in, q.d_in_off, q.d_in_len, n, (uint32_t)q.wrap, d_check, d_adler, d_crc, q.d_status,
+                                  q.d_detail, stream);
         // inflateSetDictionary refuses a dictionary whose Adler-32 is not the stream's DICTID (inflate.rs:2492-2536)
-        if (sd && wrap == ZMI_WRAP_ZLIB)
-            zmi_launch_inflate_dictid((const uint8_t*)d_in, d_in_off, d_in_len, n, sd->dictid, d_status, d_detail, d_out_len, stream);
+        if (sd && q.wrap == ZMI_WRAP_ZLIB)
+            zmi_launch_inflate_dictid((const uint8_t*)q.d_in, q.d_in_off, q.d_in_len, n, sd->dictid, q.d_status, q.d_detail, q.d_out_len, stream);
     }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;
+}
+
+// The request with one preset dictionary for all its streams (dict_len > 0, n > 0, wrap raw or zlib: the callers saw to that).
+static int zmi_inflate_shared_dict(zmi_ctx* c, zmi_inf_req q, const void* d_dict, uint32_t dict_len) {
+    zmi_sd_inflate sd;
+    {
+        ZMI_ON_DEVICE(c);
+        const uint32_t hist = dict_len < 32768u ? dict_len : 32768u;
+        const uint32_t shift = (hist + 1023u) & ~1023u;   // the resolve pass's staging block (RES_BLK, inflate.hip)
+        int rc = zmi_sd_prepare(c, d_dict, dict_len, true, q.wrap == ZMI_WRAP_ZLIB, (hipStream_t)q.stream, shift - hist, hist, 32u);
+        if (rc) return rc;
+        sd.img = (const uint8_t*)c->dict.p + ZMI_SD_INF_IMG;
+        sd.hist = hist;
+        sd.dictid = (const uint32_t*)((const uint8_t*)c->dict.p + ZMI_SD_DICTID);
+    }
+    q.sd = &sd;
+    return zmi_inflate_impl(c, q);
 }
 
 // Every stream as inflateInit2_ + inflateSetDictionary(dict) + inflate(Z_FINISH), one dictionary for the whole call; see
@@ -1263,30 +1281,28 @@ extern "C" int zmi_inflate_batch_shared_dict_dev(zmi_ctx* c, const void* d_in, c
                                                  int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, void* stream_) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (wrap != ZMI_WRAP_RAW && wrap != ZMI_WRAP_ZLIB) return zmi_fail(ZMI_E_ARG, "a preset dictionary needs wrap raw or zlib (a gzip member has no dictionary field)");
-    if (!d_dict || dict_len == 0u || n == 0u)
-        return zmi_inflate_impl(c, d_in, d_in_off, d_in_len, n, wrap, d_out, d_out_off, d_out_cap, nullptr, d_out_len, d_status, d_in_used,
-                                d_detail, nullptr, nullptr, stream_);
-    zmi_sd_inflate sd;
-    {
-        ZMI_ON_DEVICE(c);
-        const uint32_t hist = dict_len < 32768u ? dict_len : 32768u;
-        const uint32_t shift = (hist + 1023u) & ~1023u;   // the resolve pass's staging block (RES_BLK, inflate.hip)
-        int rc = zmi_sd_prepare(c, d_dict, dict_len, true, wrap == ZMI_WRAP_ZLIB, (hipStream_t)stream_, shift - hist, hist, 32u);
-        if (rc) return rc;
-        sd.img = (const uint8_t*)c->dict.p + ZMI_SD_INF_IMG;
-        sd.hist = hist;
-        sd.dictid = (const uint32_t*)((const uint8_t*)c->dict.p + ZMI_SD_DICTID);
-    }
-    return zmi_inflate_impl(c, d_in, d_in_off, d_in_len, n, wrap, d_out, d_out_off, d_out_cap, nullptr, d_out_len, d_status, d_in_used,
-                            d_detail, nullptr, nullptr, stream_, false, &sd);
+    const zmi_inf_req q{.d_in = d_in, .d_in_off = d_in_off, .d_in_len = d_in_len, .n = n, .wrap = wrap, .d_out = d_out, .d_out_off = d_out_off,
+                        .d_out_cap = d_out_cap, .d_out_len = d_out_len, .d_status = d_status, .d_in_used = d_in_used, .d_detail = d_detail,
+                        .stream = stream_};
+    if (!d_dict || dict_len == 0u || n == 0u) return zmi_inflate_impl(c, q);
+    return zmi_inflate_shared_dict(c, q, d_dict, dict_len);
 }
 
+// extended forms used by the zlib stream ABI: also return consumed input bytes and why a stream stopped
 extern "C" int zmi_inflate_batch_dict_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
                                           uint32_t n, int wrap, void* d_out, const uint64_t* d_out_off,
                                           const uint32_t* d_out_cap, const uint32_t* d_out_hist, uint32_t* d_out_len,
                                           int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, void* stream_) {
-    return zmi_inflate_impl(c, d_in, d_in_off, d_in_len, n, wrap, d_out, d_out_off, d_out_cap, d_out_hist, d_out_len, d_status,
-                            d_in_used, d_detail, nullptr, nullptr, stream_);
+    return zmi_inflate_impl(c, {.d_in = d_in, .d_in_off = d_in_off, .d_in_len = d_in_len, .n = n, .wrap = wrap, .d_out = d_out,
+                                .d_out_off = d_out_off, .d_out_cap = d_out_cap, .d_out_hist = d_out_hist, .d_out_len = d_out_len,
+                                .d_status = d_status, .d_in_used = d_in_used, .d_detail = d_detail, .stream = stream_});
+}
+extern "C" int zmi_inflate_batch_dev_ex(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                                        uint32_t n, int wrap, void* d_out, const uint64_t* d_out_off, const uint32_t* d_out_cap,
+                                        uint32_t* d_out_len, int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail,
+                                        void* stream_) {
+    return zmi_inflate_batch_dict_dev(c, d_in, d_in_off, d_in_len, n, wrap, d_out, d_out_off, d_out_cap, nullptr, d_out_len,
+                                      d_status, d_in_used, d_detail, stream_);
 }
 
 // Resumable raw-deflate decode (the device half of a streaming inflate; the facts the reference keeps in
@@ -1302,8 +1318,9 @@ extern "C" int zmi_inflate_resume_dev(zmi_ctx* c, const void* d_in, const uint64
                                       int32_t* d_status, uint32_t* d_in_used, int32_t* d_detail, uint32_t* d_resume,
                                       void* stream_) {
     if (!d_resume) return zmi_fail(ZMI_E_ARG, "d_resume is required");
-    return zmi_inflate_impl(c, d_in, d_in_off, d_in_len, n, ZMI_WRAP_RAW, d_out, d_out_off, d_out_cap, d_out_hist, d_out_len,
-                            d_status, d_in_used, d_detail, d_in_bit, d_resume, stream_);
+    return zmi_inflate_impl(c, {.d_in = d_in, .d_in_off = d_in_off, .d_in_len = d_in_len, .n = n, .wrap = ZMI_WRAP_RAW, .d_out = d_out,
+                                .d_out_off = d_out_off, .d_out_cap = d_out_cap, .d_out_hist = d_out_hist, .d_out_len = d_out_len, .d_status = d_status,
+                                .d_in_used = d_in_used, .d_detail = d_detail, .d_in_bit = d_in_bit, .d_resume = d_resume, .stream = stream_});
 }
 
 extern "C" int zmi_inflate_batch_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
@@ -1363,15 +1380,10 @@ static int zmi_inflate_packed_body(zmi_ctx* c, const void* d_in, const uint64_t*
     }
     // the bitmap scratch covers what the planned capacities can sum to: out_cap (no stream holds more than 2^32 - 1 bytes)
     const uint64_t most = (uint64_t)n * 0xFFFFFFFFull;
-    const uint64_t saved_limit = c->inflate_out_limit;
-    c->inflate_out_limit = (out_cap < most ? out_cap : most) + (1ull << 16);
-    c->inf_limit_exact = true;
-    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; c->inf_limit_exact = false; } } restore_limit{c, saved_limit};
-    int rc;
-    if (d_dict) rc = zmi_inflate_batch_shared_dict_dev(c, d_in, d_in_off, d_in_len, n, wrap, d_dict, dict_len, d_out, d_out_off, d_cap, d_out_len,
-                                                       d_status, d_in_used, d_detail, stream_);
-    else rc = zmi_inflate_impl(c, d_in, d_in_off, d_in_len, n, wrap, d_out, d_out_off, d_cap, nullptr, d_out_len, d_status, d_in_used, d_detail,
-                               nullptr, nullptr, stream_);
+    const zmi_inf_req q{.d_in = d_in, .d_in_off = d_in_off, .d_in_len = d_in_len, .n = n, .wrap = wrap, .d_out = d_out, .d_out_off = d_out_off,
+                        .d_out_cap = d_cap, .d_out_len = d_out_len, .d_status = d_status, .d_in_used = d_in_used, .d_detail = d_detail,
+                        .stream = stream_, .out_limit = (out_cap < most ? out_cap : most) + (1ull << 16), .limit_exact = true};
+    const int rc = d_dict ? zmi_inflate_shared_dict(c, q, d_dict, dict_len) : zmi_inflate_impl(c, q);
     if (rc) return rc;
     zmi_launch_inflate_pack_mark(d_size, d_out_off, n, out_cap, d_out_len, d_status, d_in_used, d_detail, stream);
     return ZMI_E_OK;
@@ -1567,10 +1579,6 @@ static int zmi_deflate_batch_simple(zmi_ctx* c, const uint8_t* in, const uint64_
 extern "C" int zmi_inflate_resume(zmi_ctx* c, const uint8_t* in, uint32_t in_len, uint32_t in_bit, const uint8_t* hist,
                                   uint32_t hist_len, uint8_t* out, uint32_t out_cap, uint32_t* out_len, int32_t* status,
                                   int32_t* detail, uint32_t* in_used, uint32_t* resume);
-extern "C" int zmi_launch_resolve_jump_segments(uint8_t* d_fin, const uint64_t* d_soff, uint32_t nseg, const uint64_t* d_bitmap,
-                                                const uint64_t* d_bm_off, int32_t* d_ptr, uint64_t total, uint32_t hist_len,
-                                                uint32_t rounds, uint32_t* d_flags, uint32_t* d_err, const uint64_t* d_one_off,
-                                                const uint32_t* d_one_len, hipStream_t stream);
 // Device -> caller's (pageable) memory for the single-stream paths.  hipMemcpy into pageable memory is the runtime's own bounce
 // through a small pinned buffer, one thread, 2-4 GB/s: the 15 MiB of a decoded stream took longer to leave the device than to
 // decode (measured: 6.4 of 7.5 ms).  Here the bytes go out in 4 MiB pieces through two pinned buffers of the context -- the DMA of
@@ -1645,17 +1653,18 @@ static int zmi_split_core(zmi_ctx* c, const uint8_t* in, uint32_t in_len, uint32
     if (!in_on_device) ZMI_HIPS(hipMemcpyAsync(c->st_in.p, in, in_len, hipMemcpyHostToDevice, hs));
     if (hist_len) ZMI_HIPS(hipMemcpyAsync((uint8_t*)c->st_out.p + base - hist_len, hist, hist_len, hipMemcpyHostToDevice, hs));
     ZMI_HIPS(hipMemcpyAsync(d, hm.data(), meta_bytes, hipMemcpyHostToDevice, hs));
-    const uint64_t saved_limit = c->inflate_out_limit;
-    c->inflate_out_limit = scratch + (1ull << 16);
-    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; } } restore_limit{c, saved_limit};
-    rc = zmi_inflate_impl(c, c->st_in.p, (const uint64_t*)(d + o_ioff), (const uint32_t*)(d + o_ilen), nseg, ZMI_WRAP_RAW, c->sp_out.p,
-                          (const uint64_t*)(d + o_ooff), (const uint32_t*)(d + o_ocap), (const uint32_t*)(d + o_hist), (uint32_t*)(d + o_olen),
-                          (int32_t*)(d + o_st), (uint32_t*)(d + o_used), (int32_t*)(d + o_det), (const uint32_t*)(d + o_bit), (uint32_t*)(d + o_res), hs, true);
+    zmi_inf_scratch dec;   // (the decode's bitmap goes to the stitch below)
+    rc = zmi_inflate_impl(c, {.d_in = c->st_in.p, .d_in_off = (const uint64_t*)(d + o_ioff), .d_in_len = (const uint32_t*)(d + o_ilen), .n = nseg,
+                              .wrap = ZMI_WRAP_RAW, .d_out = c->sp_out.p, .d_out_off = (const uint64_t*)(d + o_ooff),
+                              .d_out_cap = (const uint32_t*)(d + o_ocap), .d_out_hist = (const uint32_t*)(d + o_hist),
+                              .d_out_len = (uint32_t*)(d + o_olen), .d_status = (int32_t*)(d + o_st), .d_in_used = (uint32_t*)(d + o_used),
+                              .d_detail = (int32_t*)(d + o_det), .d_in_bit = (const uint32_t*)(d + o_bit), .d_resume = (uint32_t*)(d + o_res),
+                              .stream = hs, .decode_only = true, .out_limit = scratch + (1ull << 16), .scratch = &dec});
     if (rc) { (void)hipStreamSynchronize(hs); return rc; }
     std::vector<uint32_t> r(8 * n), codes(nseg, 0u);   // olen | status | used | detail | resume[4n]
     ZMI_HIPS(hipMemcpyAsync(r.data(), d + o_olen, 32 * n, hipMemcpyDeviceToHost, hs));
-    // (zmi_inflate_impl's scratch: bm_off u64[nseg] | used[nseg] | check[nseg] -- every segment's tables' size, see zmi_inflate_resume)
-    ZMI_HIPS(hipMemcpyAsync(codes.data(), (const uint8_t*)c->inf_tmp.p + 12u * (size_t)nseg, 4u * (size_t)nseg, hipMemcpyDeviceToHost, hs));
+    // (every segment's tables' size, see zmi_inflate_resume)
+    ZMI_HIPS(hipMemcpyAsync(codes.data(), dec.check, 4u * (size_t)nseg, hipMemcpyDeviceToHost, hs));
     ZMI_HIPS(hipStreamSynchronize(hs));
     const double sp_t1 = sp_trace ? sp_now() : 0.0;
     uint32_t* olen = r.data();
@@ -1707,8 +1716,7 @@ static int zmi_split_core(zmi_ctx* c, const uint8_t* in, uint32_t in_len, uint32
     for (uint64_t span = 3u; rounds < 34u && span < total; span *= 3u) ++rounds;
     {
         zmi_scope_timer tm(c, ZMI_K_RESOLVE, hs);
-        zmi_launch_resolve_jump_segments(d_fin, (const uint64_t*)(d + o_soff), take, (const uint64_t*)c->inf_bm.p, (const uint64_t*)c->inf_tmp.p,
-                                         (int32_t*)c->inf_ptr.p, total, hist_len, rounds, (uint32_t*)((uint8_t*)c->inf_ptr.p + (size_t)total * 4u),
+        zmi_launch_resolve_jump_segments(d_fin, (const uint64_t*)(d + o_soff), take, dec.bitmap, dec.bm_off, (int32_t*)c->inf_ptr.p, total, hist_len, rounds, (uint32_t*)((uint8_t*)c->inf_ptr.p + (size_t)total * 4u),
                                          (uint32_t*)(d + o_one + 12), (const uint64_t*)(d + o_one), (const uint32_t*)(d + o_one + 8), hs);
     }
     uint32_t err = 0;
@@ -1767,8 +1775,6 @@ extern "C" int zmi_inflate_split(zmi_ctx* c, const uint8_t* in, uint32_t in_len,
 // side and stitched as zmi_inflate_split does -- with the same discipline: a cut counts only if the decode in front of it
 // ended exactly there.  Results equal zmi_inflate_resume on the same arguments; *segments_used = 0 says the serial path ran
 // (too few boundaries found, or the first cut did not check out).
-extern "C" int zmi_launch_block_scan(const uint8_t* d_in, uint32_t n, uint64_t first_bit, uint32_t* d_pre, uint32_t pre_cap, uint32_t* d_list,
-                                     uint32_t cap, uint32_t* d_count, hipStream_t stream);
 static int zmi_inflate_blocks_body(zmi_ctx* c, const uint8_t* in, uint32_t in_len, uint32_t in_bit, const uint8_t* hist, uint32_t hist_len,
                                    uint8_t* out, uint32_t out_cap, uint32_t* out_len, int32_t* status, int32_t* detail, uint32_t* in_used,
                                    uint32_t* resume, uint32_t* segments_used) {
@@ -2249,10 +2255,6 @@ static int zmi_inflate_batch_simple(zmi_ctx* c, const uint8_t* in, const uint64_
         dooff[i] = tout;
         tout += ((uint64_t)out_cap[i] + 15u) & ~15ull;
     }
-    const uint64_t saved_limit = c->inflate_out_limit;
-    c->inflate_out_limit = tout + (1ull << 20);   // the capacities are known here: size the bitmap scratch exactly
-    c->inf_limit_exact = true;
-    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; c->inf_limit_exact = false; } } restore_limit{c, saved_limit};
     zmi_dev_alloc A;
     uint8_t* d_in = (uint8_t*)A.get(tin + 16);
     uint8_t* d_out = (uint8_t*)A.get(tout + 16);
@@ -2270,7 +2272,9 @@ static int zmi_inflate_batch_simple(zmi_ctx* c, const uint8_t* in, const uint64_
     ZMI_HIP(hipMemcpy(d_ooff, dooff.data(), (size_t)n * 8, hipMemcpyHostToDevice));
     ZMI_HIP(hipMemcpy(d_ilen, in_len, (size_t)n * 4, hipMemcpyHostToDevice));
     ZMI_HIP(hipMemcpy(d_ocap, out_cap, (size_t)n * 4, hipMemcpyHostToDevice));
-    int rc = zmi_inflate_batch_dev(c, d_in, d_ioff, d_ilen, n, wrap, d_out, d_ooff, d_ocap, d_olen, d_st, nullptr);
+    // (the capacities are known here: the bitmap scratch is sized exactly)
+    int rc = zmi_inflate_impl(c, {.d_in = d_in, .d_in_off = d_ioff, .d_in_len = d_ilen, .n = n, .wrap = wrap, .d_out = d_out, .d_out_off = d_ooff,
+                                  .d_out_cap = d_ocap, .d_out_len = d_olen, .d_status = d_st, .out_limit = tout + (1ull << 20), .limit_exact = true});
     if (rc) return rc;
     ZMI_HIP(hipDeviceSynchronize());
     ZMI_HIP(hipMemcpy(out_len, d_olen, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -2371,9 +2375,6 @@ static int zmi_inflate_batch_body(zmi_ctx* c, const uint8_t* in, const uint64_t*
             return zmi_inflate_batch_simple(c, in, in_off, in_len, n, wrap, out, out_off, out_cap, out_len, status);
         }
     }
-    const uint64_t saved_limit = c->inflate_out_limit;
-    c->inflate_out_limit = max_out + (1ull << 20);   // bitmap scratch for the largest chunk, once
-    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; } } restore_limit{c, saved_limit};
     auto m_ioff = [&](void* b) { return (uint64_t*)b; };
     auto m_ooff = [&](void* b) { return (uint64_t*)((uint8_t*)b + (size_t)max_count * 8u); };
     auto m_ilen = [&](void* b) { return (uint32_t*)((uint8_t*)b + (size_t)max_count * 16u); };
@@ -2420,8 +2421,10 @@ static int zmi_inflate_batch_body(zmi_ctx* c, const uint8_t* in, const uint64_t*
         ZMI_HIP(hipEventRecord(sl.in_done, c->hs_in));
         ZMI_HIP(hipStreamWaitEvent(c->hs_k, sl.in_done, 0));
         if (k >= ZMI_HB_SLOTS) ZMI_HIP(hipStreamWaitEvent(c->hs_k, out_done[s2], 0));   // the slot's output has left the device
-        int r = zmi_inflate_batch_dev(c, sl.in.p, m_ioff(sl.meta.p), m_ilen(sl.meta.p), ck.count, wrap, sl.out.p, m_ooff(sl.meta.p),
-                                      m_ocap(sl.meta.p), m_olen(sl.meta.p), m_st(sl.meta.p), c->hs_k);
+        int r = zmi_inflate_impl(c, {.d_in = sl.in.p, .d_in_off = m_ioff(sl.meta.p), .d_in_len = m_ilen(sl.meta.p), .n = ck.count, .wrap = wrap,
+                                     .d_out = sl.out.p, .d_out_off = m_ooff(sl.meta.p), .d_out_cap = m_ocap(sl.meta.p), .d_out_len = m_olen(sl.meta.p),
+                                     .d_status = m_st(sl.meta.p), .stream = c->hs_k,
+                                     .out_limit = max_out + (1ull << 20)});   // (the bitmap scratch of the largest chunk for every chunk: not exact)
         if (r) return r;
         ZMI_HIP(hipEventRecord(sl.k_done, c->hs_k));
         ZMI_HIP(hipStreamWaitEvent(c->hs_slab, sl.k_done, 0));
@@ -2504,7 +2507,7 @@ static int zmi_inflate_batch_body(zmi_ctx* c, const uint8_t* in, const uint64_t*
     return ZMI_E_OK;
 }
 
-// One host stream through zmi_inflate_resume_dev: `in` (raw deflate, starting at bit in_bit of its first byte),
+// One host stream through the decode zmi_inflate_resume_dev runs: `in` (raw deflate, starting at bit in_bit of its first byte),
 // `hist` = the up to 32 KiB of output in front of it.  The staging buffers belong to the context and are reused,
 // a streaming caller pays no allocation per call.  out receives min(*out_len, out_cap) bytes.
 extern "C" int zmi_inflate_resume(zmi_ctx* c, const uint8_t* in, uint32_t in_len, uint32_t in_bit, const uint8_t* hist,
@@ -2527,18 +2530,18 @@ extern "C" int zmi_inflate_resume(zmi_ctx* c, const uint8_t* in, uint32_t in_len
     struct { uint64_t in_off, out_off; uint32_t in_len, out_cap, hist, in_bit; } m = {0, (uint64_t)base, in_len, out_cap, hist_len, in_bit};
     uint8_t* d = (uint8_t*)c->st_meta.p;
     ZMI_HIP(hipMemcpyAsync(d, &m, sizeof(m), hipMemcpyHostToDevice, hs));
-    const uint64_t saved_limit = c->inflate_out_limit;
-    c->inflate_out_limit = (uint64_t)out_cap + (1ull << 16);
-    c->inf_limit_exact = true;
-    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; c->inf_limit_exact = false; } } restore_limit{c, saved_limit};
-    rc = zmi_inflate_resume_dev(c, c->st_in.p, (const uint64_t*)d, (const uint32_t*)(d + 16), (const uint32_t*)(d + 28), 1, c->st_out.p,
-                                (const uint64_t*)(d + 8), (const uint32_t*)(d + 20), (const uint32_t*)(d + 24), (uint32_t*)(d + 32),
-                                (int32_t*)(d + 36), (uint32_t*)(d + 40), (int32_t*)(d + 44), (uint32_t*)(d + 48), hs);
+    zmi_inf_scratch dec;
+    rc = zmi_inflate_impl(c, {.d_in = c->st_in.p, .d_in_off = (const uint64_t*)d, .d_in_len = (const uint32_t*)(d + 16), .n = 1, .wrap = ZMI_WRAP_RAW,
+                              .d_out = c->st_out.p, .d_out_off = (const uint64_t*)(d + 8), .d_out_cap = (const uint32_t*)(d + 20),
+                              .d_out_hist = (const uint32_t*)(d + 24), .d_out_len = (uint32_t*)(d + 32), .d_status = (int32_t*)(d + 36),
+                              .d_in_used = (uint32_t*)(d + 40), .d_detail = (int32_t*)(d + 44), .d_in_bit = (const uint32_t*)(d + 28),
+                              .d_resume = (uint32_t*)(d + 48), .stream = hs, .out_limit = (uint64_t)out_cap + (1ull << 16), .limit_exact = true,
+                              .scratch = &dec});
     if (rc) { (void)hipStreamSynchronize(hs); return rc; }
     uint32_t r[8], codes = 0;
     ZMI_HIP(hipMemcpyAsync(r, d + 32, sizeof(r), hipMemcpyDeviceToHost, hs));
-    // (zmi_inflate_impl's scratch for one stream: bm_off u64 | used | check -- a resumable decode leaves its tables' size in `check`)
-    ZMI_HIP(hipMemcpyAsync(&codes, (const uint8_t*)c->inf_tmp.p + 12, 4, hipMemcpyDeviceToHost, hs));
+    // (a resumable decode leaves its tables' size in `check`)
+    ZMI_HIP(hipMemcpyAsync(&codes, dec.check, 4, hipMemcpyDeviceToHost, hs));
     ZMI_HIP(hipStreamSynchronize(hs));   // this stream only: other contexts keep running
     if (codes != 0u) c->last_codes_used = codes;   // (a call that met no dynamic block header keeps the earlier figure)
     *out_len = r[0];
@@ -2631,10 +2634,6 @@ static int zmi_inflate_stream_body(zmi_ctx* c, const void* d_in, uint64_t in_len
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
         zmi_launch_si_header((const uint8_t*)d_in, in_len, (uint32_t)wrap, d_hdr, stream);
     }
-    // the decode's bitmap covers one group's regions
-    const uint64_t saved_limit = c->inflate_out_limit;
-    c->inflate_out_limit = group * stride + (1ull << 16);
-    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; } } restore_limit{c, saved_limit};
     const uint32_t kind = wrap == ZMI_WRAP_ZLIB ? 1u : (wrap == ZMI_WRAP_GZIP ? 2u : (wrap == ZMI_WRAP_AUTO ? 3u : 0u));
     for (uint64_t first = 0; first < n; first += group) {
         const uint32_t cnt = (uint32_t)(n - first < group ? n - first : group);
@@ -2648,10 +2647,14 @@ static int zmi_inflate_stream_body(zmi_ctx* c, const void* d_in, uint64_t in_len
                 zmi_launch_si_setup(d_cuts, n_cuts, in_len, f, cnt, stride, piece_out_max, (uint64_t*)(W + w_ioff), (uint32_t*)(W + w_in),
                                     (uint64_t*)(W + w_ooff), (uint32_t*)(W + w_cap), (uint32_t*)(W + w_hist), stream);
         }
-        rc = zmi_inflate_impl(c, d_in, (const uint64_t*)(W + w_ioff), (const uint32_t*)(W + w_in), cnt, ZMI_WRAP_RAW, d_dec, (const uint64_t*)(W + w_ooff),
-                              (const uint32_t*)(W + w_cap), (const uint32_t*)(W + w_hist), (uint32_t*)(W + w_olen), (int32_t*)(W + w_st),
-                              (uint32_t*)(W + w_used), (int32_t*)(W + w_det), bits ? (const uint32_t*)(W + w_bit) : nullptr, (uint32_t*)(W + w_res),
-                              stream_, true);
+        zmi_inf_scratch dec;   // (the decode's bitmap covers one group's regions; the symbolic resolve reads it)
+        rc = zmi_inflate_impl(c, {.d_in = d_in, .d_in_off = (const uint64_t*)(W + w_ioff), .d_in_len = (const uint32_t*)(W + w_in), .n = cnt,
+                                  .wrap = ZMI_WRAP_RAW, .d_out = d_dec, .d_out_off = (const uint64_t*)(W + w_ooff),
+                                  .d_out_cap = (const uint32_t*)(W + w_cap), .d_out_hist = (const uint32_t*)(W + w_hist),
+                                  .d_out_len = (uint32_t*)(W + w_olen), .d_status = (int32_t*)(W + w_st), .d_in_used = (uint32_t*)(W + w_used),
+                                  .d_detail = (int32_t*)(W + w_det), .d_in_bit = bits ? (const uint32_t*)(W + w_bit) : nullptr,
+                                  .d_resume = (uint32_t*)(W + w_res), .stream = stream_, .decode_only = true,
+                                  .out_limit = group * stride + (1ull << 16), .scratch = &dec});
         if (rc) return rc;
         {
             zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
@@ -2665,7 +2668,7 @@ static int zmi_inflate_stream_body(zmi_ctx* c, const void* d_in, uint64_t in_len
         }
         {
             zmi_scope_timer tm(c, ZMI_K_RESOLVE, stream);
-            zmi_launch_si_resolve(d_dec, stride, d_len + f, piece_out_max, cnt, (const uint64_t*)c->inf_bm.p, (const uint64_t*)c->inf_tmp.p, d_sym, stream);
+            zmi_launch_si_resolve(d_dec, stride, d_len + f, piece_out_max, cnt, dec.bitmap, dec.bm_off, d_sym, stream);
         }
         {
             zmi_scope_timer tm(c, ZMI_K_PARSE, stream);   // (the window scan; an inflate call runs no cost parse)
@@ -2765,10 +2768,6 @@ extern "C" int zmi_inflate_ranges_dev(zmi_ctx* c, const void* d_in, uint64_t in_
     if (rc) return rc;
     uint8_t* W = (uint8_t*)c->si_work.p;
     uint32_t* d_u32 = (uint32_t*)(W + w_u32);   // in_n | cap | hist | bit | ... (rg_tab, inflate.hip)
-    // the decode's bitmap covers one group's rooms
-    const uint64_t saved_limit = c->inflate_out_limit;
-    c->inflate_out_limit = group * room + (1ull << 16);
-    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; } } restore_limit{c, saved_limit};
     for (uint64_t first = 0; first < n_ranges; first += group) {
         const uint32_t cnt = (uint32_t)(n_ranges - first < group ? n_ranges - first : group);
         const uint32_t f = (uint32_t)first;
@@ -2778,9 +2777,11 @@ extern "C" int zmi_inflate_ranges_dev(zmi_ctx* c, const void* d_in, uint64_t in_
                                (uint64_t*)(W + w_ioff), (uint64_t*)(W + w_ooff), d_u32, G, stream);
             if (d_ix_win) zmi_launch_rg_hist((const uint8_t*)d_ix_win, d_u32, G, cnt, rstride, W + w_reg, stream);
         }
-        rc = zmi_inflate_impl(c, d_in, (const uint64_t*)(W + w_ioff), d_u32, cnt, ZMI_WRAP_RAW, W + w_reg, (const uint64_t*)(W + w_ooff), d_u32 + g,
-                              d_u32 + 2 * g, (uint32_t*)(W + w_olen), (int32_t*)(W + w_st), (uint32_t*)(W + w_used), (int32_t*)(W + w_det),
-                              d_u32 + 3 * g, (uint32_t*)(W + w_res), stream_);
+        rc = zmi_inflate_impl(c, {.d_in = d_in, .d_in_off = (const uint64_t*)(W + w_ioff), .d_in_len = d_u32, .n = cnt, .wrap = ZMI_WRAP_RAW,
+                                  .d_out = W + w_reg, .d_out_off = (const uint64_t*)(W + w_ooff), .d_out_cap = d_u32 + g, .d_out_hist = d_u32 + 2 * g,
+                                  .d_out_len = (uint32_t*)(W + w_olen), .d_status = (int32_t*)(W + w_st), .d_in_used = (uint32_t*)(W + w_used),
+                                  .d_detail = (int32_t*)(W + w_det), .d_in_bit = d_u32 + 3 * g, .d_resume = (uint32_t*)(W + w_res),
+                                  .stream = stream_, .out_limit = group * room + (1ull << 16)});   // (the decode's bitmap covers one group's rooms)
         if (rc) return rc;
         {
             zmi_scope_timer tm(c, ZMI_K_PACK, stream);
@@ -2899,7 +2900,7 @@ extern "C" int zmi_inflate_members_dev(zmi_ctx* c, const void* d_in, uint64_t in
     // An out_cap above the scratch limit is cut at multiples of half the limit: group g holds the members whose planned offset lies
     // in [g * half, (g + 1) * half) -- the members come from device words, so every group is a launch over all proposals in which
     // the others are empty streams.  Offsets and bytes do not depend on the cut.  The limit is the context's scratch limit alone
-    // (as zmi_inflate_stream_dev): the inflate-out limit is whatever the last batch call was sized for and says nothing here.
+    // (as zmi_inflate_stream_dev): the inflate-out limit is the setting for batch calls that size no scratch of their own and says nothing here.
     uint64_t limit = c->scratch_limit;
     if (const char* lv = zmi_tune("ZMI_MM_LIMIT")) if (atoll(lv) >= (128ll << 10)) limit = (uint64_t)atoll(lv);   // (tests: groups on small files)
     uint64_t half = 0, groups = 1, room_max = ~0ull;
@@ -2933,10 +2934,7 @@ extern "C" int zmi_inflate_members_dev(zmi_ctx* c, const void* d_in, uint64_t in
     uint32_t* g_in = (uint32_t*)(M + m_g);
     uint32_t *g_cap = g_in + n, *g_olen = g_in + 2 * n, *g_used = g_in + 4 * n;
     int32_t *g_st = (int32_t*)(g_in + 3 * n), *g_det = (int32_t*)(g_in + 5 * n);
-    // the decode's bitmap covers one group's regions
-    const uint64_t saved_limit = c->inflate_out_limit;
-    c->inflate_out_limit = (out_cap > limit ? limit : out_cap) + (1ull << 16);
-    struct restore { zmi_ctx* c; uint64_t v; ~restore() { c->inflate_out_limit = v; } } restore_limit{c, saved_limit};
+    const uint64_t bm_limit = (out_cap > limit ? limit : out_cap) + (1ull << 16);   // the decode's bitmap covers one group's regions
     ZMI_HIP(hipMemsetAsync(d_w, 0, 64, stream));
     {
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
@@ -2956,8 +2954,9 @@ extern "C" int zmi_inflate_members_dev(zmi_ctx* c, const void* d_in, uint64_t in
                 zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
                 zmi_launch_mm_setup(d_starts, n_starts, d_tab, d_off, d_w, out_cap, half, (uint32_t)g, g_ioff, g_in, g_ooff, g_cap, stream);
             }
-            rc = zmi_inflate_impl(c, d_in, g_ioff, g_in, n_starts, ZMI_WRAP_GZIP, d_out, g_ooff, g_cap, nullptr, g_olen, g_st, g_used, g_det, nullptr,
-                                  nullptr, stream_);
+            rc = zmi_inflate_impl(c, {.d_in = d_in, .d_in_off = g_ioff, .d_in_len = g_in, .n = n_starts, .wrap = ZMI_WRAP_GZIP, .d_out = d_out,
+                                      .d_out_off = g_ooff, .d_out_cap = g_cap, .d_out_len = g_olen, .d_status = g_st, .d_in_used = g_used,
+                                      .d_detail = g_det, .stream = stream_, .out_limit = bm_limit});
             if (rc) return rc;
             zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
             zmi_launch_mm_collect(d_starts, n_starts, d_tab, d_off, d_w, out_cap, half, (uint32_t)g, g_olen, g_st, g_used, g_det, stream);
@@ -2969,11 +2968,12 @@ extern "C" int zmi_inflate_members_dev(zmi_ctx* c, const void* d_in, uint64_t in
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
         zmi_launch_mm_lr_setup(d_starts, n_starts, d_tab, d_off, d_w, in_len, out_cap, room_max, l_ioff, l_in, l_ooff, l_cap, stream);
     }
-    rc = zmi_inflate_impl(c, d_in, l_ioff, l_in, 1u, ZMI_WRAP_GZIP, d_out, l_ooff, l_cap, nullptr, l_olen, l_st, l_used, l_det, nullptr, nullptr,
-                          stream_, false, nullptr, true);
+    zmi_inf_scratch lr;   // (of the last-resort launch)
+    rc = zmi_inflate_impl(c, {.d_in = d_in, .d_in_off = l_ioff, .d_in_len = l_in, .n = 1u, .wrap = ZMI_WRAP_GZIP, .d_out = d_out, .d_out_off = l_ooff,
+                              .d_out_cap = l_cap, .d_out_len = l_olen, .d_status = l_st, .d_in_used = l_used, .d_detail = l_det, .stream = stream_,
+                              .no_jump = true, .out_limit = bm_limit, .scratch = &lr});
     if (rc) return rc;
     {
-        const zmi_inf_tables lr = zmi_inf_tables_of(c, 1u);   // (of the last-resort launch)
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
         zmi_launch_scan_sizes(d_tab, n_starts, d_rank, stream);   // (the live flags)
         zmi_launch_mm_final(d_starts, n_starts, d_tab, d_off, d_w, (const uint8_t*)d_in, in_len, out_cap, d_rank, l_olen, l_st, l_used, l_det, lr.check,

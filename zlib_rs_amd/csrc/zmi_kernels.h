@@ -137,6 +137,18 @@ int zmi_launch_resolve_jump_segments(uint8_t* d_fin, const uint64_t* d_soff, uin
 int zmi_launch_inflate_resolve(uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_len, uint32_t n_streams,
                                const uint64_t* d_bitmap, const uint64_t* d_bm_off, const uint32_t* d_out_hist,
                                const uint32_t* d_order, hipStream_t stream);
+// the batch with one shared preset dictionary (inflate.hip): every stream's `hist`, the resolve pass that reads the dictionary's image,
+// the DICTID check; and the check of every stream's trailer against the sums of the produced bytes
+int zmi_launch_inflate_shared_hist(uint32_t* d_hist, uint32_t n_streams, uint32_t hist, hipStream_t stream);
+int zmi_launch_inflate_resolve_shared(uint8_t* d_out, const uint64_t* d_out_off, const uint32_t* d_out_len, uint32_t n_streams,
+                                      const uint64_t* d_bitmap, const uint64_t* d_bm_off, const uint32_t* d_order,
+                                      const uint8_t* d_img, uint32_t hist, hipStream_t stream);
+int zmi_launch_inflate_dictid(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_streams,
+                              const uint32_t* d_dictid, int32_t* d_status, int32_t* d_detail, uint32_t* d_out_len,
+                              hipStream_t stream);
+int zmi_launch_inflate_verify(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                              uint32_t n_streams, uint32_t wrap, const uint32_t* d_check, const uint32_t* d_adler,
+                              const uint32_t* d_crc, int32_t* d_status, int32_t* d_detail, hipStream_t stream);
 // single-stream inflate (inflate.hip): header, piece layout from the cuts, cut verification, symbolic resolve, window scan,
 // substitute, trailer; proposals of cuts
 int zmi_launch_si_header(const uint8_t* d_in, uint64_t n, uint32_t wrap, uint32_t* d_hdr, hipStream_t stream);

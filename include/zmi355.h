@@ -760,6 +760,101 @@ int zmi_zip_write_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, 
                       int strategy, uint64_t base, void* d_out, uint64_t out_cap, uint64_t* d_out_len,
                       zmi_zip_entry* d_entries /* NULL or n_entries */, zmi_zip_info* d_info /* NULL */, int32_t* d_status, void* stream);
 
+/* ---- reading PNG images: the chunk chain, a batch inflate of the IDAT streams, the scanline unfilter ------------------------------------
+ * A PNG is a chain of chunks (length u32 BE | type | data | CRC-32 of type + data, W3C PNG third edition section 5.3; RFC 2083
+ * section 3.2) behind an eight-byte signature (5.2); the image is one zlib stream cut into consecutive IDAT chunks (10.1, 11.2.4) that
+ * inflates to `height` scanlines of 1 filter byte + row_bytes bytes (7.2, 9.2).  Two calls, both asynchronous on `stream`, neither
+ * synchronises with the host, every per-image failure is a status word.  Image i is the file d_in[d_in_off[i] .. + d_in_len[i]), at
+ * any alignment.  PNG is not part of the reference project: the contract is the specification.  Not read: Adam7 (8.2), images whose
+ * scanlines reach 4 GiB (the batch decoder's lengths are uint32_t); nothing is written; APNG frames, gamma and ICC are not looked at.
+ *
+ * zmi_png_headers_dev   one zmi_png_image per file.  The first rule that holds, in this order, is the record's status:
+ *   ZMI_PE_SIGNATURE    the eight bytes 89 50 4e 47 0d 0a 1a 0a are wrong (5.2)
+ *   ZMI_PE_IHDR         the first chunk is not a 13-byte IHDR; a dimension of 0 or above 2^31 - 1; a depth / colour type pair outside
+ *                       table 11.1 (11.2.2); compression or filter method not 0; interlace method above 1
+ *   ZMI_PE_INTERLACE    interlace method 1: listed with its dimensions, flagged, not decoded (the chain is then not walked)
+ *   ZMI_PE_TRUNC        a chunk length above 2^31 - 1 (5.3), a chunk that leaves the file, no IEND before the file ends
+ *   ZMI_PE_CRITICAL     an unknown chunk whose first letter is upper case (5.4)
+ *   ZMI_PE_ORDER        no IDAT; IDAT chunks that are not consecutive; PLTE missing for colour type 3, PLTE behind IDAT, a PLTE length
+ *                       not a multiple of 3 or above 768 (5.6, 11.2.3); a second IHDR
+ *   ZMI_PE_BIG          (1 + row_bytes) * height does not fit 32 bits
+ *   Ancillary chunks are skipped unread -- acTL, fcTL and fdAT too, so the default image of an APNG decodes; tRNS (11.3.2.1) is only
+ *   located.  Bytes behind IEND are ignored.
+ *
+ * zmi_png_decode_dev    slot j decodes image d_sel[j] of the table d_images[0 .. n_images) (d_sel NULL: slot j = image j); duplicates
+ *               are allowed; an index >= n_images, and a record no headers call would write for this file (the IDAT run it names --
+ *               idat_pos + 12 * n_idat + idat_bytes -- and the IEND behind it leave the file, a size of 0), get ZMI_E_ARG in the
+ *               slot's status and nothing of them is read.
+ *   Region      height * row_bytes bytes: the unfiltered scanlines, no filter bytes, no row padding.  Depth 8 is an [H, W, C] byte
+ *               tensor as it stands; samples below 8 bits stay packed (7.2); 16-bit samples stay big-endian unless
+ *               flags & ZMI_PNG_NATIVE16, with which the unfilter's own store writes them little-endian.
+ *   Plan        d_out_off, out_align, out_cap as zmi_inflate_batch_packed_dev: d_out_off[j] = the sum of the region sizes of the
+ *               readable slots in front, each rounded up to out_align (a power of two, 1 .. 4096, otherwise ZMI_E_ARG);
+ *               d_out_off[n_sel] = the room the selection needs whether or not it fitted; a slot that ends behind out_cap reports
+ *               Z_BUF_ERROR / ZMI_PE_OUT; nothing at or behind d_out + out_cap and nothing in the gaps is written.  A flagged or failed
+ *               slot takes no room (a failed one: the room the plan gave it), has length 0, and raises nothing.
+ *   Reading     one workgroup walk per slot checks the CRC-32 of IHDR, PLTE, every IDAT and IEND (never an ancillary chunk's;
+ *               flags & ZMI_PNG_NO_CRC skips it) and gathers the payloads of several IDAT chunks into one stream in context scratch
+ *               (a single IDAT is read in place); the batch decoder runs with ZMI_WRAP_ZLIB and capacity (1 + row_bytes) * height
+ *               into scratch, which checks the Adler-32; the unfilter kernel (9.2: None, Sub, Up, Average on a 9-bit sum, Paeth with
+ *               ties in the order a, b, c; every neighbour outside the image is 0) writes the region; one kernel writes the slot's
+ *               words, the first of these that holds:
+ *   d_status / d_detail   Z_DATA_ERROR / the record's ZMI_PE_*     flagged by the headers call (Z_VERSION_ERROR for INTERLACE and BIG)
+ *               Z_BUF_ERROR / ZMI_PE_OUT        the region does not fit out_cap
+ *               Z_MEM_ERROR / ZMI_PE_SCRATCH    the gathered streams of the call exceed its scratch, see below
+ *               Z_DATA_ERROR / ZMI_PE_CRC       a wrong CRC-32 in a critical chunk
+ *               Z_DATA_ERROR / ZMI_PE_DATA      a corrupt zlib stream, a wrong Adler-32, FDICT set
+ *               Z_DATA_ERROR / ZMI_PE_LENGTH    the stream ends before or behind exactly (1 + row_bytes) * height bytes.  libpng only
+ *                                               warns about surplus image data ("Too much image data"); this call refuses it
+ *               Z_DATA_ERROR / ZMI_PE_FILTER    a filter byte above 4 (9.2); the region's bytes are then unspecified
+ *   Bytes behind the end of the zlib stream but inside the IDAT payload are no error (libpng and PIL accept them).
+ *   d_out_len[j] = height * row_bytes with status 0, otherwise 0.  Never status 0 with wrong bytes; one bad image does not touch its
+ *   neighbours.  n_sel 0 writes d_out_off[0] = 0.  Bytes and words do not depend on the alignment of d_in, on n_images, on the slot
+ *   index or on the decode-kernel selection.
+ *   Scratch of the context, sized from out_cap and n_sel because no size of the input is known to the host: 88 bytes per slot; the
+ *   filtered scanlines, 2 * out_cap + 16 bytes per slot (1 + row_bytes <= 2 * row_bytes) -- so out_cap should be the room the batch
+ *   needs, not a large buffer kept for reuse; the gathered streams of the images with more than one IDAT, min(2.125 * out_cap + 1 KiB
+ *   per slot + 64 KiB, the context's scratch limit) -- the streams are planned in slot order, and every slot whose stream does not end
+ *   inside that room (a call whose multi-IDAT payloads EXPAND their scanlines by more than 6 % in total, by junk behind the streams for
+ *   instance) reports ZMI_PE_SCRATCH, keeps its room and has length 0; and the decoder's, sized by this call from out_cap whatever the
+ *   context's limits are.  Scratch that cannot be reserved is ZMI_E_NOMEM.
+ *   Event timing: 5 = slot tables and plans, 0 = the walk (chunk CRC-32 and gather), 7 = unused (the gather is fused into the
+ *   walk), 3 / 6 = decode, resolve (the decoder's own Adler-32 pass adds to 0, its verify to 4), 2 = the unfilter (the encoder's slot is
+ *   idle on every read path), 4 = the slot words. */
+#define ZMI_PE_SIGNATURE 1   /* Z_DATA_ERROR */
+#define ZMI_PE_IHDR 2        /* Z_DATA_ERROR */
+#define ZMI_PE_INTERLACE 3   /* Z_VERSION_ERROR */
+#define ZMI_PE_TRUNC 4       /* Z_DATA_ERROR */
+#define ZMI_PE_CRITICAL 5    /* Z_DATA_ERROR */
+#define ZMI_PE_ORDER 6       /* Z_DATA_ERROR */
+#define ZMI_PE_BIG 7         /* Z_VERSION_ERROR */
+#define ZMI_PE_CRC 8         /* slots only, from here on: Z_DATA_ERROR */
+#define ZMI_PE_DATA 9
+#define ZMI_PE_LENGTH 10
+#define ZMI_PE_FILTER 11
+#define ZMI_PE_OUT 12        /* Z_BUF_ERROR */
+#define ZMI_PE_SCRATCH 13    /* Z_MEM_ERROR */
+#define ZMI_PNG_NATIVE16 1u  /* flags: 16-bit samples leave little-endian */
+#define ZMI_PNG_NO_CRC 2u    /* flags: no chunk CRC-32 is checked */
+typedef struct zmi_png_image {      /* 48 bytes */
+    uint32_t width, height;           /* IHDR (11.2.2); 0 where the record's status is SIGNATURE or IHDR */
+    uint8_t  depth, colour, channels; /* bit depth 1 / 2 / 4 / 8 / 16, colour type 0 / 2 / 3 / 4 / 6, samples per pixel 1 .. 4 */
+    uint8_t  bpp;                     /* the filters' pixel distance: max(1, channels * depth / 8) (9.2) */
+    uint32_t row_bytes;               /* ceil(width * channels * depth / 8); 0xFFFFFFFF together with ZMI_PE_BIG where that is 4 GiB or more */
+    uint32_t idat_pos;                /* position in the file of the first IDAT chunk (of its length field) */
+    uint32_t n_idat, idat_bytes;      /* the consecutive IDAT chunks from there, and the sum of their payload lengths */
+    uint32_t plte_pos, plte_len;      /* position of the PLTE chunk's DATA in the file and its length; 0, 0 if absent */
+    uint32_t trns_pos, trns_len;      /* the same for tRNS */
+    int32_t  status;                  /* 0: readable by zmi_png_decode_dev; otherwise the ZMI_PE_* reason */
+} zmi_png_image;
+uint32_t zmi_png_strip(void);       /* bytes of a scanline one LDS strip of the unfilter kernel holds (for tests that place row_bytes around it) */
+int zmi_png_headers_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_images,
+                        zmi_png_image* d_images, void* stream);
+int zmi_png_decode_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                       const zmi_png_image* d_images, uint32_t n_images, const uint32_t* d_sel, uint32_t n_sel, uint32_t flags,
+                       uint32_t out_align, void* d_out, uint64_t out_cap, uint64_t* d_out_off /* n_sel + 1 */, uint32_t* d_out_len,
+                       int32_t* d_status, int32_t* d_detail, void* stream);
+
 /* ---- host-buffer convenience wrappers: copy in, run the batch on the GPU, copy back ---- */
 int zmi_deflate_batch(zmi_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_shards,
                       int level, int strategy, int wrap, uint8_t* out, uint64_t out_stride, uint32_t* out_len,

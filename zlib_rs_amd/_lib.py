@@ -76,6 +76,11 @@ def lib():
     L.zmi_zip_walk_tile.argtypes = []
     L.zmi_zip_directory_dev.argtypes = [vp, vp, u64, vp, u32, vp, vp]
     L.zmi_zip_inflate_dev.argtypes = [vp, vp, u64, vp, u32, vp, u32, u32, vp, u64, vp, vp, vp, vp, vp]
+    # reading PNG images: the chunk chain, a batch inflate of the IDAT streams, the scanline unfilter (csrc/png_kernels.h, zmi_api.hip)
+    L.zmi_png_strip.restype = u32
+    L.zmi_png_strip.argtypes = []
+    L.zmi_png_headers_dev.argtypes = [vp, vp, vp, vp, u32, vp, vp]
+    L.zmi_png_decode_dev.argtypes = [vp, vp, vp, vp, vp, u32, vp, u32, u32, u32, vp, u64, vp, vp, vp, vp, vp]
     # writing ZIP archives: entries, directory, ZIP64 (csrc/pack.hip, checksum.hip, zmi_api.hip)
     L.zmi_zip_bound.restype = u64
     L.zmi_zip_bound.argtypes = [u32, u64, u64, u32, i32]

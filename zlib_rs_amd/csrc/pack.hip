@@ -1188,3 +1188,6 @@ extern "C" int zmi_launch_zip_close(uint8_t* d_out, uint64_t out_cap, const uint
     ZMI_LAUNCH(zmi_zip_close_kernel, dim3(1), dim3(1), 0, stream, d_out, out_cap, d_pay_end, d_cd_end, d_n_eff, base, d_out_len, d_info, d_status);
     return 0;
 }
+
+// ---- reading PNG images (zmi_png_headers_dev / zmi_png_decode_dev) ------------------------------------------------------------------------
+#include "png_kernels.h"

@@ -105,6 +105,7 @@ struct zmi_ctx {
     zmi_buf mm_scan, mm_meta;           // zmi_gzip_find_members_dev: segment counts and offsets; zmi_inflate_members_dev: its tables
     zmi_buf pk;                         // zmi_inflate_batch_packed_dev: size[n] cap[n] (the size pass's result, the planned capacity table)
     zmi_buf zip_dir, zip_sel;           // zmi_zip_directory_dev: four words, the chain positions, four words per segment; zmi_zip_inflate_dev: the slots' tables
+    zmi_buf png;                        // zmi_png_decode_dev: the slots' tables | the gathered IDAT streams | the filtered scanlines
     zmi_buf dict;                       // the shared-dictionary batch calls: layout words and DICTID | deflate image | inflate image (zmi_sd_*)
 };
 
@@ -165,6 +166,7 @@ extern "C" int zmi_ctx_destroy(zmi_ctx* c) {
     if (c->pk.p) (void)hipFree(c->pk.p);
     if (c->zip_dir.p) (void)hipFree(c->zip_dir.p);
     if (c->zip_sel.p) (void)hipFree(c->zip_sel.p);
+    if (c->png.p) (void)hipFree(c->png.p);
     if (c->mm_scan.p) (void)hipFree(c->mm_scan.p);
     if (c->mm_meta.p) (void)hipFree(c->mm_meta.p);
     for (int k = 0; k < 2; ++k) if (c->st_pin[k].p) (void)hipHostFree(c->st_pin[k].p);
@@ -1488,6 +1490,102 @@ extern "C" int zmi_zip_inflate_dev(zmi_ctx* c, const void* d_in, uint64_t in_len
     {
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
         zmi_launch_zip_verify(d_entries, n_entries, d_sel, n_sel, in_len, d_out_off, out_cap, d_used, d_crc, d_out_len, d_status, d_detail, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+// ---- PNG images (include/zmi355.h; kernels in png_kernels.h) ----
+extern "C" int zmi_png_headers_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_images,
+                                   zmi_png_image* d_images, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (n_images == 0) return ZMI_E_OK;
+    if (!d_in || !d_in_off || !d_in_len || !d_images) return zmi_fail(ZMI_E_ARG, "null argument");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    {
+        zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
+        zmi_launch_png_headers((const uint8_t*)d_in, d_in_off, d_in_len, n_images, d_images, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+extern "C" int zmi_png_decode_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, const zmi_png_image* d_images,
+                                  uint32_t n_images, const uint32_t* d_sel, uint32_t n_sel, uint32_t flags, uint32_t out_align, void* d_out,
+                                  uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (out_align == 0u || out_align > 4096u || (out_align & (out_align - 1u)) != 0u)
+        return zmi_fail(ZMI_E_ARG, "out_align must be a power of two, 1 .. 4096");
+    if (flags & ~(ZMI_PNG_NATIVE16 | ZMI_PNG_NO_CRC)) return zmi_fail(ZMI_E_ARG, "unknown flag");
+    if (!d_out_off) return zmi_fail(ZMI_E_ARG, "d_out_off is required");
+    if (n_sel > 0x7FFFFFFFu) return zmi_fail(ZMI_E_ARG, "n_sel must be below 2^31");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    if (n_sel == 0) {
+        ZMI_HIP(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), stream));
+        return ZMI_E_OK;
+    }
+    if (!d_out_len || !d_status || !d_detail) return zmi_fail(ZMI_E_ARG, "d_out_len, d_status and d_detail are required");
+    if ((n_images && (!d_images || !d_in || !d_in_off || !d_in_len)) || (out_cap && !d_out)) return zmi_fail(ZMI_E_ARG, "null argument");
+    if (out_cap > (1ull << 44)) return zmi_fail(ZMI_E_NOMEM, "out_cap sizes the scratch: give the room there is");
+    // Everything is sized from out_cap and n_sel: no size of the input is known here.  Scanlines: 1 + row_bytes <= 2 * row_bytes, and
+    // every region starts at a multiple of 16.  Gathered streams: see the header.
+    const size_t n = n_sel;
+    const uint64_t scan_cap = 2ull * out_cap + 16ull * n + 64ull;
+    // (the gather buffer is this call's own addition to what the decoder needs: it stays under the context's scratch limit)
+    uint64_t gather_cap = 2ull * out_cap + (out_cap >> 3) + 1024ull * n + (64ull << 10);
+    if (gather_cap > c->scratch_limit) gather_cap = c->scratch_limit;
+    const size_t tab_bytes = ((4u * n + 3u) * 8u + 13u * n * 4u + 255u) & ~(size_t)255u;
+    const size_t gather_at = tab_bytes, scan_at = (gather_at + gather_cap + 16u + 255u) & ~(size_t)255u;
+    int rc = zmi_reserve(c->png, scan_at + 16u + scan_cap + 16u);
+    if (rc) return rc;
+    uint64_t* d_goff = (uint64_t*)c->png.p;                      // where the gathered stream of a slot stands (the plan over d_gsz)
+    uint64_t* d_soff = d_goff + n + 1;                           // ... its filtered scanlines (the decoder's own plan over d_ssz)
+    uint64_t* d_item_off = d_soff + n + 1;                       // the scan of d_items
+    uint64_t* d_zin_off = d_item_off + n + 1;                    // where the decoder reads the slot's zlib stream
+    uint32_t* d_pix = (uint32_t*)(d_zin_off + n);                // height * row_bytes of a readable slot, else 0
+    uint32_t* d_pcap = d_pix + n;                                // ... where the region fits out_cap, else 0
+    uint32_t* d_ssz = d_pcap + n;                                // (1 + row_bytes) * height of a slot that is decoded, else 0
+    uint32_t* d_scap = d_ssz + n;
+    uint32_t* d_gsz = d_scap + n;                                // idat_bytes of a decoded slot with several IDAT chunks, else 0
+    uint32_t* d_gcap = d_gsz + n;
+    uint32_t* d_items = d_gcap + n;                              // bands of 64 rows
+    uint32_t* d_fl = d_items + n;                                // PNG_FL_*: set by the walk and the unfilter
+    uint32_t* d_zin_len = d_fl + n;
+    uint32_t* d_slen = d_zin_len + n;                            // the decoder's words
+    uint32_t* d_sused = d_slen + n;
+    int32_t* d_sst = (int32_t*)(d_sused + n);
+    int32_t* d_sdet = d_sst + n;
+    uint8_t* d_gbuf = (uint8_t*)c->png.p + gather_at;
+    uint8_t* d_sbuf = (uint8_t*)c->png.p + scan_at + 16u;        // (the unfilter reads whole dwords around a row: 16 bytes of margin)
+    uint32_t split = 1u;
+    if (const char* sv = zmi_tune("ZMI_PNG_SPLIT")) split = (uint32_t)atoi(sv);   // (the probe: a chain per image instead of per None / Sub row)
+    {
+        zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
+        zmi_launch_png_prep(d_images, n_images, d_sel, n_sel, d_in_len, 0u, d_pix, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+        zmi_launch_inflate_pack_plan(d_pix, n_sel, out_align, out_cap, d_out_off, d_pcap, stream);
+        zmi_launch_png_prep(d_images, n_images, d_sel, n_sel, d_in_len, 1u, d_pix, d_pcap, d_ssz, d_gsz, d_items, d_fl, stream);
+        zmi_launch_inflate_pack_plan(d_gsz, n_sel, 16u, gather_cap, d_goff, d_gcap, stream);
+        zmi_launch_scan_sizes(d_items, n_sel, d_item_off, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_CHECKSUM, stream);
+        zmi_launch_png_walk((const uint8_t*)d_in, d_in_off, d_in_len, d_images, d_sel, n_sel, d_ssz, d_gsz, d_goff, d_gcap, d_gbuf,
+                            (flags & ZMI_PNG_NO_CRC) ? 0u : 1u, d_zin_off, d_zin_len, d_fl, stream);
+    }
+    rc = zmi_inflate_packed_body(c, d_in, d_zin_off, d_zin_len, n_sel, ZMI_WRAP_ZLIB, nullptr, 0u, d_ssz, d_scap, 16u, d_sbuf, scan_cap, d_soff,
+                                 d_slen, d_sst, d_sused, d_sdet, ZMI_K_PARSE, stream_);
+    if (rc) return rc;
+    {
+        zmi_scope_timer tm(c, ZMI_K_ENCODE, stream);
+        zmi_launch_png_unfilter(d_images, d_sel, n_sel, d_item_off, out_cap / 64u + n, d_sbuf, d_soff, d_ssz, d_slen, d_sst, (uint8_t*)d_out,
+                                d_out_off, (flags & ZMI_PNG_NATIVE16) ? 1u : 0u, split, d_fl, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_png_finish(d_images, n_images, d_sel, n_sel, d_in_len, d_out_off, out_cap, d_ssz, d_slen, d_sst, d_fl, d_out_len, d_status,
+                              d_detail, stream);
     }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;

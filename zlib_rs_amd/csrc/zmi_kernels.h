@@ -64,6 +64,7 @@ struct zmi_enc_params {
 
 struct zmi_zip_entry;   // include/zmi355.h
 struct zmi_zip_info;
+struct zmi_png_image;
 
 extern "C" {
 int zmi_launch_gen(uint8_t* d_out, uint64_t seed, uint32_t first_shard, uint32_t n_shards, uint32_t shard_bytes,
@@ -276,4 +277,24 @@ int zmi_launch_zip_prep(const zmi_zip_entry* d_entries, uint32_t n_entries, cons
 int zmi_launch_zip_verify(const zmi_zip_entry* d_entries, uint32_t n_entries, const uint32_t* d_sel, uint32_t n_sel, uint64_t in_len,
                           const uint64_t* d_out_off, uint64_t out_cap, const uint32_t* d_used, const uint32_t* d_crc, uint32_t* d_out_len,
                           int32_t* d_status, int32_t* d_detail, hipStream_t stream);
+// PNG images (png_kernels.h, compiled into pack.hip): the records; the slots' sizes (pass 0: d_pix, for the plan of the regions; pass 1,
+// behind it: scanline sizes, gather sizes, bands of 64 rows, cleared flag words); the walk (chunk CRC-32, the gather of several IDAT
+// chunks, where the decoder reads each slot's stream); the unfilter over the items -- d_item_off the scan of the bands, bound what it
+// can sum to; the slots' final words
+uint32_t zmi_png_strip(void);
+int zmi_launch_png_headers(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n, zmi_png_image* d_images,
+                           hipStream_t stream);
+int zmi_launch_png_prep(const zmi_png_image* d_images, uint32_t n_images, const uint32_t* d_sel, uint32_t n_sel, const uint32_t* d_in_len,
+                        uint32_t pass, uint32_t* d_pix, const uint32_t* d_pcap, uint32_t* d_ssz, uint32_t* d_gsz, uint32_t* d_items, uint32_t* d_fl,
+                        hipStream_t stream);
+int zmi_launch_png_walk(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, const zmi_png_image* d_images,
+                        const uint32_t* d_sel, uint32_t n_sel, const uint32_t* d_ssz, const uint32_t* d_gsz, const uint64_t* d_goff,
+                        const uint32_t* d_gcap, uint8_t* d_gbuf, uint32_t check_crc, uint64_t* d_zin_off, uint32_t* d_zin_len, uint32_t* d_fl,
+                        hipStream_t stream);
+int zmi_launch_png_unfilter(const zmi_png_image* d_images, const uint32_t* d_sel, uint32_t n_sel, const uint64_t* d_item_off, uint64_t bound,
+                            const uint8_t* d_sbuf, const uint64_t* d_soff, const uint32_t* d_ssz, const uint32_t* d_slen, const int32_t* d_sst,
+                            uint8_t* d_out, const uint64_t* d_out_off, uint32_t native16, uint32_t split, uint32_t* d_fl, hipStream_t stream);
+int zmi_launch_png_finish(const zmi_png_image* d_images, uint32_t n_images, const uint32_t* d_sel, uint32_t n_sel, const uint32_t* d_in_len,
+                          const uint64_t* d_out_off, uint64_t out_cap, const uint32_t* d_ssz, const uint32_t* d_slen, const int32_t* d_sst,
+                          const uint32_t* d_fl, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, hipStream_t stream);
 }

@@ -22,6 +22,11 @@ MM_HEADER, MM_TRUNC, MM_DATA, MM_CHECK, MM_LENGTH, MM_OUT, MM_BIG, MM_AGAIN = 1,
 ZA_NOEOCD, ZA_BOUNDS, ZA_CHAIN, ZA_COUNT, ZA_ZIP64, ZA_MULTIDISK = 1, 2, 3, 4, 5, 6
 ZE_LOCAL, ZE_METHOD, ZE_CRYPT, ZE_BIG, ZE_EXTRA, ZE_STORED, ZE_DATA, ZE_LENGTH, ZE_CHECK, ZE_OUT = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 ZIP_ENTRY_BYTES = 48
+# zmi_png_headers_dev / zmi_png_decode_dev (include/zmi355.h ZMI_PE_* / ZMI_PNG_*)
+(PE_SIGNATURE, PE_IHDR, PE_INTERLACE, PE_TRUNC, PE_CRITICAL, PE_ORDER, PE_BIG, PE_CRC, PE_DATA, PE_LENGTH, PE_FILTER, PE_OUT,
+ PE_SCRATCH) = range(1, 14)
+PNG_NATIVE16, PNG_NO_CRC = 1, 2
+PNG_IMAGE_BYTES = 48
 
 
 def _stream_ptr():
@@ -138,6 +143,116 @@ class BgzfIndex:
         else:
             off = [0]
         return cls(torch.tensor(off, dtype=torch.int64, device=torch.device(device)), block_bytes, n)
+
+
+class PngBatch:
+    """A batch of PNG files as zmi_png_headers_dev lists them (include/zmi355.h).  data: the files on the device; offsets int64 [n] /
+    lengths int32 [n]: file i is data[offsets[i] : + lengths[i]]; images: uint8 [n, 48], the device table of zmi_png_image records.
+    width / height / status are int32 views of the table, depth / colour / channels int32 copies of its byte fields."""
+
+    def __init__(self, data, offsets, lengths, images):
+        self.data, self.offsets, self.lengths, self.images = data, offsets, lengths, images
+        self._host = None
+
+    @property
+    def n_images(self):
+        return int(self.images.shape[0])
+
+    def _word(self, k):
+        return self.images.view(torch.int32)[:, k]
+
+    @property
+    def width(self):
+        return self._word(0)
+
+    @property
+    def height(self):
+        return self._word(1)
+
+    @property
+    def depth(self):
+        return self.images[:, 8].to(torch.int32)
+
+    @property
+    def colour(self):
+        return self.images[:, 9].to(torch.int32)
+
+    @property
+    def channels(self):
+        return self.images[:, 10].to(torch.int32)
+
+    @property
+    def row_bytes(self):
+        return self._word(3)
+
+    @property
+    def status(self):
+        """int32 [n]: 0 = readable, else the PE_* reason the headers call gives"""
+        return self._word(11)
+
+    @property
+    def readable(self):
+        return self.status == 0
+
+    def record(self, j):
+        """the host copy of record j as a dict (the table is copied to the host once)"""
+        if self._host is None:
+            self._host = self.images.cpu().numpy()
+        r = self._host[j]
+        w = r.view("<u4")
+        return {"width": int(w[0]), "height": int(w[1]), "depth": int(r[8]), "colour": int(r[9]), "channels": int(r[10]), "bpp": int(r[11]),
+                "row_bytes": int(w[3]), "idat_pos": int(w[4]), "n_idat": int(w[5]), "idat_bytes": int(w[6]), "plte_pos": int(w[7]),
+                "plte_len": int(w[8]), "trns_pos": int(w[9]), "trns_len": int(w[10]), "status": int(r.view("<i4")[11])}
+
+    def image(self, out, out_off, j, image=None, native16=True):
+        """Slot j of a png_decode result as a zero-copy view of `out`: [H, W, C] uint8 for depth 8, [H, W, C] uint16 for depth 16 decoded
+        with native16, [H, row_bytes] uint8 for packed depths and for big-endian 16-bit samples.  A uint16 view needs the slot at an
+        even address: decoded with align=1 it may stand at an odd one, which raises ValueError (decode with align >= 2, the default
+        is 16).  image: the index of the image the slot decoded (default: j, the whole batch in order)."""
+        r = self.record(j if image is None else image)
+        at = int(out_off[j])
+        flat = out[at:at + r["height"] * r["row_bytes"]]
+        if r["depth"] == 8:
+            return flat.view(r["height"], r["width"], r["channels"])
+        if r["depth"] == 16 and native16:
+            if (out.data_ptr() + at) % 2:
+                raise ValueError("image: slot %d stands at an odd address, a uint16 view needs align >= 2" % j)
+            return flat.view(torch.uint16).view(r["height"], r["width"], r["channels"])
+        return flat.view(r["height"], r["row_bytes"])
+
+    def palette(self, j):
+        """(PLTE as uint8 [n, 3], tRNS as uint8 [m] or None) of image j: views of the file on the device; (None, None) without PLTE"""
+        r = self.record(j)
+        base = int(self.offsets[j])
+        if r["plte_pos"] == 0:
+            return None, None
+        plte = self.data[base + r["plte_pos"]:base + r["plte_pos"] + r["plte_len"]].view(-1, 3)
+        trns = self.data[base + r["trns_pos"]:base + r["trns_pos"] + r["trns_len"]] if r["trns_pos"] else None
+        return plte, trns
+
+    def expand(self, img, j):
+        """Plain torch indexing, no kernel: the view image() gave for image j -> [H, W, C] uint8.  Packed gray samples are unpacked and
+        scaled by 255 // (2^depth - 1), as PIL scales them; palette indices of any depth become RGB, or RGBA where the file has a tRNS
+        (entries beyond it are opaque); depth-8 images come back as they are; 16-bit images are not touched."""
+        r = self.record(j)
+        depth, colour, W = r["depth"], r["colour"], r["width"]
+        if depth < 8:
+            per = 8 // depth
+            shifts = torch.arange(per - 1, -1, -1, device=img.device, dtype=torch.int32) * depth
+            idx = ((img.to(torch.int32).unsqueeze(-1) >> shifts) & ((1 << depth) - 1)).reshape(r["height"], -1)[:, :W]
+        elif depth == 8 and colour == 3:
+            idx = img.reshape(r["height"], W).to(torch.int32)
+        else:
+            return img
+        if colour == 0:
+            return (idx * (255 // ((1 << depth) - 1))).to(torch.uint8).unsqueeze(-1)
+        plte, trns = self.palette(j)
+        table = plte
+        if trns is not None:
+            alpha = torch.full((plte.shape[0], 1), 255, dtype=torch.uint8, device=plte.device)
+            alpha[:trns.numel(), 0] = trns[:plte.shape[0]]
+            table = torch.cat([plte, alpha], dim=1)
+        return table[idx.to(torch.int64).clamp(0, table.shape[0] - 1)]
 
 
 class ZipDirectory:
@@ -903,6 +1018,82 @@ class Engine:
             out = torch.empty(need, dtype=torch.uint8, device=self.device)
             call(out)
         return out[:need], out_off, out_len, status
+
+    # ---- PNG images (include/zmi355.h) ----
+    def png_headers(self, data, offsets=None, lengths=None):
+        """The chunk chains of a batch of PNG files -> PngBatch.  data: a uint8 device tensor with offsets / lengths (int64 / int32
+        tables, file i = data[offsets[i] : + lengths[i]]; neither: the tensor is ONE file), one bytes object, or a list of bytes, which
+        is concatenated and uploaded.  No synchronisation; a file the call flags (PE_*) is listed and raises nothing."""
+        if isinstance(data, (list, tuple)):
+            import numpy as np
+            offs = np.zeros(len(data), dtype=np.int64)
+            if len(data) > 1:
+                np.cumsum([len(b) for b in data[:-1]], out=offs[1:])
+            offsets = torch.from_numpy(offs)
+            lengths = torch.tensor([len(b) for b in data], dtype=torch.int32)
+            data = b"".join(bytes(b) for b in data)
+        data = self._zip_data(data)
+        if offsets is None:
+            offsets = torch.zeros(1, dtype=torch.int64)
+            lengths = torch.tensor([int(data.numel())], dtype=torch.int32)
+        offsets = offsets.to(device=self.device, dtype=torch.int64).contiguous()
+        lengths = lengths.to(device=self.device, dtype=torch.int32).contiguous()
+        n = int(lengths.numel())
+        if int(offsets.numel()) < n:
+            raise ValueError("png_headers: %d lengths need %d offsets" % (n, n))
+        images = torch.zeros((n, PNG_IMAGE_BYTES), dtype=torch.uint8, device=self.device)
+        _lib.check(self.L.zmi_png_headers_dev(self._ctx, data.data_ptr() if data.numel() else None, offsets.data_ptr() if n else None,
+                                              lengths.data_ptr() if n else None, n, images.data_ptr() if n else None, _stream_ptr()),
+                   "zmi_png_headers_dev")
+        return PngBatch(data, offsets, lengths, images)
+
+    def png_decode(self, data, batch=None, indices=None, align=16, native16=True, check_crc=True, out=None):
+        """Images of a batch of PNG files, inflated and unfiltered densely into one buffer -> (out, out_off int64 [n_sel + 1], out_len
+        int32 [n_sel], status int32 [n_sel]).  Slot j stands at out[out_off[j] : out_off[j] + out_len[j]] as height * row_bytes bytes
+        (PngBatch.image gives the view); out_off[-1] is the room the selection needs.  batch: the PngBatch of png_headers (None: made
+        here from data; with a batch, data may be None); indices (a list or an int32 device tensor) select, None: every image.  status
+        0: every check passed; every other status has length 0 and nothing is raised for an image.  last_png_detail keeps the PE_*
+        tensor.  native16: 16-bit samples leave little-endian; check_crc=False skips the chunk CRC-32s.  out=None allocates the sum of
+        the selected regions, which is ONE word read by the host."""
+        b = batch if batch is not None else self.png_headers(data)
+        if align < 1 or align > 4096 or align & (align - 1):
+            raise ValueError("align must be a power of two, 1 .. 4096")
+        sel = None
+        if indices is not None:
+            sel = indices if isinstance(indices, torch.Tensor) else torch.tensor(list(indices), dtype=torch.int32, device=self.device)
+            sel = sel.to(device=self.device, dtype=torch.int32).contiguous()
+        n = b.n_images
+        n_sel = int(sel.numel()) if sel is not None else n
+        out_off = torch.zeros(n_sel + 1, dtype=torch.int64, device=self.device)
+        out_len = torch.zeros(n_sel, dtype=torch.int32, device=self.device)
+        status = torch.zeros(n_sel, dtype=torch.int32, device=self.device)
+        detail = torch.zeros(n_sel, dtype=torch.int32, device=self.device)
+        self.last_png_detail = detail
+        flags = (PNG_NATIVE16 if native16 else 0) | (0 if check_crc else PNG_NO_CRC)
+
+        def call(buf):
+            _lib.check(self.L.zmi_png_decode_dev(self._ctx, b.data.data_ptr() if n else None, b.offsets.data_ptr() if n else None,
+                                                 b.lengths.data_ptr() if n else None, b.images.data_ptr() if n else None, n,
+                                                 sel.data_ptr() if sel is not None and n_sel else None, n_sel, flags, int(align),
+                                                 buf.data_ptr() if buf.numel() else None, int(buf.numel()), out_off.data_ptr(),
+                                                 out_len.data_ptr(), status.data_ptr(), detail.data_ptr(), _stream_ptr()),
+                       "zmi_png_decode_dev")
+
+        if out is not None:
+            call(out)
+            return out, out_off, out_len, status
+        if n_sel == 0 or n == 0:
+            if n_sel:
+                call(torch.empty(0, dtype=torch.uint8, device=self.device))
+            return torch.empty(0, dtype=torch.uint8, device=self.device), out_off, out_len, status
+        size = (b.height.to(torch.int64) & 0xFFFFFFFF) * (b.row_bytes.to(torch.int64) & 0xFFFFFFFF) * b.readable.to(torch.int64)
+        if sel is not None:
+            inside = (sel >= 0) & (sel < n)
+            size = size[sel.to(torch.int64).clamp(0, n - 1)] * inside.to(torch.int64)
+        guess = int((((size + (align - 1)) // align) * align).sum().item())
+        out = torch.empty(guess, dtype=torch.uint8, device=self.device)
+        call(out)
+        return out, out_off, out_len, status
 
     # ---- writing ZIP archives (include/zmi355.h, DESIGN.md section 21) ----
     def zip_bound(self, n_entries, names_bytes, in_bytes, piece_bytes=1 << 20, level=6):

@@ -766,7 +766,7 @@ int zmi_zip_write_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, 
  * inflates to `height` scanlines of 1 filter byte + row_bytes bytes (7.2, 9.2).  Two calls, both asynchronous on `stream`, neither
  * synchronises with the host, every per-image failure is a status word.  Image i is the file d_in[d_in_off[i] .. + d_in_len[i]), at
  * any alignment.  PNG is not part of the reference project: the contract is the specification.  Not read: Adam7 (8.2), images whose
- * scanlines reach 4 GiB (the batch decoder's lengths are uint32_t); nothing is written; APNG frames, gamma and ICC are not looked at.
+ * scanlines reach 4 GiB (the batch decoder's lengths are uint32_t); APNG frames, gamma and ICC are not looked at.  Writing: further down.
  *
  * zmi_png_headers_dev   one zmi_png_image per file.  The first rule that holds, in this order, is the record's status:
  *   ZMI_PE_SIGNATURE    the eight bytes 89 50 4e 47 0d 0a 1a 0a are wrong (5.2)
@@ -854,6 +854,69 @@ int zmi_png_decode_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off,
                        const zmi_png_image* d_images, uint32_t n_images, const uint32_t* d_sel, uint32_t n_sel, uint32_t flags,
                        uint32_t out_align, void* d_out, uint64_t out_cap, uint64_t* d_out_off /* n_sel + 1 */, uint32_t* d_out_len,
                        int32_t* d_status, int32_t* d_detail, void* stream);
+
+/* ---- writing PNG images: the scanline filter with a choice per row, deflate in pieces, the chunks ------------------------------------------
+ * The inverse of the two calls above: a batch of images in device memory becomes a batch of complete PNG files in device memory, one
+ * asynchronous call on `stream` that never synchronises with the host; every per-image failure is a status word.  Not written: colour
+ * type 3 (PLTE / tRNS), Adam7, ancillary chunks, APNG, several IDAT chunks per image; one level, strategy and filter mode per call.
+ *
+ *   Input       image i is the pixels d_in[d_in_off[i] .. + d_in_len[i]) at any alignment -- exactly the region zmi_png_decode_dev writes:
+ *               height * row_bytes bytes, no filter bytes, no row padding.  Samples below 8 bits are packed, padding bits are taken as
+ *               they stand.  16-bit samples are big-endian, or little-endian under flags & ZMI_PNG_NATIVE16 (the filter kernel's own
+ *               load swaps them; there is no extra pass).  Any other flag: ZMI_E_ARG.
+ *   d_images    of d_images[i] only width, height, depth and colour are read; channels, bpp and row_bytes are recomputed, so a table
+ *               from zmi_png_headers_dev can be encoded again as it stands and a caller may fill just four fields.  The table is device
+ *               data: every violation is ZMI_E_ARG in d_status[i] -- length 0, no room taken, neighbours untouched, nothing of the image
+ *               read --, the first of these that holds: a dimension of 0 or above 2^31 - 1; a depth / colour pair outside table 11.1;
+ *               colour type 3; (1 + row_bytes) * height above ZMI_PNG_SCAN_MAX; d_in_len[i] != height * row_bytes.
+ *   scan_bytes  the caller's bound on the sum of (1 + row_bytes) * height over the valid images (the lengths live on the device: what
+ *               in_bytes is to zmi_zip_write_dev).  It sizes the piece table, n_images + scan_bytes / piece_bytes places (more than
+ *               2^31 - 1: ZMI_E_ARG as the return value), and the scanline scratch.  A larger true sum is ZMI_E_ARG in every slot:
+ *               nothing is written, every d_out_off word is 0.
+ *   File        every byte is fixed, one IDAT per image:
+ *                 89 50 4e 47 0d 0a 1a 0a | 00 00 00 0d "IHDR" width height depth colour 00 00 00 crc |
+ *                 len "IDAT" zlib-stream crc | 00 00 00 00 "IEND" ae 42 60 82
+ *               The zlib stream: the two header bytes zmi_deflate_stream_dev writes for ZMI_WRAP_ZLIB at that level and strategy; the
+ *               filtered scanlines cut into pieces of piece_bytes, each compressed as an independent piece of ONE raw stream exactly
+ *               as zmi_deflate_pieces_dev(ZMI_STREAM_INDEPENDENT) does with max_len = piece_bytes -- every piece but the last ends with
+ *               the flush marker, the last ends the stream --; the big-endian Adler-32 of the filtered scanlines.  Level 0 is deflate
+ *               stored blocks through the same path (PNG has no "stored" method).  A file's bytes are a function of (its pixels and
+ *               four fields, flags, filter, piece_bytes, level, strategy) alone -- not of n_images, its index, the alignment of d_in,
+ *               out_align, the scratch limit or the launch grouping.  An image whose IDAT data (the stream with its 6 bytes of frame)
+ *               passes 2^31 - 1 bytes is ZMI_E_ARG too (its length is computed in 64 bits; the room the plan gave it stays taken).
+ *               Otherwise d_status[i] is 0, Z_BUF_ERROR, or the first encoder status of its pieces.
+ *   Filter      filter 0 .. 4: that type (9.2: None, Sub, Up, Average on a 9-bit sum, Paeth with ties in the order a, b, c) on every
+ *               row.  ZMI_PNG_FILTER_ADAPTIVE: per row the type whose filtered bytes v have the least sum of (v < 128 ? v : 256 - v)
+ *               over the row's row_bytes bytes (the minimum sum of absolute differences of 12.7, exact, 64-bit), the SMALLEST type
+ *               among those of least cost -- on row 0 None therefore beats Up and Sub beats Paeth, which always tie there.  The
+ *               neighbours are raw bytes, every one outside the image is 0.  filter above 5: ZMI_E_ARG as the return value.
+ *   Plan        d_out_off[i] = the sum of the file lengths of the valid images in front, each rounded up to out_align (a power of two,
+ *               1 .. 4096, otherwise ZMI_E_ARG); d_out_off[n_images] = the room the batch needs whether or not it fitted.  A file that
+ *               ends at or before out_cap is complete with status 0; one that crosses it has Z_BUF_ERROR and length 0 (pieces of it
+ *               that end in front of out_cap may have been written).  Nothing at or behind d_out + out_cap and nothing in the alignment
+ *               gaps is written.  d_out_len[i] = the file's length with status 0, otherwise 0.  n_images 0 writes d_out_off[0] = 0.
+ *   d_written   NULL, or n_images rows: the table zmi_png_headers_dev would list for the written files -- every field, status 0 --;
+ *               the row of an image whose status is not 0 is all zeros with that status.
+ *   zmi_png_bound   room that always suffices (not tight); piece_bytes 0: 0.
+ *   Arguments   piece_bytes 1 .. 2^30, level -1 .. 9, strategy 0 .. 4, n_images <= 2^31 - 1, otherwise ZMI_E_ARG as the return value.
+ *   Launch groups as in zmi_zip_write_dev: a group's slots and match scratch stay within the scratch limit, the running offset stays in
+ *   a device word, an image may lie across groups; the bytes do not depend on the grouping.
+ *   Scratch of the context: the filtered scanlines, scan_bytes + 128 bytes, NOT capped by the scratch limit (all images are filtered
+ *   before the first group is encoded); 48 bytes per image, 40 bytes and 1 bit per place of the piece table, 12 bytes per slot of a
+ *   group; one group's slots as in zmi_zip_write_dev.  Scratch that cannot be reserved is ZMI_E_NOMEM.
+ *   Event timing: 3 = the filter kernel (the decoder's slot is idle on every write path, as the encoder's is where the reader put its
+ *   unfilter), 0 = Adler-32 of the scanline pieces, CRC-32 of the compressed pieces, the folds per image, 1 / 5 / 2 = match search, parse,
+ *   encode, 7 = layout, scans, the piece table, places and pack, 4 = the files' fixed bytes and the images' words. */
+#define ZMI_PNG_FILTER_ADAPTIVE 5u      /* filter: 0 .. 4 = that type on every row (9.2), 5 = per row, see above */
+#define ZMI_PNG_SCAN_MAX 0x7F000000u    /* most filtered bytes per image: 16 MiB below 2^31, which holds the encoder's worst case (stored
+                                           blocks, a marker per piece) for pieces of 64 KiB and more; smaller pieces: see File */
+uint32_t zmi_png_filter_tile(void);     /* bytes of a scanline one trip of the filter kernel covers per wave (for tests that place row_bytes around it) */
+uint64_t zmi_png_bound(uint32_t n_images, uint64_t scan_bytes, uint32_t piece_bytes, uint32_t out_align, int level);
+int zmi_png_encode_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len,
+                       const zmi_png_image* d_images, uint32_t n_images, uint64_t scan_bytes, uint32_t flags, uint32_t filter,
+                       uint32_t piece_bytes, int level, int strategy, uint32_t out_align, void* d_out, uint64_t out_cap,
+                       uint64_t* d_out_off /* n_images + 1 */, uint32_t* d_out_len, zmi_png_image* d_written /* NULL or n_images */,
+                       int32_t* d_status, void* stream);
 
 /* ---- host-buffer convenience wrappers: copy in, run the batch on the GPU, copy back ---- */
 int zmi_deflate_batch(zmi_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_shards,

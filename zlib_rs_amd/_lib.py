@@ -85,6 +85,12 @@ def lib():
     L.zmi_zip_bound.restype = u64
     L.zmi_zip_bound.argtypes = [u32, u64, u64, u32, i32]
     L.zmi_zip_write_dev.argtypes = [vp, vp, vp, vp, u32, u64, vp, vp, vp, vp, u32, i32, i32, u64, vp, u64, vp, vp, vp, vp, vp]
+    # writing PNG images: the forward filter, deflate in pieces, the chunks (csrc/png_kernels.h, checksum.hip, zmi_api.hip)
+    L.zmi_png_filter_tile.restype = u32
+    L.zmi_png_filter_tile.argtypes = []
+    L.zmi_png_bound.restype = u64
+    L.zmi_png_bound.argtypes = [u32, u64, u32, u32, i32]
+    L.zmi_png_encode_dev.argtypes = [vp, vp, vp, vp, vp, u32, u64, u32, u32, u32, i32, i32, u32, vp, u64, vp, vp, vp, vp, vp]
     # the multi-GPU stitch (csrc/exchange.hip); RCCL itself is loaded by the library on first use
     L.zmi_comm_unique_id.argtypes = [vp]
     L.zmi_comm_create.argtypes = [C.POINTER(vp), vp, i32, i32, vp]

@@ -364,7 +364,7 @@ extern "C" int zmi_launch_checksum_combine(const uint32_t* d_check, const uint32
     return 0;
 }
 
-// ---- the CRC-32 of every entry of a piece table (zmi_zip_write_dev) ----------------------------------------------------------------------
+// ---- the CRC-32 of every entry of a piece table (zmi_zip_write_dev; adler != 0: the Adler-32, zmi_png_encode_dev) -------------------------
 // Segment e < *n_live (a device word, at most the n the launch covers) is the pieces [first[e], first[e + 1]) of the (check, len)
 // tables; out[e] = their fold, a copy of the word where the segment
 // is one piece.  One thread per segment folds up to ZMI_SEG_SERIAL pieces in order -- an archive of small files is all such segments,
@@ -374,18 +374,19 @@ extern "C" int zmi_launch_checksum_combine(const uint32_t* d_check, const uint32
 #define ZMI_SEG_SERIAL 64u
 __global__ void __launch_bounds__(256) zmi_combine_segments_kernel(const uint32_t* __restrict__ check, const uint32_t* __restrict__ len,
                                                                   const uint64_t* __restrict__ first, const uint32_t* __restrict__ n_live,
-                                                                  uint32_t* __restrict__ out) {
+                                                                  uint32_t adler, uint32_t* __restrict__ out) {
     __shared__ uint32_t pw[64];
     const uint32_t t = threadIdx.x;
     if (t < 64u) pw[t] = kXpowTab.v[t];
     __syncthreads();
+    const bool ad = adler != 0u;
     const uint64_t gi = (uint64_t)blockIdx.x * 256u + t;
     const bool live = gi < *n_live;
     const uint64_t p0 = live ? first[gi] : 0ull, cnt = live ? first[gi + 1u] - p0 : 0ull;
     if (live && cnt <= ZMI_SEG_SERIAL) {
-        uint32_t c = 0;
+        uint32_t c = ad ? 1u : 0u;
         uint64_t l = 0;
-        for (uint64_t p = p0; p < p0 + cnt; ++p) zmi_combine_pair(false, pw, c, l, check[p], (uint64_t)len[p]);
+        for (uint64_t p = p0; p < p0 + cnt; ++p) zmi_combine_pair(ad, pw, c, l, check[p], (uint64_t)len[p]);
         out[gi] = c;
     }
     const uint32_t lane = zmi_lane();
@@ -394,9 +395,9 @@ __global__ void __launch_bounds__(256) zmi_combine_segments_kernel(const uint32_
         const uint64_t q0 = ((uint64_t)__shfl((uint32_t)(p0 >> 32), src) << 32) | __shfl((uint32_t)p0, src);
         const uint64_t qn = ((uint64_t)__shfl((uint32_t)(cnt >> 32), src) << 32) | __shfl((uint32_t)cnt, src);
         const uint64_t per = (qn + 63u) / 64u;
-        uint32_t c = 0;
+        uint32_t c = ad ? 1u : 0u;
         uint64_t l = 0;
-        for (uint64_t p = lane * per; p < (lane + 1u) * per && p < qn; ++p) zmi_combine_pair(false, pw, c, l, check[q0 + p], (uint64_t)len[q0 + p]);
+        for (uint64_t p = lane * per; p < (lane + 1u) * per && p < qn; ++p) zmi_combine_pair(ad, pw, c, l, check[q0 + p], (uint64_t)len[q0 + p]);
         for (uint32_t d = 1; d < 64u; d <<= 1) {
             const uint32_t oc = __shfl_xor(c, (int)d);
             const uint32_t olo = __shfl_xor((uint32_t)l, (int)d), ohi = __shfl_xor((uint32_t)(l >> 32), (int)d);
@@ -404,11 +405,11 @@ __global__ void __launch_bounds__(256) zmi_combine_segments_kernel(const uint32_
             if (lane & d) {
                 uint32_t c2 = oc;
                 uint64_t l2 = ol;
-                zmi_combine_pair(false, pw, c2, l2, c, l);
+                zmi_combine_pair(ad, pw, c2, l2, c, l);
                 c = c2;
                 l = l2;
             } else {
-                zmi_combine_pair(false, pw, c, l, oc, ol);
+                zmi_combine_pair(ad, pw, c, l, oc, ol);
             }
         }
         if (lane == 0u) out[gi - lane + (uint32_t)src] = c;   // (lane 0's gi is the wave's first segment)
@@ -417,6 +418,13 @@ __global__ void __launch_bounds__(256) zmi_combine_segments_kernel(const uint32_
 extern "C" int zmi_launch_combine_segments(const uint32_t* d_check, const uint32_t* d_len, const uint64_t* d_first, uint32_t n,
                                            const uint32_t* d_n_live, uint32_t* d_out, hipStream_t stream) {
     if (n == 0) return 0;
-    ZMI_LAUNCH(zmi_combine_segments_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_check, d_len, d_first, d_n_live, d_out);
+    ZMI_LAUNCH(zmi_combine_segments_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_check, d_len, d_first, d_n_live, 0u, d_out);
+    return 0;
+}
+// the same fold of Adler-32 values (zmi_png_encode_dev: the scanlines of an image from its pieces'); a segment without pieces gives 1
+extern "C" int zmi_launch_combine_segments_adler(const uint32_t* d_check, const uint32_t* d_len, const uint64_t* d_first, uint32_t n,
+                                                 const uint32_t* d_n_live, uint32_t* d_out, hipStream_t stream) {
+    if (n == 0) return 0;
+    ZMI_LAUNCH(zmi_combine_segments_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_check, d_len, d_first, d_n_live, 1u, d_out);
     return 0;
 }

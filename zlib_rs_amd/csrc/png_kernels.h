@@ -1,4 +1,5 @@
-// png_kernels.h -- reading PNG images (zmi_png_headers_dev / zmi_png_decode_dev, include/zmi355.h); included by pack.hip.
+// png_kernels.h -- reading PNG images (zmi_png_headers_dev / zmi_png_decode_dev, include/zmi355.h) and, in the second half of the
+// file, writing them (zmi_png_encode_dev); included by pack.hip.
 //
 // The format is the W3C PNG specification, third edition (RFC 2083): a chain of chunks -- length u32 big-endian | type | data | CRC-32
 // of type + data (section 5.3) -- behind an eight-byte signature (5.2); the image is ONE zlib stream cut into consecutive IDAT chunks
@@ -588,5 +589,435 @@ extern "C" int zmi_launch_png_finish(const zmi_png_image* d_images, uint32_t n_i
     if (n_sel == 0) return 0;
     ZMI_LAUNCH(zmi_png_finish_kernel, dim3((n_sel + 255u) / 256u), dim3(256), 0, stream, d_images, n_images, d_sel, n_sel, d_in_len, d_out_off, out_cap,
                d_ssz, d_slen, d_sst, d_fl, d_out_len, d_status, d_detail);
+    return 0;
+}
+
+// ---- writing PNG images (zmi_png_encode_dev; every byte of the file: include/zmi355.h) -------------------------------
+// An image's filtered scanlines go into context scratch, are cut into pieces of piece_bytes and join ONE piece table that the
+// independent-piece encoder works through in launch groups, exactly as the entries of zmi_zip_write_dev do -- the piece table, the bitmap
+// of chain mode 2 and the payload copies ARE that call's kernels (zmi_zip_pieces_kernel with a "name" of 13 bytes: the hole of 43 bytes
+// in front of an image's first piece; zmi_zip_pack_kernel).  What is new:
+//   zmi_png_wlayout_kernel   one thread per image: the checks, the scanline size, the piece count, the bands of rows
+//   zmi_png_filter_kernel    the hot path, below
+//   zmi_png_place_kernel     one group's places: a piece takes its hole, its payload and, where it ends an image, the tail of 20 bytes;
+//                            the place behind an image's last piece is rounded up to out_align -- a scan over (size, ends) pairs
+//   zmi_png_wfinish_kernel   one wave per image: signature, IHDR, IDAT length and type, zlib header in the hole; Adler-32, the IDAT
+//                            CRC-32 and IEND in the tail; the image's words and its zmi_png_image
+#define PW_HEAD 43u              // 8 signature + 25 IHDR chunk + 8 IDAT length and type + 2 zlib header
+#define PW_TAIL 20u              // 4 Adler-32 + 4 IDAT CRC-32 + 12 IEND chunk
+#define PW_ROWS 8u               // most rows of a band, the filter kernel's work item
+#define PW_TILE 256u             // bytes of a scanline one trip of a wave covers: an aligned dword of the output per lane
+#define PW_ADAPTIVE 5u
+
+// rows of a band: about 8 KiB of scanlines, one row at least, PW_ROWS at most (a single 8192 x 8192 image is 8192 items, not 1024;
+// a full band is never less than 16 bytes of scanlines, which bounds the items by the caller's scan_bytes)
+static __device__ __forceinline__ uint32_t pw_band_rows(uint32_t rb) {
+    const uint32_t r = 8192u / (rb + 1u);
+    return r < 1u ? 1u : (r > PW_ROWS ? PW_ROWS : r);
+}
+struct pw_geom { uint32_t w, h, depth, colour, ch, bpp, rb, scan; };
+// the four fields of record i that are read, checked (include/zmi355.h lists the rules); false: the image is ZMI_E_ARG
+static __device__ __forceinline__ bool pw_geom_of(const zmi_png_image* __restrict__ img, const uint32_t* __restrict__ in_len, uint32_t i, pw_geom* g) {
+    const uint32_t w = img[i].width, h = img[i].height, depth = img[i].depth, colour = img[i].colour;
+    uint32_t ch = 0u;
+    if (colour == 0u) ch = (depth == 1u || depth == 2u || depth == 4u || depth == 8u || depth == 16u) ? 1u : 0u;
+    else if (colour == 2u || colour == 4u || colour == 6u) ch = (depth == 8u || depth == 16u) ? (colour == 2u ? 3u : (colour == 4u ? 2u : 4u)) : 0u;
+    if (w == 0u || h == 0u || w > 0x7FFFFFFFu || h > 0x7FFFFFFFu || ch == 0u) return false;
+    const uint64_t rb = ((uint64_t)w * ch * depth + 7ull) >> 3;
+    if (rb >= ZMI_PNG_SCAN_MAX) return false;
+    const uint64_t scan = (1ull + rb) * h;
+    if (scan > ZMI_PNG_SCAN_MAX || (uint64_t)in_len[i] != rb * h) return false;
+    g->w = w; g->h = h; g->depth = depth; g->colour = colour; g->ch = ch;
+    g->bpp = ch * depth >= 8u ? ch * depth / 8u : 1u;
+    g->rb = (uint32_t)rb; g->scan = (uint32_t)scan;
+    return true;
+}
+
+// per image: ssz = (1 + row_bytes) * height, npc = its pieces, bands = its items of the filter kernel -- all 0 for an image that fails
+// the checks --, nlen = 13 (what zmi_zip_pieces_kernel adds to 30 for the hole).  *sum (zeroed by the caller) receives the sum of ssz, one
+// atomic per wave, for the scan_bytes check.
+__global__ void __launch_bounds__(256) zmi_png_wlayout_kernel(const zmi_png_image* __restrict__ img, const uint32_t* __restrict__ in_len, uint32_t n,
+                                                              uint32_t piece_bytes, uint32_t* __restrict__ ssz, uint32_t* __restrict__ nlen,
+                                                              uint32_t* __restrict__ npc, uint32_t* __restrict__ bands, unsigned long long* sum) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    uint32_t s = 0u;                                     // (no early return: the wave's lanes meet in the shuffles below)
+    if (i < n) {
+        pw_geom g;
+        const bool ok = pw_geom_of(img, in_len, i, &g);
+        s = ok ? g.scan : 0u;
+        ssz[i] = s;
+        nlen[i] = PW_HEAD - 30u;
+        npc[i] = ok ? (uint32_t)(((uint64_t)s + piece_bytes - 1u) / piece_bytes) : 0u;
+        bands[i] = ok ? (g.h + pw_band_rows(g.rb) - 1u) / pw_band_rows(g.rb) : 0u;
+    }
+    unsigned long long w = s;
+    for (uint32_t d = 1u; d < 64u; d <<= 1) w += __shfl_xor(w, (int)d);
+    if ((threadIdx.x & 63u) == 0u && w) atomicAdd(sum, w);
+}
+
+// ---- the forward filter (section 9.2, the choice of 12.7) -------------------------------------------------------------------------------
+// f[r][i] = x[r][i] - pred_t(a, b, c) mod 256 with a = x[r][i - bpp], b = x[r - 1][i], c = x[r - 1][i - bpp], 0 outside the image: every
+// neighbour is a RAW byte, so nothing here is serial and the work is one read of the pixels and one write of 1 + row_bytes per row.
+// The work item is (image, band of pw_band_rows rows), one wave each; the wave walks a row in trips of PW_TILE bytes.  A lane owns the four
+// row bytes that make up ONE ALIGNED DWORD OF THE OUTPUT (1 + row_bytes shifts every row by one more, so the row offset x of a lane's
+// bytes is 4 * k - (the row's misalignment in the scratch)): the store is one dword per lane whatever the alignments are, and only the
+// first and last dword of a row are written byte-wise.  The four operands -- the row and the row above at x and at x - bpp -- are each
+// two aligned dword loads joined by v_alignbyte (pw_ld4: the input stands at any alignment); neighbouring lanes and the a / c loads hit
+// the lines the x / b loads brought in, the row above comes from L2 (the same wave read it one row earlier, a band's first row from the
+// band in front).  bpp is therefore only a distance between two loads, not a shift inside registers, and the kernel needs no variant
+// per bpp.  Bytes outside [0, row_bytes) read as 0 by a mask, which also gives a and c of the first pixel and row 0's b and c.
+// NATIVE16 swaps the two bytes of every sample as they are loaded (where x is odd the sample pairs lie across a lane's four bytes: the
+// load then takes the eight bytes around them).
+// Adaptive choice: pass 1 computes all five filtered dwords of a trip with packed byte arithmetic (Paeth byte by byte, branch-free) and
+// adds sum(min(v, 256 - v)) -- v_sad_u8 of v ^ 0x80 against 0x80 -- into five 64-bit counters per lane; a wave reduction gives the exact
+// costs, the smallest type of least cost wins, and pass 2 recomputes that type alone and stores it (the row comes from L1 / L2 again: a
+// row of 24 KiB is what one wave just read).  A fixed type runs pass 2 only.
+// Bounds: loads are aligned dwords that hold at least one byte of the row itself; stores write the row's own 1 + row_bytes bytes.
+#ifdef ZMI_EMU
+static inline uint32_t pw_sad4(uint32_t a, uint32_t b) {
+    uint32_t s = 0u;
+    for (int i = 0; i < 4; ++i) { const int d = (int)((a >> (8 * i)) & 0xFFu) - (int)((b >> (8 * i)) & 0xFFu); s += (uint32_t)(d < 0 ? -d : d); }
+    return s;
+}
+#else
+static __device__ __forceinline__ uint32_t pw_sad4(uint32_t a, uint32_t b) { return __builtin_amdgcn_sad_u8(a, b, 0u); }
+#endif
+// the bytes q of a dword at row offset y with 0 <= y + q < rb, as a mask
+static __device__ __forceinline__ uint32_t pw_mask(int32_t y, int32_t rb) {
+    const int32_t lo = y < 0 ? -y : 0;
+    int32_t hi = rb - y;
+    if (hi > 4) hi = 4;
+    if (lo >= 4 || hi <= lo) return 0u;
+    return (0xFFFFFFFFu << (8 * lo)) & (0xFFFFFFFFu >> (8 * (4 - hi)));
+}
+static __device__ __forceinline__ uint32_t pw_swap16(uint32_t v) { return ((v & 0x00FF00FFu) << 8) | ((v >> 8) & 0x00FF00FFu); }
+// row[y .. y + 4) as a little-endian dword, bytes outside [0, rb) as 0
+// (IN: the caller knows [y - 8, y + 12) to lie inside the row -- no test, no mask)
+template <bool IN>
+static __device__ __forceinline__ uint32_t pw_ld4_raw(const uint8_t* row, int32_t y, int32_t rb) {
+    const uint8_t* p = row + y;
+    const uint32_t m = (uint32_t)((uintptr_t)p & 3u);
+    const uint32_t* q = (const uint32_t*)(p - m);
+    if (IN) return __builtin_amdgcn_alignbyte(q[1], q[0], m);
+    const int32_t q0 = y - (int32_t)m;                   // the row offset of q's first byte
+    uint32_t w0 = 0u, w1 = 0u;
+    if (q0 + 3 >= 0 && q0 < rb) w0 = q[0];
+    if (m != 0u && q0 + 7 >= 0 && q0 + 4 < rb) w1 = q[1];
+    return __builtin_amdgcn_alignbyte(w1, w0, m) & pw_mask(y, rb);
+}
+template <bool IN>
+static __device__ __forceinline__ uint32_t pw_ld4(const uint8_t* row, int32_t y, int32_t rb, bool sw) {
+    if (!sw) return pw_ld4_raw<IN>(row, y, rb);
+    if ((y & 1) == 0) return pw_swap16(pw_ld4_raw<IN>(row, y, rb));
+    const int32_t y0 = y - 1;                            // (rb is even: a sample is inside the row or outside it as a whole)
+    return __builtin_amdgcn_alignbyte(pw_swap16(pw_ld4_raw<IN>(row, y0 + 4, rb)), pw_swap16(pw_ld4_raw<IN>(row, y0, rb)), 1u);
+}
+// packed bytes: x - p mod 256, and the Average predictor floor((a + b) / 2) on the 9-bit sum
+static __device__ __forceinline__ uint32_t pw_sub4(uint32_t x, uint32_t p) {
+    return ((x | 0x80808080u) - (p & 0x7F7F7F7Fu)) ^ ((x ^ ~p) & 0x80808080u);
+}
+static __device__ __forceinline__ uint32_t pw_avg4(uint32_t a, uint32_t b) { return (a & b) + (((a ^ b) & 0xFEFEFEFEu) >> 1); }
+static __device__ __forceinline__ uint32_t pw_paeth4(uint32_t a4, uint32_t b4, uint32_t c4) {
+    uint32_t r = 0u;
+#pragma unroll
+    for (uint32_t q = 0u; q < 4u; ++q) {
+        const int a = (int)((a4 >> (8u * q)) & 0xFFu), b = (int)((b4 >> (8u * q)) & 0xFFu), c = (int)((c4 >> (8u * q)) & 0xFFu);
+        const int pa0 = b - c, pb0 = a - c, pc0 = pa0 + pb0;
+        const int pa = pa0 < 0 ? -pa0 : pa0, pb = pb0 < 0 ? -pb0 : pb0, pc = pc0 < 0 ? -pc0 : pc0;
+        const int p = (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+        r |= (uint32_t)p << (8u * q);
+    }
+    return r;
+}
+// sum over the wave of a 64-bit value below 2^56, the same in every lane
+static __device__ __forceinline__ uint64_t pw_wave_sum64(uint64_t v) {
+    const uint64_t lo = zmi_wave_sum((uint32_t)(v & 0xFFFFFFull)), mid = zmi_wave_sum((uint32_t)((v >> 24) & 0xFFFFFFull));
+    const uint64_t hi = zmi_wave_sum((uint32_t)(v >> 48));
+    return lo + (mid << 24) + (hi << 48);
+}
+
+// one trip of pass 1: the five filtered dwords of this lane's bytes, their costs added to cost[]
+template <bool IN>
+static __device__ __forceinline__ void pw_trip_cost(const uint8_t* cur, const uint8_t* up, int32_t rb, int32_t bpp, int32_t x, bool sw, uint64_t* cost) {
+    const uint32_t vm = IN ? 0xFFFFFFFFu : pw_mask(x, rb);
+    const uint32_t x4 = pw_ld4<IN>(cur, x, rb, sw), a4 = pw_ld4<IN>(cur, x - bpp, rb, sw);
+    const uint32_t b4 = up ? pw_ld4<IN>(up, x, rb, sw) : 0u, c4 = up ? pw_ld4<IN>(up, x - bpp, rb, sw) : 0u;
+    const uint32_t f[5] = {x4, pw_sub4(x4, a4) & vm, pw_sub4(x4, b4) & vm, pw_sub4(x4, pw_avg4(a4, b4)) & vm, pw_sub4(x4, pw_paeth4(a4, b4, c4)) & vm};
+#pragma unroll
+    for (uint32_t k = 0u; k < 5u; ++k) cost[k] += pw_sad4(f[k] ^ 0x80808080u, 0x80808080u);
+}
+// one trip of pass 2: type t (the same in every lane) alone, stored
+template <bool IN>
+static __device__ __forceinline__ void pw_trip_store(const uint8_t* cur, const uint8_t* up, int32_t rb, int32_t bpp, int32_t x, bool sw, uint32_t t,
+                                                     uint8_t* dst) {
+    const uint32_t vm = IN ? 0xFFFFFFFFu : pw_mask(x, rb);
+    if (vm == 0u) return;
+    const uint32_t x4 = pw_ld4<IN>(cur, x, rb, sw);
+    uint32_t p4 = 0u;
+    if (t == 1u) p4 = pw_ld4<IN>(cur, x - bpp, rb, sw);
+    else if (t == 2u) p4 = up ? pw_ld4<IN>(up, x, rb, sw) : 0u;
+    else if (t >= 3u) {
+        const uint32_t a4 = pw_ld4<IN>(cur, x - bpp, rb, sw);
+        const uint32_t b4 = up ? pw_ld4<IN>(up, x, rb, sw) : 0u, c4 = up ? pw_ld4<IN>(up, x - bpp, rb, sw) : 0u;
+        p4 = t == 3u ? pw_avg4(a4, b4) : pw_paeth4(a4, b4, c4);
+    }
+    const uint32_t f4 = pw_sub4(x4, p4);
+    uint8_t* o = dst + 1 + x;
+    if (vm == 0xFFFFFFFFu) *(uint32_t*)o = f4;
+    else {
+#pragma unroll
+        for (uint32_t q = 0u; q < 4u; ++q)
+            if ((vm >> (8u * q)) & 0xFFu) o[q] = (uint8_t)(f4 >> (8u * q));
+    }
+}
+
+// one row: cur its rb bytes, up the row above (NULL: row 0), dst its 1 + rb bytes in the scratch.  A trip whose 256 bytes lie eight
+// bytes and a pixel clear of both ends of the row (wave-uniform) needs no bounds test and no mask: all but the first and last of a row
+static __device__ __forceinline__ void pw_filter_row(const uint8_t* cur, const uint8_t* up, int32_t rb, int32_t bpp, uint8_t* dst, uint32_t filter,
+                                                     bool sw, uint32_t lane) {
+    const int32_t md = (int32_t)((uintptr_t)(dst + 1) & 3u);
+    uint32_t t = filter;
+    if (filter == PW_ADAPTIVE) {
+        uint64_t cost[5] = {0ull, 0ull, 0ull, 0ull, 0ull};
+        for (int32_t x0 = -md; x0 < rb; x0 += (int32_t)PW_TILE) {
+            const int32_t x = x0 + 4 * (int32_t)lane;
+            if (x0 - bpp >= 8 && x0 + (int32_t)PW_TILE + 8 <= rb) pw_trip_cost<true>(cur, up, rb, bpp, x, sw, cost);
+            else pw_trip_cost<false>(cur, up, rb, bpp, x, sw, cost);
+        }
+        uint64_t best = 0ull;
+        t = 0u;
+#pragma unroll
+        for (uint32_t k = 0u; k < 5u; ++k) {
+            const uint64_t ck = pw_wave_sum64(cost[k]);
+            if (k == 0u || ck < best) { best = ck; t = k; }
+        }
+    }
+    for (int32_t x0 = -md; x0 < rb; x0 += (int32_t)PW_TILE) {
+        const int32_t x = x0 + 4 * (int32_t)lane;
+        if (x0 - bpp >= 8 && x0 + (int32_t)PW_TILE + 8 <= rb) pw_trip_store<true>(cur, up, rb, bpp, x, sw, t, dst);
+        else pw_trip_store<false>(cur, up, rb, bpp, x, sw, t, dst);
+    }
+    if (lane == 0u) dst[0] = (uint8_t)t;
+}
+
+// *sum > scan_bytes: the scratch may not hold the scanlines, nothing is filtered (the pieces kernel voids the table for the same reason)
+__global__ void __launch_bounds__(64) zmi_png_filter_kernel(const zmi_png_image* __restrict__ img, const uint8_t* __restrict__ in,
+                                                            const uint64_t* __restrict__ in_off, const uint32_t* __restrict__ in_len, uint32_t n,
+                                                            const uint64_t* __restrict__ item_off, const unsigned long long* __restrict__ sum,
+                                                            uint64_t scan_bytes, uint8_t* __restrict__ scan, const uint64_t* __restrict__ soff,
+                                                            uint32_t filter, uint32_t native16) {
+    if (*sum > scan_bytes) return;
+    const uint32_t lane = threadIdx.x;
+    const uint64_t total = item_off[n];
+    for (uint64_t it = blockIdx.x; it < total; it += gridDim.x) {
+        uint32_t lo = 0u, hi = n;                       // the image whose items hold `it`
+        while (hi - lo > 1u) {
+            const uint32_t mid = lo + (hi - lo) / 2u;
+            if (item_off[mid] <= it) lo = mid; else hi = mid;
+        }
+        pw_geom g;
+        if (!pw_geom_of(img, in_len, lo, &g)) continue;  // (an image without items is never found: this cannot happen)
+        const uint32_t band = (uint32_t)(it - item_off[lo]);
+        const uint32_t rows = pw_band_rows(g.rb), r0 = band * rows, r1 = g.h - r0 < rows ? g.h : r0 + rows;
+        const uint8_t* src = in + in_off[lo];
+        uint8_t* dst = scan + soff[lo];
+        const bool sw = native16 != 0u && g.depth == 16u;
+        for (uint32_t r = r0; r < r1; ++r) {
+            const uint8_t* cur = src + (uint64_t)r * g.rb;
+            pw_filter_row(cur, r ? cur - g.rb : nullptr, (int32_t)g.rb, (int32_t)g.bpp, dst + (uint64_t)r * (1ull + g.rb), filter, sw, lane);
+        }
+    }
+}
+
+// One launch group's places, one workgroup.  Piece i of the group takes size_i = its hole + its payload (+ PW_TAIL where its bit in
+// `ends` says that it ends an image), nothing for a void place; behind a piece that ends an image the running place is rounded up to
+// align.  pos[0] holds where the group starts (the word the group before left, read before anything is written), pos[i] receives
+// piece i's place and pos[n] where the group ends.  "p -> p + s, then round" composes: a run of pieces with at least one end is
+// p -> roundup(p + a) + b, one without is p -> p + a, so the run of every thread is folded first and the 1024 folds are scanned.
+struct pw_run { uint64_t a, b; uint32_t r; };
+static __device__ __forceinline__ pw_run pw_then(pw_run f, pw_run g, uint64_t am) {   // f first, then g; am = align - 1
+    pw_run o;
+    if (!f.r) { o.a = f.a + g.a; o.r = g.r; o.b = g.r ? g.b : 0ull; return o; }
+    o.a = f.a; o.r = 1u;
+    o.b = g.r ? ((f.b + g.a + am) & ~am) + g.b : f.b + g.a;
+    return o;
+}
+__global__ void __launch_bounds__(1024) zmi_png_place_kernel(const uint32_t* __restrict__ head, const uint32_t* __restrict__ olen,
+                                                             const uint32_t* __restrict__ ends, uint32_t n, uint32_t align, uint64_t* pos) {
+    __shared__ uint64_t sa[1024], sb[1024];
+    __shared__ uint32_t sr[1024];
+    const uint32_t t = threadIdx.x;
+    const uint64_t am = (uint64_t)align - 1u;
+    const uint64_t base = pos[0];
+    const uint32_t per = (n + 1023u) / 1024u;
+    const uint32_t lo = t * per < n ? t * per : n, hi = lo + per < n ? lo + per : n;
+    pw_run mine = {0ull, 0ull, 0u};
+    for (uint32_t i = lo; i < hi; ++i) {
+        const bool e = (ends[i >> 5] >> (i & 31u)) & 1u;
+        const uint32_t h = head[i];
+        const pw_run one = {h == 0xFFFFFFFFu ? 0ull : (uint64_t)h + olen[i] + (e ? PW_TAIL : 0u), 0ull, e ? 1u : 0u};
+        mine = pw_then(mine, one, am);
+    }
+    sa[t] = mine.a; sb[t] = mine.b; sr[t] = mine.r;
+    __syncthreads();
+    for (uint32_t d = 1u; d < 1024u; d <<= 1) {
+        pw_run f = {0ull, 0ull, 0u};
+        if (t >= d) { f.a = sa[t - d]; f.b = sb[t - d]; f.r = sr[t - d]; }
+        __syncthreads();
+        if (t >= d) {
+            pw_run g = {sa[t], sb[t], sr[t]};
+            g = pw_then(f, g, am);
+            sa[t] = g.a; sb[t] = g.b; sr[t] = g.r;
+        }
+        __syncthreads();
+    }
+    uint64_t p = base;
+    if (t > 0u) p = sr[t - 1u] ? ((base + sa[t - 1u] + am) & ~am) + sb[t - 1u] : base + sa[t - 1u];
+    for (uint32_t i = lo; i < hi; ++i) {
+        const bool e = (ends[i >> 5] >> (i & 31u)) & 1u;
+        const uint32_t h = head[i];
+        pos[i] = p;
+        p += h == 0xFFFFFFFFu ? 0ull : (uint64_t)h + olen[i] + (e ? PW_TAIL : 0u);
+        if (e) p = (p + am) & ~am;
+    }
+    if (t == 1023u) pos[n] = p;
+}
+
+static __device__ __forceinline__ uint32_t pw_crc_byte(uint32_t c, uint32_t b) {
+    c ^= b;
+    for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? PNG_CRC_POLY : 0u);
+    return c;
+}
+// the CRC-32 of A | B from those of A and B (B of l2 bytes)
+static __device__ __forceinline__ uint32_t pw_crc_join(uint32_t c1, uint32_t c2, uint64_t l2) { return png_gf2_mulmod(c1, png_gf2_xpow8(l2)) ^ c2; }
+static __device__ __forceinline__ uint8_t pw_byte(const uint64_t* w, uint32_t k) { return (uint8_t)(w[k >> 3] >> (8u * (k & 7u))); }
+static __device__ __forceinline__ void pw_put(uint64_t* w, uint32_t k, uint32_t b) { w[k >> 3] |= (uint64_t)(b & 0xFFu) << (8u * (k & 7u)); }
+static __device__ __forceinline__ void pw_put_be32(uint64_t* w, uint32_t k, uint32_t v) {
+    pw_put(w, k, v >> 24); pw_put(w, k + 1u, v >> 16); pw_put(w, k + 2u, v >> 8); pw_put(w, k + 3u, v);
+}
+
+// One wave per image, behind the last group.  *n_eff = 0: the scan_bytes check failed, every image is ZMI_E_ARG at offset 0.  Otherwise
+// an image that failed the checks is ZMI_E_ARG where the images in front end; a good one sums its pieces' payloads (64 bits) and takes
+// their first encoder status, and is written where it ends at or before out_cap: the lanes share the 43 + 20 bytes, every lane having
+// computed the same words.  crc / adler: the folds per image of the pieces' CRC-32 (of the payload) and Adler-32 (of the scanlines).
+__global__ void __launch_bounds__(256) zmi_png_wfinish_kernel(const zmi_png_image* __restrict__ img, const uint32_t* __restrict__ in_len, uint32_t n,
+                                                              const uint32_t* __restrict__ n_eff, const uint64_t* __restrict__ first,
+                                                              const uint64_t* __restrict__ pos, const uint32_t* __restrict__ olen,
+                                                              const int32_t* __restrict__ st, const uint32_t* __restrict__ adler,
+                                                              const uint32_t* __restrict__ crc, uint32_t level, uint32_t strategy,
+                                                              uint8_t* __restrict__ out, uint64_t out_cap, uint64_t* __restrict__ out_off,
+                                                              uint32_t* __restrict__ out_len, int32_t* __restrict__ status,
+                                                              zmi_png_image* __restrict__ written) {
+    const uint32_t lane = zmi_lane();
+    const uint32_t i = blockIdx.x * 4u + zmi_wave();
+    if (i >= n) return;                                  // (the whole wave)
+    const bool bad = *n_eff == 0u;
+    if (i == 0u && lane == 0u) out_off[n] = bad ? 0ull : pos[first[n]];
+    pw_geom g = {};
+    const bool ok = !bad && pw_geom_of(img, in_len, i, &g);
+    zmi_png_image rec;
+    rec.width = rec.height = 0u; rec.depth = rec.colour = rec.channels = rec.bpp = 0; rec.row_bytes = 0u; rec.idat_pos = rec.n_idat = rec.idat_bytes = 0u;
+    rec.plte_pos = rec.plte_len = rec.trns_pos = rec.trns_len = 0u; rec.status = PNG_E_ARG;
+    if (!ok) {
+        if (lane == 0u) {
+            out_off[i] = bad ? 0ull : pos[first[i]];
+            out_len[i] = 0u;
+            status[i] = PNG_E_ARG;
+            if (written) written[i] = rec;
+        }
+        return;
+    }
+    const uint64_t p0 = first[i], p1 = first[i + 1u];
+    uint64_t cl = 0ull;
+    int32_t es = 0;
+    for (uint64_t p = p0 + lane; p < p1; p += 64u) {
+        cl += olen[p];
+        if (es == 0) es = st[p];
+    }
+    const uint64_t clen = pw_wave_sum64(cl);
+    const uint64_t failed = __ballot(es != 0);
+    if (failed) es = __shfl(es, __ffsll((unsigned long long)failed) - 1);
+    const uint64_t at = pos[p0], flen = PW_HEAD + clen + PW_TAIL;
+    int32_t s = 0;
+    if (es != 0) s = es;
+    else if (clen + 6ull > 0x7FFFFFFFull) s = PNG_E_ARG;
+    else if (at + flen > out_cap) s = ZMI_BUF_ERROR;
+    if (lane == 0u) {
+        out_off[i] = at;
+        out_len[i] = s == 0 ? (uint32_t)flen : 0u;
+        status[i] = s;
+        if (written) {
+            if (s == 0) {
+                rec.width = g.w; rec.height = g.h; rec.depth = (uint8_t)g.depth; rec.colour = (uint8_t)g.colour; rec.channels = (uint8_t)g.ch;
+                rec.bpp = (uint8_t)g.bpp; rec.row_bytes = g.rb; rec.idat_pos = 33u; rec.n_idat = 1u; rec.idat_bytes = (uint32_t)clen + 6u;
+            }
+            rec.status = s;
+            written[i] = rec;
+        }
+    }
+    if (s != 0) return;
+    uint8_t zh[10];
+    zmi_stream_header(1u, level, strategy, zh);
+    uint64_t hw[6] = {0x0A1A0A0D474E5089ull, 0ull, 0ull, 0ull, 0ull, 0ull}, tw[3] = {0ull, 0ull, 0ull};
+    pw_put_be32(hw, 8u, 13u);
+    pw_put_be32(hw, 12u, PNG_IHDR);
+    pw_put_be32(hw, 16u, g.w);
+    pw_put_be32(hw, 20u, g.h);
+    pw_put(hw, 24u, g.depth);
+    pw_put(hw, 25u, g.colour);
+    uint32_t c = 0xFFFFFFFFu;
+    for (uint32_t k = 12u; k < 29u; ++k) c = pw_crc_byte(c, pw_byte(hw, k));
+    pw_put_be32(hw, 29u, ~c);
+    pw_put_be32(hw, 33u, (uint32_t)clen + 6u);
+    pw_put_be32(hw, 37u, PNG_IDAT);
+    pw_put(hw, 41u, zh[0]);
+    pw_put(hw, 42u, zh[1]);
+    const uint32_t ad = adler[i];
+    pw_put_be32(tw, 0u, ad);
+    c = 0xFFFFFFFFu;
+    for (uint32_t k = 37u; k < 43u; ++k) c = pw_crc_byte(c, pw_byte(hw, k));
+    uint32_t ic = pw_crc_join(~c, crc[i], clen);
+    c = 0xFFFFFFFFu;
+    for (uint32_t k = 0u; k < 4u; ++k) c = pw_crc_byte(c, pw_byte(tw, k));
+    ic = pw_crc_join(ic, ~c, 4ull);
+    pw_put_be32(tw, 4u, ic);
+    pw_put_be32(tw, 12u, PNG_IEND);
+    pw_put_be32(tw, 16u, 0xAE426082u);
+    if (lane < PW_HEAD) out[at + lane] = pw_byte(hw, lane);
+    if (lane < PW_TAIL) out[at + PW_HEAD + clen + lane] = pw_byte(tw, lane);
+}
+
+extern "C" uint32_t zmi_png_filter_tile(void) { return PW_TILE; }
+extern "C" int zmi_launch_png_wlayout(const zmi_png_image* d_images, const uint32_t* d_in_len, uint32_t n, uint32_t piece_bytes, uint32_t* d_ssz,
+                                      uint32_t* d_nlen, uint32_t* d_npc, uint32_t* d_bands, uint64_t* d_sum, hipStream_t stream) {
+    if (n == 0) return 0;
+    ZMI_LAUNCH(zmi_png_wlayout_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_images, d_in_len, n, piece_bytes, d_ssz, d_nlen, d_npc, d_bands,
+               (unsigned long long*)d_sum);
+    return 0;
+}
+// The items are a device word; a full band is at least 2 * PW_ROWS bytes of scan_bytes, so they are at most n + scan_bytes / 16.  The grid
+// is that, or a few waves per SIMD that take the items in turn
+extern "C" int zmi_launch_png_filter(const zmi_png_image* d_images, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
+                                     const uint64_t* d_item_off, const uint64_t* d_sum, uint64_t scan_bytes, uint8_t* d_scan,
+                                     const uint64_t* d_soff, uint32_t filter, uint32_t native16, hipStream_t stream) {
+    if (n == 0) return 0;
+    const uint64_t bound = (uint64_t)n + scan_bytes / (2u * PW_ROWS);
+    const uint32_t grid = bound < 32768ull ? (uint32_t)bound : 32768u;
+    ZMI_LAUNCH(zmi_png_filter_kernel, dim3(grid), dim3(64), 0, stream, d_images, d_in, d_in_off, d_in_len, n, d_item_off, (const unsigned long long*)d_sum,
+               scan_bytes, d_scan, d_soff, filter, native16);
+    return 0;
+}
+extern "C" int zmi_launch_png_place(const uint32_t* d_head, const uint32_t* d_olen, const uint32_t* d_ends, uint32_t n, uint32_t align, uint64_t* d_pos,
+                                    hipStream_t stream) {
+    ZMI_LAUNCH(zmi_png_place_kernel, dim3(1), dim3(1024), 0, stream, d_head, d_olen, d_ends, n, align, d_pos);
+    return 0;
+}
+extern "C" int zmi_launch_png_wfinish(const zmi_png_image* d_images, const uint32_t* d_in_len, uint32_t n, const uint32_t* d_n_eff, const uint64_t* d_first,
+                                      const uint64_t* d_pos, const uint32_t* d_olen, const int32_t* d_st, const uint32_t* d_adler, const uint32_t* d_crc,
+                                      uint32_t level, uint32_t strategy, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_out_len,
+                                      int32_t* d_status, zmi_png_image* d_written, hipStream_t stream) {
+    if (n == 0) return 0;
+    ZMI_LAUNCH(zmi_png_wfinish_kernel, dim3((n + 3u) / 4u), dim3(256), 0, stream, d_images, d_in_len, n, d_n_eff, d_first, d_pos, d_olen, d_st, d_adler,
+               d_crc, level, strategy, d_out, out_cap, d_out_off, d_out_len, d_status, d_written);
     return 0;
 }

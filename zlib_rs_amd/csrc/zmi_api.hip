@@ -1591,6 +1591,152 @@ extern "C" int zmi_png_decode_dev(zmi_ctx* c, const void* d_in, const uint64_t* 
     return ZMI_E_OK;
 }
 
+// ---- writing PNG images (include/zmi355.h; the kernels: png_kernels.h, checksum.hip) -------------------------------
+// zmi_zip_write_dev's plan with the filtered scanlines in place of the entries: the filter kernel writes every image's scanlines into
+// context scratch, their pieces are one table of at most n_images + scan_bytes / piece_bytes places that goes through the
+// independent-piece encoder in launch groups (chain mode 2 with the bitmap of the pieces that end an image's stream); a group's payloads
+// are checksummed where they stand in the slots and placed behind the device word the group before ended at; the 43 + 20 fixed bytes
+// around every image's payload are written once the last group is in place.
+extern "C" uint64_t zmi_png_bound(uint32_t n_images, uint64_t scan_bytes, uint32_t piece_bytes, uint32_t out_align, int level) {
+    (void)level;
+    if (piece_bytes == 0) return 0;
+    // signature, IHDR, IDAT frame, zlib frame and IEND, and the pad, per image; per piece the slot of zmi_deflate_pieces_stride and the
+    // block headers of its regions
+    return (uint64_t)n_images * (63u + (uint64_t)(out_align ? out_align - 1u : 0u)) + scan_bytes + (scan_bytes >> 3) +
+           ((uint64_t)n_images + scan_bytes / piece_bytes) * 160u;
+}
+
+extern "C" int zmi_png_encode_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, const zmi_png_image* d_images,
+                                  uint32_t n, uint64_t scan_bytes, uint32_t flags, uint32_t filter, uint32_t piece_bytes, int level, int strategy,
+                                  uint32_t out_align, void* d_out, uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_out_len,
+                                  zmi_png_image* d_written, int32_t* d_status, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (piece_bytes == 0 || piece_bytes > (1u << 30)) return zmi_fail(ZMI_E_ARG, "piece_bytes must be 1 .. 2^30");
+    int rc = zmi_bgzf_check_args(level, strategy);
+    if (rc) return rc;
+    if (out_align == 0u || out_align > 4096u || (out_align & (out_align - 1u)) != 0u)
+        return zmi_fail(ZMI_E_ARG, "out_align must be a power of two, 1 .. 4096");
+    if (flags & ~ZMI_PNG_NATIVE16) return zmi_fail(ZMI_E_ARG, "unknown flag");
+    if (filter > ZMI_PNG_FILTER_ADAPTIVE) return zmi_fail(ZMI_E_ARG, "filter must be 0 .. 4 or ZMI_PNG_FILTER_ADAPTIVE");
+    if (n > 0x7FFFFFFFu) return zmi_fail(ZMI_E_ARG, "zmi_png_encode_dev: more than 2^31 - 1 images");
+    if (!d_out_off) return zmi_fail(ZMI_E_ARG, "d_out_off is required");
+    if ((out_cap && !d_out) || (n && (!d_in_off || !d_in_len || !d_images || !d_out_len || !d_status || (scan_bytes && !d_in))))
+        return zmi_fail(ZMI_E_ARG, "null argument");
+    const uint64_t np64 = n ? (uint64_t)n + scan_bytes / piece_bytes : 0u;
+    if (np64 > 0x7FFFFFFFull) return zmi_fail(ZMI_E_ARG, "zmi_png_encode_dev: more than 2^31 - 1 pieces");
+    if (scan_bytes > (1ull << 44)) return zmi_fail(ZMI_E_NOMEM, "scan_bytes sizes the scratch: give the bound there is");
+    const uint32_t np = (uint32_t)np64;
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    if (n == 0) {
+        ZMI_HIP(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), stream));
+        return ZMI_E_OK;
+    }
+
+    // launch groups and slots: as zmi_zip_write_dev, at every level (level 0 is deflate stored blocks from the same encoder)
+    const uint32_t max_len = scan_bytes < piece_bytes ? (uint32_t)scan_bytes : piece_bytes;
+    const uint32_t regions = zmi_enc_regions(piece_bytes, zmi_deflate_pieces_stride(piece_bytes), 65536u, kLevels[level].tok, false);
+    const uint64_t hold = (uint64_t)regions * ((zmi_enc_region_worst(max_len, regions, kLevels[level].tok, false) + 15u) & ~15ull);
+    uint64_t stride = zmi_deflate_pieces_stride(max_len);
+    if (stride < hold) stride = hold;
+    const uint64_t match_per = ((((uint64_t)max_len + 63u) & ~63ull) ? (((uint64_t)max_len + 63u) & ~63ull) : 64u) * 4u;
+    uint64_t group = c->scratch_limit / (stride + match_per + match_per / 16u);
+    if (const char* gv = zmi_tune("ZMI_STREAM_GROUP")) if (atoll(gv) > 0) group = (uint64_t)atoll(gv);
+    if (group == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one piece");
+    if (group > np) group = np;
+    rc = zmi_reserve(c->sd_slots, (size_t)(group * stride));
+    if (rc) return rc;
+    const uint32_t wpg = (uint32_t)((group + 31u) / 32u);                       // bitmap words per group
+    const uint64_t n_groups = (np + group - 1u) / group;
+    const size_t bm_words = (size_t)(n_groups * wpg);
+
+    // tables, 48 bytes per image and 40 bytes + 1 bit per place, 12 bytes per slot of a group: u64 first piece, scanline offset, first item
+    // [n + 1 each] | piece offsets in the scanlines [np] | piece places [np + 1] | slot offsets [group] | four words (the count that is
+    // valid; the sum of the scanline sizes, u64) | u32 scanline sizes, hole lengths, piece counts, bands, Adler-32, CRC-32 [n each] |
+    // piece lengths, holes, encoder sizes, statuses, Adler-32, CRC-32 [np each] | a table the slot layout fills [group] | the bitmap;
+    // then the scanlines, 64 bytes clear of either end
+    const size_t tab_bytes = (((size_t)n + 1u) * 24u + (size_t)np * 16u + 8u + (size_t)group * 8u + 16u + (size_t)n * 24u + (size_t)np * 24u +
+                              (size_t)group * 4u + bm_words * 4u + 16u + 255u) & ~(size_t)255u;
+    rc = zmi_reserve(c->png, tab_bytes + 64u + (size_t)scan_bytes + 64u);
+    if (rc) return rc;
+    uint64_t* d_first = (uint64_t*)c->png.p;
+    uint64_t* d_soff = d_first + n + 1u;
+    uint64_t* d_item_off = d_soff + n + 1u;
+    uint64_t* d_poff = d_item_off + n + 1u;
+    uint64_t* d_pos = d_poff + np;
+    uint64_t* d_slot_off = d_pos + np + 1u;
+    uint32_t* d_neff = (uint32_t*)(d_slot_off + group);
+    uint64_t* d_sum = (uint64_t*)(d_neff + 2u);       // the sum of the scanline sizes (zmi_png_wlayout_kernel)
+    uint32_t* d_ssz = d_neff + 4u;
+    uint32_t* d_nlen = d_ssz + n;
+    uint32_t* d_npc = d_nlen + n;
+    uint32_t* d_bands = d_npc + n;
+    uint32_t* d_iadler = d_bands + n;
+    uint32_t* d_icrc = d_iadler + n;
+    uint32_t* d_plen = d_icrc + n;
+    uint32_t* d_head = d_plen + np;
+    uint32_t* d_olen = d_head + np;
+    int32_t* d_st = (int32_t*)(d_olen + np);
+    uint32_t* d_padler = (uint32_t*)(d_st + np);
+    uint32_t* d_pcrc = d_padler + np;
+    uint32_t* d_slot_len = d_pcrc + np;
+    uint32_t* d_ends = d_slot_len + group;
+    int32_t* d_call = (int32_t*)(d_neff + 1u);        // the pieces kernel's call-wide status word: the slots carry that here
+    uint8_t* d_scan = (uint8_t*)c->png.p + tab_bytes + 64u;
+
+    ZMI_HIP(hipMemsetAsync(d_pos, 0, 8, stream));     // where the first group's pack starts
+    ZMI_HIP(hipMemsetAsync(d_neff, 0, 16, stream));
+    ZMI_HIP(hipMemsetAsync(d_ends, 0, bm_words * 4u, stream));
+    {
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_png_wlayout(d_images, d_in_len, n, piece_bytes, d_ssz, d_nlen, d_npc, d_bands, d_sum, stream);
+        zmi_launch_scan_sizes(d_npc, n, d_first, stream);
+        zmi_launch_scan_sizes(d_ssz, n, d_soff, stream);
+        zmi_launch_scan_sizes(d_bands, n, d_item_off, stream);
+        zmi_launch_zip_pieces(d_soff, d_ssz, d_nlen, d_first, d_sum, n, scan_bytes, piece_bytes, np, (uint32_t)group, wpg, d_poff, d_plen, d_head,
+                              d_ends, d_neff, d_call, stream);
+        zmi_launch_piece_layout(group * stride, (uint32_t)stride, (uint32_t)group, d_slot_off, d_slot_len, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_INFLATE, stream);
+        zmi_launch_png_filter(d_images, (const uint8_t*)d_in, d_in_off, d_in_len, n, d_item_off, d_sum, scan_bytes, d_scan, d_soff, filter,
+                              (flags & ZMI_PNG_NATIVE16) ? 1u : 0u, stream);
+    }
+    rc = zmi_piece_checks(c, d_scan, d_poff, d_plen, np, ZMI_WRAP_ZLIB, d_padler, stream);
+    if (rc) return rc;
+    for (uint64_t first = 0; first < np; first += group) {
+        const uint32_t cnt = (uint32_t)(np - first < group ? np - first : group);
+        const uint32_t* d_gends = d_ends + (first / group) * wpg;
+        rc = zmi_deflate_impl(c, {.d_in = d_scan, .d_in_off = d_poff + first, .d_in_len = d_plen + first, .n = cnt, .max_len = max_len,
+                                  .level = level, .strategy = strategy, .wrap = ZMI_WRAP_RAW, .chain_mode = 2u, .d_out = c->sd_slots.p,
+                                  .out_stride = stride, .d_out_len = d_olen + first, .d_status = d_st + first, .stream = stream_, .carry = 0,
+                                  .ends = d_gends, .geom_len = piece_bytes});
+        if (rc) return rc;
+        {
+            // the IDAT CRC-32 covers the COMPRESSED bytes: every piece's where it stands in its slot, folded per image below
+            zmi_scope_timer tm(c, ZMI_K_CHECKSUM, stream);
+            zmi_launch_checksum((const uint8_t*)c->sd_slots.p, d_slot_off, d_olen + first, cnt, 2u, d_pcrc + first, d_pcrc + first, stream);
+        }
+        // the group's pieces go behind the previous group's, the running offset never leaves the device
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_png_place(d_head + first, d_olen + first, d_gends, cnt, out_align, d_pos + first, stream);
+        zmi_launch_zip_pack(nullptr, d_poff + first, d_head + first, (const uint8_t*)c->sd_slots.p, stride, d_olen + first, cnt,
+                            stride > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)stride, (uint8_t*)d_out, d_pos + first, out_cap, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_CHECKSUM, stream);
+        zmi_launch_combine_segments_adler(d_padler, d_plen, d_first, n, d_neff, d_iadler, stream);
+        zmi_launch_combine_segments(d_pcrc, d_olen, d_first, n, d_neff, d_icrc, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_png_wfinish(d_images, d_in_len, n, d_neff, d_first, d_pos, d_olen, d_st, d_iadler, d_icrc, (uint32_t)level, (uint32_t)strategy,
+                               (uint8_t*)d_out, out_cap, d_out_off, d_out_len, d_status, d_written, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
 static int zmi_host_pipeline_init(zmi_ctx* c) {   // three streams (in / kernels / out) and the events of the two slots
     if (c->hb_live) return 0;
     ZMI_HIP(hipStreamCreateWithFlags(&c->hs_in, hipStreamNonBlocking));

@@ -297,4 +297,22 @@ int zmi_launch_png_unfilter(const zmi_png_image* d_images, const uint32_t* d_sel
 int zmi_launch_png_finish(const zmi_png_image* d_images, uint32_t n_images, const uint32_t* d_sel, uint32_t n_sel, const uint32_t* d_in_len,
                           const uint64_t* d_out_off, uint64_t out_cap, const uint32_t* d_ssz, const uint32_t* d_slen, const int32_t* d_sst,
                           const uint32_t* d_fl, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, hipStream_t stream);
+// writing PNG images (png_kernels.h; the piece table and the payload copies are zmi_launch_zip_pieces / zmi_launch_zip_pack): the images'
+// scanline sizes, piece counts and bands of rows (*d_sum: the sum of the sizes); the forward filter over the items -- d_item_off the scan
+// of the bands -- into the scanline scratch at d_soff; one launch group's places (d_pos[0]: where it starts,
+// d_ends: the group's bitmap); the Adler-32 of every image from its pieces' (checksum.hip); the files' fixed bytes and the images' words
+uint32_t zmi_png_filter_tile(void);
+int zmi_launch_png_wlayout(const zmi_png_image* d_images, const uint32_t* d_in_len, uint32_t n, uint32_t piece_bytes, uint32_t* d_ssz,
+                           uint32_t* d_nlen, uint32_t* d_npc, uint32_t* d_bands, uint64_t* d_sum, hipStream_t stream);
+int zmi_launch_png_filter(const zmi_png_image* d_images, const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
+                          const uint64_t* d_item_off, const uint64_t* d_sum, uint64_t scan_bytes, uint8_t* d_scan,
+                          const uint64_t* d_soff, uint32_t filter, uint32_t native16, hipStream_t stream);
+int zmi_launch_png_place(const uint32_t* d_head, const uint32_t* d_olen, const uint32_t* d_ends, uint32_t n, uint32_t align, uint64_t* d_pos,
+                         hipStream_t stream);
+int zmi_launch_combine_segments_adler(const uint32_t* d_check, const uint32_t* d_len, const uint64_t* d_first, uint32_t n,
+                                      const uint32_t* d_n_live, uint32_t* d_out, hipStream_t stream);
+int zmi_launch_png_wfinish(const zmi_png_image* d_images, const uint32_t* d_in_len, uint32_t n, const uint32_t* d_n_eff, const uint64_t* d_first,
+                           const uint64_t* d_pos, const uint32_t* d_olen, const int32_t* d_st, const uint32_t* d_adler, const uint32_t* d_crc,
+                           uint32_t level, uint32_t strategy, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_out_len,
+                           int32_t* d_status, zmi_png_image* d_written, hipStream_t stream);
 }

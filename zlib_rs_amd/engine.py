@@ -22,7 +22,7 @@ MM_HEADER, MM_TRUNC, MM_DATA, MM_CHECK, MM_LENGTH, MM_OUT, MM_BIG, MM_AGAIN = 1,
 ZA_NOEOCD, ZA_BOUNDS, ZA_CHAIN, ZA_COUNT, ZA_ZIP64, ZA_MULTIDISK = 1, 2, 3, 4, 5, 6
 ZE_LOCAL, ZE_METHOD, ZE_CRYPT, ZE_BIG, ZE_EXTRA, ZE_STORED, ZE_DATA, ZE_LENGTH, ZE_CHECK, ZE_OUT = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 ZIP_ENTRY_BYTES = 48
-# zmi_png_headers_dev / zmi_png_decode_dev (include/zmi355.h ZMI_PE_* / ZMI_PNG_*)
+# zmi_png_headers_dev / zmi_png_decode_dev / zmi_png_encode_dev (include/zmi355.h ZMI_PE_* / ZMI_PNG_*)
 (PE_SIGNATURE, PE_IHDR, PE_INTERLACE, PE_TRUNC, PE_CRITICAL, PE_ORDER, PE_BIG, PE_CRC, PE_DATA, PE_LENGTH, PE_FILTER, PE_OUT,
  PE_SCRATCH) = range(1, 14)
 PNG_NATIVE16, PNG_NO_CRC = 1, 2
@@ -328,6 +328,8 @@ class Engine:
         import ctypes as C
         self._ctx = C.c_void_p()
         _lib.check(self.L.zmi_ctx_create(C.byref(self._ctx), self.device.index), "zmi_ctx_create")
+        self.last_png_detail = None      # png_decode: the PE_* tensor of the last call
+        self.last_png_written = None     # png_encode: the table zmi_png_headers_dev would list for the files of the last call
         if scratch_bytes:
             _lib.check(self.L.zmi_ctx_set_scratch_limit(self._ctx, int(scratch_bytes)), "zmi_ctx_set_scratch_limit")
 
@@ -1094,6 +1096,103 @@ class Engine:
         out = torch.empty(guess, dtype=torch.uint8, device=self.device)
         call(out)
         return out, out_off, out_len, status
+
+    # ---- writing PNG images (include/zmi355.h) ----
+    _PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+    _PNG_COLOUR = {1: 0, 2: 4, 3: 2, 4: 6}
+
+    def png_bound(self, n_images, scan_bytes, piece_bytes=1 << 20, align=1, level=6):
+        """room that always suffices for n_images files whose filtered scanlines -- (1 + row_bytes) * height each -- are scan_bytes in all"""
+        return int(self.L.zmi_png_bound(int(n_images), int(scan_bytes), int(piece_bytes), int(align), int(level)))
+
+    def png_encode(self, images, level=6, strategy=0, filter="adaptive", piece_bytes=1 << 20, align=1, native16=True, out=None,
+                   scan_bytes=None):
+        """A batch of images as complete PNG files, one behind the other in one buffer -> (out, out_off int64 [n + 1], out_len int32
+        [n], status int32 [n]), as png_decode returns them: file i is out[out_off[i] : out_off[i] + out_len[i]], out_off[-1] the room
+        the batch needs.  images: a list of device tensors [H, W] or [H, W, C] with C 1 .. 4 (gray, gray + alpha, RGB, RGBA) of dtype
+        uint8 (depth 8) or uint16 / int16 (depth 16, the 16 bits as they stand), joined by ONE torch.cat; or the tuple (data, offsets,
+        lengths, table) of a uint8 device buffer, the int64 / int32 tables of the images' places in it and their records (a uint8
+        [n, 48] tensor or a PngBatch, of which width, height, depth and colour are read): packed depths, and what png_decode returned --
+        png_encode((data, out_off, out_len, batch)) writes a decoded batch again.  filter: "adaptive" (per row, the least sum of absolute
+        differences), "none", "sub", "up", "average", "paeth", or 0 .. 5.  native16: 16-bit samples stand little-endian in the buffer.
+        scan_bytes (the tuple form only): the caller's bound on the sum of (1 + row_bytes) * height over the images, which sizes the
+        scratch and the piece table; None: twice the buffer, which holds where no two images share bytes of it.  A per-image failure is a
+        status with length 0 and raises nothing; data and out are never copied; last_png_written keeps the table zmi_png_headers_dev
+        would list for the files.  No synchronisation."""
+        if isinstance(filter, str):
+            if filter not in self._PNG_FILTERS:
+                raise ValueError("png_encode: filter must be one of %s" % ", ".join(sorted(self._PNG_FILTERS)))
+            filter = self._PNG_FILTERS[filter]
+        if not 0 <= int(filter) <= 5:
+            raise ValueError("png_encode: filter must be 0 .. 5")
+        if align < 1 or align > 4096 or align & (align - 1):
+            raise ValueError("align must be a power of two, 1 .. 4096")
+        if out is not None and (out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous()):
+            raise ValueError("png_encode: out must be a contiguous uint8 tensor on %s" % self.device)
+        if isinstance(images, tuple) and len(images) == 4 and isinstance(images[1], torch.Tensor) and images[1].dtype in (torch.int64, torch.int32):
+            data, offsets, lengths, table = images                   # (no image has an offset table's dtype)
+            if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.device != self.device or not data.is_contiguous():
+                raise ValueError("png_encode: data must be a contiguous uint8 tensor on %s" % self.device)
+            table = table.images if isinstance(table, PngBatch) else table
+            if table.dtype != torch.uint8 or table.device != self.device or table.dim() != 2 or table.shape[1] != PNG_IMAGE_BYTES:
+                raise ValueError("png_encode: the table must be a uint8 [n, %d] tensor on %s" % (PNG_IMAGE_BYTES, self.device))
+            table = table.contiguous()
+            n = int(table.shape[0])
+            offsets = offsets.to(device=self.device, dtype=torch.int64).contiguous()
+            lengths = lengths.to(device=self.device, dtype=torch.int32).contiguous()
+            if int(offsets.numel()) < n or int(lengths.numel()) < n:
+                raise ValueError("png_encode: %d records need %d offsets and lengths" % (n, n))
+            # (1 + row_bytes) * height <= 2 * row_bytes * height: the buffer bounds the scanlines without a look at the device
+            scan_bytes = 2 * int(data.numel()) if scan_bytes is None else int(scan_bytes)
+        else:
+            import numpy as np
+            if scan_bytes is not None:
+                raise ValueError("png_encode: scan_bytes goes with (data, offsets, lengths, table); a list's shapes give it")
+            if not isinstance(images, (list, tuple)) or len(images) == 0:
+                raise ValueError("png_encode: images must be a non-empty list of tensors or (data, offsets, lengths, table)")
+            table = np.zeros((len(images), PNG_IMAGE_BYTES), dtype=np.uint8)
+            words, parts, offs, lens, at, scan_bytes = table.view("<u4"), [], [], [], 0, 0
+            for k, t in enumerate(images):
+                if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype not in (torch.uint8, torch.uint16, torch.int16):
+                    raise ValueError("png_encode: image %d must be a uint8, uint16 or int16 tensor on %s" % (k, self.device))
+                if t.dim() not in (2, 3) or (t.dim() == 3 and not 1 <= t.shape[2] <= 4) or t.numel() == 0:
+                    raise ValueError("png_encode: image %d must be [H, W] or [H, W, C] with C 1 .. 4, not %s" % (k, tuple(t.shape)))
+                c = 1 if t.dim() == 2 else int(t.shape[2])
+                words[k, 0], words[k, 1] = int(t.shape[1]), int(t.shape[0])
+                table[k, 8], table[k, 9] = 8 * t.element_size(), self._PNG_COLOUR[c]
+                body = t.contiguous().view(-1).view(torch.uint8)
+                parts.append(body)
+                offs.append(at)
+                lens.append(int(body.numel()))
+                at += lens[-1]
+                scan_bytes += lens[-1] + int(t.shape[0])
+            data = parts[0] if len(parts) == 1 else torch.cat(parts)
+            n = len(images)
+            offsets = torch.tensor(offs, dtype=torch.int64, device=self.device)
+            lengths = torch.tensor(lens, dtype=torch.int32, device=self.device)
+            table = torch.from_numpy(table).to(self.device)
+        if out is None:
+            out = torch.empty(self.png_bound(n, scan_bytes, piece_bytes, align, level), dtype=torch.uint8, device=self.device)
+        out_off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        out_len = torch.zeros(n, dtype=torch.int32, device=self.device)
+        status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        self.last_png_written = written = torch.zeros((n, PNG_IMAGE_BYTES), dtype=torch.uint8, device=self.device)
+        _lib.check(self.L.zmi_png_encode_dev(self._ctx, data.data_ptr() if data.numel() else None, offsets.data_ptr() if n else None,
+                                             lengths.data_ptr() if n else None, table.data_ptr() if n else None, n, int(scan_bytes),
+                                             PNG_NATIVE16 if native16 else 0, int(filter), int(piece_bytes), int(level), int(strategy), int(align),
+                                             out.data_ptr() if out.numel() else None, int(out.numel()), out_off.data_ptr(),
+                                             out_len.data_ptr() if n else None, written.data_ptr() if n else None,
+                                             status.data_ptr() if n else None, _stream_ptr()), "zmi_png_encode_dev")
+        return out, out_off, out_len, status
+
+    def save_png(self, tensor, **kw):
+        """One image ([H, W] or [H, W, C], uint8 / uint16 / int16, on the device) -> the bytes of its .png file; a status that is not 0
+        raises.  Keywords as png_encode's."""
+        out, off, ln, st = self.png_encode([tensor], **kw)
+        host = torch.stack([ln.to(torch.int64), st.to(torch.int64)]).view(-1).tolist()
+        if host[1] != 0:
+            raise RuntimeError("zmi_png_encode_dev: status %d" % host[1])
+        return out[:host[0]].cpu().numpy().tobytes()
 
     # ---- writing ZIP archives (include/zmi355.h, DESIGN.md section 21) ----
     def zip_bound(self, n_entries, names_bytes, in_bytes, piece_bytes=1 << 20, level=6):

@@ -918,6 +918,127 @@ int zmi_png_encode_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off,
                        uint64_t* d_out_off /* n_images + 1 */, uint32_t* d_out_len, zmi_png_image* d_written /* NULL or n_images */,
                        int32_t* d_status, void* stream);
 
+/* ---- reading TIFF files with Deflate compression: the IFD chain, a batch inflate of strips or tiles, the predictor undo ----------------
+ * A TIFF is a header (TIFF 6.0 section 2: II or MM, magic 42, the offset of the first image file directory) and a chain of IFDs, one a
+ * page: a count, entries of tag | type | count | value-or-offset, the offset of the next IFD, 0 at the end.  BigTIFF, as libtiff reads
+ * it: magic 43, offset size 8, a reserved 0, 64-bit offsets and counts, entries of 20 bytes, an 8-byte entry count.  A page is cut
+ * into strips (section 3) or tiles (section 15), every segment compressed on its own -- Deflate is compression 8 of the Adobe Photoshop
+ * TIFF Technical Notes, 32946 the older code for the same zlib stream -- and the file holds the table of the segments' offsets and byte
+ * counts.  Behind the decoder stands the predictor: horizontal differencing (section 14) or the floating-point predictor of Adobe
+ * Technical Note 3.  Two calls, both asynchronous on `stream`, neither synchronises with the host, every per-file and per-segment
+ * failure is a device word; positions are 64-bit and d_in may stand at any alignment.  TIFF is not part of the reference project: the
+ * contract is these documents.  Not read: LZW, JPEG, ZSTD, LERC, PackBits; PlanarConfiguration 2; depths below 8; SubIFDs (tag 330 is
+ * not followed); YCbCr subsampling and colour maps (the photometric value is listed, nothing more); segments of 4 GiB or more.
+ *
+ * zmi_tiff_directory_dev   takes the whole file d_in[0 .. in_len).  *d_info: status 0, or Z_DATA_ERROR with detail
+ *   ZMI_TA_HEADER       not II / MM with magic 42, or magic 43 with offset size 8 and a reserved word of 0
+ *   ZMI_TA_CHAIN | index << 8    IFD number `index` leaves the file, has 0 entries, or stands behind ZMI_TIFF_PAGES_MAX IFDs already
+ *                       walked (the guard against a chain that loops); a first-IFD offset of 0 is index 0.  The IFDs in front of it
+ *                       are counted and listed all the same.
+ *   n_pages = the IFDs walked, n_listed = min(n_pages, cap): more pages than cap is no error, and cap 0 counts.  One lane follows the
+ *   chain; the tags of the listed pages are read by a thread per page, in whatever order they stand (real writers do not keep them
+ *   ascending; of a tag that stands twice the first counts): 256 ImageWidth, 257 ImageLength, 258 BitsPerSample, 259 Compression, 262
+ *   PhotometricInterpretation, 273 StripOffsets, 277 SamplesPerPixel, 278 RowsPerStrip, 279 StripByteCounts, 284 PlanarConfiguration,
+ *   317 Predictor, 322 TileWidth, 323 TileLength, 324 TileOffsets, 325 TileByteCounts, 338 ExtraSamples (its count only), 339
+ *   SampleFormat (its first value).  Defaults (section 8): BitsPerSample 1, SamplesPerPixel 1, Compression 1, RowsPerStrip 2^32 - 1,
+ *   PlanarConfiguration 1, Predictor 1, SampleFormat 1.  Scalars may be BYTE, SHORT, LONG or LONG8, the two arrays SHORT, LONG or LONG8;
+ *   a value that fits the entry's value field (4 bytes, BigTIFF 8) stands there, and the record keeps the file position of the value
+ *   bytes either way.  The record's status is the first of these that holds:
+ *   ZMI_TP_TAGS         width, height or one of the segment tags is missing; both or neither of the strip tags (273, 279) and the tile
+ *                       tags (322 .. 325) are present; an array's count is not n_segs; an array or a read value leaves the file or has
+ *                       another type; a dimension, a tile size or RowsPerStrip is 0                                   (Z_DATA_ERROR)
+ *   ZMI_TP_FORMAT       BitsPerSample differs between samples; a depth that is not 8 / 16 / 32 / 64; predictor 3 with a SampleFormat
+ *                       other than 3 or a depth below 16; predictor 0 or above 3; samples 0 or above 8             (Z_DATA_ERROR)
+ *   ZMI_TP_COMPRESSION  anything but 1, 8 and 32946                                                                (Z_VERSION_ERROR)
+ *   ZMI_TP_PLANAR       PlanarConfiguration 2                                                                      (Z_VERSION_ERROR)
+ *   ZMI_TP_BIG          seg_bytes does not fit 32 bits: the field reads 0xFFFFFFFF                                 (Z_VERSION_ERROR)
+ *   A flagged page is listed with what was read of it; the geometry fields of a ZMI_TP_TAGS page are 0.
+ *
+ * zmi_tiff_read_dev     slot j reads segment d_sel[j] of page `page` of the table d_pages[0 .. n_pages) (d_sel NULL: slot j = segment
+ *               j); segments are numbered row by row, duplicates are allowed.  An index >= the page's n_segs, a page index >= n_pages
+ *               and a record no directory call would write for a file of in_len bytes (arrays that leave it, sizes that do not follow
+ *               from the fields) get ZMI_E_ARG in the slot's status, and nothing of them is read.
+ *   Region      default (dense): rows * seg_w * samples * sample_bytes bytes, rows = seg_h but for the last strip of a page, which has
+ *               the rows left, height - k * seg_h: the decoded segment with the predictor undone and every sample in the machine's
+ *               little-endian order whatever the file's, a [rows, seg_w, C] tensor as it stands; edge tiles keep their padding columns
+ *               and rows.  d_out_off, out_align, out_cap as zmi_png_decode_dev: d_out_off[j] = the sum of the region sizes of the
+ *               slots in front that read a segment, each rounded up to out_align (a power of two, 1 .. 4096, otherwise ZMI_E_ARG);
+ *               d_out_off[n_sel] = the room the selection needs whether or not it fitted; a slot that ends behind out_cap reports
+ *               Z_BUF_ERROR / ZMI_TE_OUT; nothing at or behind d_out + out_cap and nothing in the gaps is written.  A flagged page
+ *               and a bad index take no room, a failed segment keeps the room the plan gave it.
+ *   flags & ZMI_TIFF_ASSEMBLE   the output is the page as ONE [height, width, C] image of height * width * samples * sample_bytes
+ *               bytes at d_out: every selected segment is written at its place, cropped at the right and the bottom edge; what no
+ *               selected segment covers is left untouched.  d_out_off[j] = the byte offset of the segment's first pixel,
+ *               d_out_off[n_sel] = the image's size (0 where the page is not readable); an image that does not fit out_cap is
+ *               Z_BUF_ERROR / ZMI_TE_OUT in every slot; out_align is ignored.  d_out_len[j] = the bytes of the cropped segment.
+ *   decoded_bytes   the caller's bound on the sum of the decoded sizes (the dense region sizes, in either mode) of the slots that
+ *               read a segment -- what scan_bytes is to zmi_png_encode_dev: it sizes the scratch that holds the still-predicted
+ *               bytes.  A larger true sum is ZMI_E_ARG in every slot, and nothing is written.
+ *   Reading     one kernel reads offset and byte count of every slot from the file's two arrays, in the file's byte order and the
+ *               array's value type.  Compression 8 / 32946 goes through the batch decoder with ZMI_WRAP_ZLIB and capacity = the decoded
+ *               size into scratch, which checks the Adler-32; compression 1 goes through the range copy.  A segment with byte count 0
+ *               is sparse (GDAL writes missing tiles so): its region is zero bytes, its status 0, its detail ZMI_TE_SPARSE.  The
+ *               unpredict kernel writes the regions: predictor 1 copies (MM files: the bytes of every sample swapped); predictor 2
+ *               (section 14) is x[i] = d[i] + x[i - samples] mod 2^(8 * sample_bytes) along a row, d read in the file's byte order,
+ *               integer arithmetic on the bits whatever SampleFormat says; predictor 3 (Technical Note 3) is p[i] = q[i] +
+ *               p[i - samples] mod 256 over the row's bytes, after which byte b of sample k is p[b * seg_w * samples + k], b = 0 the
+ *               most significant in II and MM files alike.  One kernel writes the slot's words, the first of these that holds:
+ *   d_status / d_detail   Z_DATA_ERROR or Z_VERSION_ERROR / the record's ZMI_TP_*   the page is flagged (see above)
+ *               Z_BUF_ERROR / ZMI_TE_OUT        the region (assemble: the image) does not fit out_cap
+ *               Z_DATA_ERROR / ZMI_TE_BOUNDS    offset + byte count leaves the file, or the byte count is 4 GiB or more
+ *               0 / ZMI_TE_SPARSE               byte count 0
+ *               Z_DATA_ERROR / ZMI_TE_DATA      a corrupt zlib stream, a wrong Adler-32, FDICT set
+ *               Z_DATA_ERROR / ZMI_TE_LENGTH    the stream -- compression 1: the byte count -- ends before or behind exactly the decoded
+ *                                               size.  Bytes behind the end of the zlib stream but inside the byte count are no error
+ *                                               (libtiff accepts them).
+ *   d_out_len[j] = the region's size with status 0, otherwise 0.  Never status 0 with wrong bytes; one bad segment does not touch its
+ *   neighbours.  n_sel 0 writes d_out_off[0] = 0 and nothing else.  Bytes and words do not depend on the alignment of d_in, on n_sel,
+ *   on the slot index or on the decode-kernel selection.
+ *   Scratch of the context: 8 bytes per page of cap (the directory call); 96 bytes per slot; the still-predicted bytes, decoded_bytes
+ *   + 16 bytes per slot + 96; and the decoder's, sized by this call from decoded_bytes.  Scratch that cannot be reserved is ZMI_E_NOMEM.
+ *   Event timing: 5 = directory; slot tables and plans, 3 / 6 = decode, resolve (the decoder's own Adler-32 pass adds to 0, its verify
+ *   to 4), 7 = the copies of compression 1, 2 = the unpredict (the encoder's slot is idle on every read path: where the PNG reader put
+ *   its unfilter), 4 = the slot words. */
+#define ZMI_TA_HEADER 1      /* zmi_tiff_info.detail & 0xFF, status Z_DATA_ERROR */
+#define ZMI_TA_CHAIN 2       /* ... the index of the first bad IFD above the low 8 bits */
+#define ZMI_TP_TAGS 1        /* zmi_tiff_page.status and the slot's detail: Z_DATA_ERROR */
+#define ZMI_TP_FORMAT 2      /* Z_DATA_ERROR */
+#define ZMI_TP_COMPRESSION 3 /* Z_VERSION_ERROR */
+#define ZMI_TP_PLANAR 4      /* Z_VERSION_ERROR */
+#define ZMI_TP_BIG 5         /* Z_VERSION_ERROR */
+#define ZMI_TE_OUT 6         /* slots only, from here on: Z_BUF_ERROR */
+#define ZMI_TE_BOUNDS 7      /* Z_DATA_ERROR */
+#define ZMI_TE_DATA 8
+#define ZMI_TE_LENGTH 9
+#define ZMI_TE_SPARSE 10     /* status 0 */
+#define ZMI_TIFF_ASSEMBLE 1u /* flags: the page as one image */
+#define ZMI_TIFF_PAGES_MAX 65535u
+typedef struct zmi_tiff_page {      /* 72 bytes */
+    uint64_t offsets_pos, counts_pos; /* file positions of the values of StripOffsets / TileOffsets and of the byte counts */
+    uint32_t width, height;
+    uint32_t seg_w, seg_h;            /* tile size; strips: seg_w = width, seg_h = min(RowsPerStrip, height) */
+    uint32_t segs_across, segs_down, n_segs;
+    uint32_t seg_bytes;               /* decoded bytes of a full segment: seg_w * seg_h * samples * sample_bytes */
+    uint16_t bits, samples, sample_format, predictor, compression, photometric, extra_samples;
+    uint8_t  sample_bytes;            /* bits / 8; 0 where the depth is not 8 / 16 / 32 / 64 */
+    uint8_t  big_endian, bigtiff, tiled;
+    uint8_t  offsets_type, counts_type;   /* 3 SHORT, 4 LONG, 16 LONG8 */
+    int32_t  status;                  /* 0: readable by zmi_tiff_read_dev; otherwise the ZMI_TP_* reason */
+} zmi_tiff_page;
+typedef struct zmi_tiff_info {      /* 40 bytes */
+    uint64_t n_pages, n_listed, first_ifd;
+    uint32_t big_endian, bigtiff;
+    int32_t status, detail;
+} zmi_tiff_info;
+uint32_t zmi_tiff_row_tile(void);   /* bytes of a row one trip of the unpredict kernel covers per wave (for tests that place row lengths
+                                       around it): pixel sizes that do not divide 16 make the trip a little shorter, see tiff_kernels.h */
+int zmi_tiff_directory_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, zmi_tiff_page* d_pages, uint32_t cap, zmi_tiff_info* d_info,
+                           void* stream);
+int zmi_tiff_read_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, const zmi_tiff_page* d_pages, uint32_t n_pages, uint32_t page,
+                      const uint32_t* d_sel, uint32_t n_sel, uint64_t decoded_bytes, uint32_t flags, uint32_t out_align, void* d_out,
+                      uint64_t out_cap, uint64_t* d_out_off /* n_sel + 1 */, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail,
+                      void* stream);
+
 /* ---- host-buffer convenience wrappers: copy in, run the batch on the GPU, copy back ---- */
 int zmi_deflate_batch(zmi_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_shards,
                       int level, int strategy, int wrap, uint8_t* out, uint64_t out_stride, uint32_t* out_len,

@@ -91,6 +91,11 @@ def lib():
     L.zmi_png_bound.restype = u64
     L.zmi_png_bound.argtypes = [u32, u64, u32, u32, i32]
     L.zmi_png_encode_dev.argtypes = [vp, vp, vp, vp, vp, u32, u64, u32, u32, u32, i32, i32, u32, vp, u64, vp, vp, vp, vp, vp]
+    # reading TIFF files: the IFD chain, a batch inflate of strips or tiles, the predictor undo (csrc/tiff_kernels.h, zmi_api.hip)
+    L.zmi_tiff_row_tile.restype = u32
+    L.zmi_tiff_row_tile.argtypes = []
+    L.zmi_tiff_directory_dev.argtypes = [vp, vp, u64, vp, u32, vp, vp]
+    L.zmi_tiff_read_dev.argtypes = [vp, vp, u64, vp, u32, u32, vp, u32, u64, u32, u32, vp, u64, vp, vp, vp, vp, vp]
     # the multi-GPU stitch (csrc/exchange.hip); RCCL itself is loaded by the library on first use
     L.zmi_comm_unique_id.argtypes = [vp]
     L.zmi_comm_create.argtypes = [C.POINTER(vp), vp, i32, i32, vp]

@@ -1191,3 +1191,6 @@ extern "C" int zmi_launch_zip_close(uint8_t* d_out, uint64_t out_cap, const uint
 
 // ---- reading PNG images (zmi_png_headers_dev / zmi_png_decode_dev) ------------------------------------------------------------------------
 #include "png_kernels.h"
+
+// ---- reading TIFF files (zmi_tiff_directory_dev / zmi_tiff_read_dev) ---------------------------------------------------------------------
+#include "tiff_kernels.h"

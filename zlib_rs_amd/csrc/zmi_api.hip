@@ -105,6 +105,8 @@ struct zmi_ctx {
     zmi_buf mm_scan, mm_meta;           // zmi_gzip_find_members_dev: segment counts and offsets; zmi_inflate_members_dev: its tables
     zmi_buf pk;                         // zmi_inflate_batch_packed_dev: size[n] cap[n] (the size pass's result, the planned capacity table)
     zmi_buf zip_dir, zip_sel;           // zmi_zip_directory_dev: four words, the chain positions, four words per segment; zmi_zip_inflate_dev: the slots' tables
+    zmi_buf tiff_dir;                   // zmi_tiff_directory_dev: the positions of the listed IFDs
+    zmi_buf tiff;                       // zmi_tiff_read_dev: the slots' tables | the still-predicted segments
     zmi_buf png;                        // zmi_png_decode_dev: the slots' tables | the gathered IDAT streams | the filtered scanlines
     zmi_buf dict;                       // the shared-dictionary batch calls: layout words and DICTID | deflate image | inflate image (zmi_sd_*)
 };
@@ -167,6 +169,8 @@ extern "C" int zmi_ctx_destroy(zmi_ctx* c) {
     if (c->zip_dir.p) (void)hipFree(c->zip_dir.p);
     if (c->zip_sel.p) (void)hipFree(c->zip_sel.p);
     if (c->png.p) (void)hipFree(c->png.p);
+    if (c->tiff.p) (void)hipFree(c->tiff.p);
+    if (c->tiff_dir.p) (void)hipFree(c->tiff_dir.p);
     if (c->mm_scan.p) (void)hipFree(c->mm_scan.p);
     if (c->mm_meta.p) (void)hipFree(c->mm_meta.p);
     for (int k = 0; k < 2; ++k) if (c->st_pin[k].p) (void)hipHostFree(c->st_pin[k].p);
@@ -1586,6 +1590,100 @@ extern "C" int zmi_png_decode_dev(zmi_ctx* c, const void* d_in, const uint64_t* 
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
         zmi_launch_png_finish(d_images, n_images, d_sel, n_sel, d_in_len, d_out_off, out_cap, d_ssz, d_slen, d_sst, d_fl, d_out_len, d_status,
                               d_detail, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+// ---- TIFF files (include/zmi355.h; kernels in tiff_kernels.h) -------------------------------------------------------
+extern "C" int zmi_tiff_directory_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, zmi_tiff_page* d_pages, uint32_t cap, zmi_tiff_info* d_info,
+                                      void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (!d_info || (in_len && !d_in) || (cap && !d_pages)) return zmi_fail(ZMI_E_ARG, "null argument");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    int rc = zmi_reserve(c->tiff_dir, 64u + (size_t)cap * 8u);
+    if (rc) return rc;
+    {
+        zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
+        zmi_launch_tiff_directory((const uint8_t*)d_in, in_len, d_pages, cap, d_info, (uint64_t*)c->tiff_dir.p, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+extern "C" int zmi_tiff_read_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, const zmi_tiff_page* d_pages, uint32_t n_pages, uint32_t page,
+                                 const uint32_t* d_sel, uint32_t n_sel, uint64_t decoded_bytes, uint32_t flags, uint32_t out_align, void* d_out,
+                                 uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (flags & ~ZMI_TIFF_ASSEMBLE) return zmi_fail(ZMI_E_ARG, "unknown flag");
+    const uint32_t assemble = (flags & ZMI_TIFF_ASSEMBLE) ? 1u : 0u;
+    if (!assemble && (out_align == 0u || out_align > 4096u || (out_align & (out_align - 1u)) != 0u))
+        return zmi_fail(ZMI_E_ARG, "out_align must be a power of two, 1 .. 4096");
+    if (!d_out_off) return zmi_fail(ZMI_E_ARG, "d_out_off is required");
+    if (n_sel > 0x7FFFFFFFu) return zmi_fail(ZMI_E_ARG, "n_sel must be below 2^31");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    if (n_sel == 0) {
+        ZMI_HIP(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), stream));
+        return ZMI_E_OK;
+    }
+    if (!d_out_len || !d_status || !d_detail) return zmi_fail(ZMI_E_ARG, "d_out_len, d_status and d_detail are required");
+    if ((n_pages && !d_pages) || (in_len && !d_in) || (out_cap && !d_out)) return zmi_fail(ZMI_E_ARG, "null argument");
+    if (decoded_bytes > (1ull << 44)) return zmi_fail(ZMI_E_NOMEM, "decoded_bytes sizes the scratch: give the sum there is");
+    // The still-predicted segments stand in scratch, every one at a multiple of 16 (the decoder's own plan over d_ssz), 16 bytes of
+    // margin on either side: the unpredict stages whole dwords around a row.
+    const size_t n = n_sel;
+    const uint64_t scan_cap = decoded_bytes + 16ull * n + 64ull;
+    const size_t tab_bytes = ((4u * n + 3u) * 8u + 14u * n * 4u + 255u) & ~(size_t)255u;
+    int rc = zmi_reserve(c->tiff, tab_bytes + 16u + scan_cap + 16u);
+    if (rc) return rc;
+    uint64_t* d_soff = (uint64_t*)c->tiff.p;                      // where the segment of a slot stands in scratch (the decoder's plan over d_ssz)
+    uint64_t* d_item_off = d_soff + n + 1;                       // the scan of d_items
+    uint64_t* d_pix_off = d_item_off + n + 1;                    // the scan of d_pix: its last word is the sum decoded_bytes bounds
+    uint64_t* d_zin_off = d_pix_off + n + 1;                     // the segment's place in the file
+    uint32_t* d_pix = (uint32_t*)(d_zin_off + n);                // the decoded size of a slot that reads a segment, else 0
+    uint32_t* d_pcap = d_pix + n;                                // ... where its region fits out_cap, else 0
+    uint32_t* d_ssz = d_pcap + n;                                // ... where its bytes are fetched: not sparse, inside the file
+    uint32_t* d_scap = d_ssz + n;
+    uint32_t* d_zin_len = d_scap + n;                            // the byte count of a deflated slot
+    uint32_t* d_rawlen = d_zin_len + n;                          // the bytes to copy for a slot of compression 1
+    uint32_t* d_items = d_rawlen + n;                            // groups of TIFF_ROWS rows
+    uint32_t* d_fl = d_items + n;                                // TIFF_FL_*
+    uint32_t* d_slen = d_fl + n;                                 // the decoder's words
+    uint32_t* d_sused = d_slen + n;
+    int32_t* d_sst = (int32_t*)(d_sused + n);
+    int32_t* d_sdet = d_sst + n;
+    uint8_t* d_sbuf = (uint8_t*)c->tiff.p + tab_bytes + 16u;
+    const uint8_t* in = (const uint8_t*)d_in;
+    {
+        zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
+        zmi_launch_tiff_slots(in, in_len, d_pages, n_pages, page, d_sel, n_sel, assemble, 0u, out_cap, decoded_bytes, nullptr, d_pix, d_pcap, d_zin_off,
+                              d_zin_len, nullptr, nullptr, nullptr, d_fl, d_out_off, stream);
+        if (!assemble) zmi_launch_inflate_pack_plan(d_pix, n_sel, out_align, out_cap, d_out_off, d_pcap, stream);
+        zmi_launch_scan_sizes(d_pix, n_sel, d_pix_off, stream);
+        zmi_launch_tiff_slots(in, in_len, d_pages, n_pages, page, d_sel, n_sel, assemble, 1u, out_cap, decoded_bytes, d_pix_off, d_pix, d_pcap,
+                              d_zin_off, d_zin_len, d_ssz, d_rawlen, d_items, d_fl, d_out_off, stream);
+        zmi_launch_scan_sizes(d_items, n_sel, d_item_off, stream);
+    }
+    rc = zmi_inflate_packed_body(c, d_in, d_zin_off, d_zin_len, n_sel, ZMI_WRAP_ZLIB, nullptr, 0u, d_ssz, d_scap, 16u, d_sbuf, scan_cap, d_soff,
+                                 d_slen, d_sst, d_sused, d_sdet, ZMI_K_PARSE, stream_);
+    if (rc) return rc;
+    {
+        // compression 1: the segment's bytes as they stand (max_len only shapes the launch)
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_copy_ranges(in, d_zin_off, 0u, d_rawlen, n_sel, d_sbuf, d_soff, scan_cap, in_len > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)in_len,
+                               stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_ENCODE, stream);
+        zmi_launch_tiff_unpredict(d_pages, n_pages, page, d_sel, n_sel, in_len, assemble, d_item_off, decoded_bytes / 8u + n, d_sbuf, d_soff, d_ssz,
+                                  d_slen, d_sst, d_rawlen, d_fl, (uint8_t*)d_out, d_out_off, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_tiff_finish(d_pages, n_pages, page, d_sel, n_sel, in_len, assemble, out_cap, decoded_bytes, d_pix_off, d_out_off, d_ssz, d_slen,
+                               d_sst, d_fl, d_out_len, d_status, d_detail, stream);
     }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;

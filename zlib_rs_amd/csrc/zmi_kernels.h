@@ -65,6 +65,8 @@ struct zmi_enc_params {
 struct zmi_zip_entry;   // include/zmi355.h
 struct zmi_zip_info;
 struct zmi_png_image;
+struct zmi_tiff_page;
+struct zmi_tiff_info;
 
 extern "C" {
 int zmi_launch_gen(uint8_t* d_out, uint64_t seed, uint32_t first_shard, uint32_t n_shards, uint32_t shard_bytes,
@@ -315,4 +317,22 @@ int zmi_launch_png_wfinish(const zmi_png_image* d_images, const uint32_t* d_in_l
                            const uint64_t* d_pos, const uint32_t* d_olen, const int32_t* d_st, const uint32_t* d_adler, const uint32_t* d_crc,
                            uint32_t level, uint32_t strategy, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_out_len,
                            int32_t* d_status, zmi_png_image* d_written, hipStream_t stream);
+// TIFF files (tiff_kernels.h, compiled into pack.hip): the IFD chain and the pages' records (d_ifd_pos: cap words of scratch); the slots'
+// tables (pass 0 in front of the plan, pass 1 behind it and behind the scan d_pix_off of the decoded sizes); the unpredict over the row
+// groups -- d_item_off the scan of d_items -- from the scratch at d_soff to the regions; the slots' final words
+uint32_t zmi_tiff_row_tile(void);
+int zmi_launch_tiff_directory(const uint8_t* d_in, uint64_t in_len, zmi_tiff_page* d_pages, uint32_t cap, zmi_tiff_info* d_info,
+                              uint64_t* d_ifd_pos, hipStream_t stream);
+int zmi_launch_tiff_slots(const uint8_t* d_in, uint64_t in_len, const zmi_tiff_page* d_pages, uint32_t n_pages, uint32_t page,
+                          const uint32_t* d_sel, uint32_t n_sel, uint32_t assemble, uint32_t pass, uint64_t out_cap, uint64_t decoded_bytes,
+                          const uint64_t* d_pix_off, uint32_t* d_pix, uint32_t* d_pcap, uint64_t* d_zin_off, uint32_t* d_zin_len,
+                          uint32_t* d_ssz, uint32_t* d_rawlen, uint32_t* d_items, uint32_t* d_fl, uint64_t* d_out_off, hipStream_t stream);
+int zmi_launch_tiff_unpredict(const zmi_tiff_page* d_pages, uint32_t n_pages, uint32_t page, const uint32_t* d_sel, uint32_t n_sel,
+                              uint64_t in_len, uint32_t assemble, const uint64_t* d_item_off, uint64_t bound, uint8_t* d_sbuf,
+                              const uint64_t* d_soff, const uint32_t* d_ssz, const uint32_t* d_slen, const int32_t* d_sst,
+                              const uint32_t* d_rawlen, const uint32_t* d_fl, uint8_t* d_out, const uint64_t* d_out_off, hipStream_t stream);
+int zmi_launch_tiff_finish(const zmi_tiff_page* d_pages, uint32_t n_pages, uint32_t page, const uint32_t* d_sel, uint32_t n_sel,
+                           uint64_t in_len, uint32_t assemble, uint64_t out_cap, uint64_t decoded_bytes, const uint64_t* d_pix_off,
+                           const uint64_t* d_out_off, const uint32_t* d_ssz, const uint32_t* d_slen, const int32_t* d_sst,
+                           const uint32_t* d_fl, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, hipStream_t stream);
 }

@@ -27,6 +27,11 @@ ZIP_ENTRY_BYTES = 48
  PE_SCRATCH) = range(1, 14)
 PNG_NATIVE16, PNG_NO_CRC = 1, 2
 PNG_IMAGE_BYTES = 48
+# zmi_tiff_directory_dev / zmi_tiff_read_dev (include/zmi355.h ZMI_TA_* / ZMI_TP_* / ZMI_TE_* / ZMI_TIFF_*)
+TA_HEADER, TA_CHAIN = 1, 2
+TP_TAGS, TP_FORMAT, TP_COMPRESSION, TP_PLANAR, TP_BIG, TE_OUT, TE_BOUNDS, TE_DATA, TE_LENGTH, TE_SPARSE = range(1, 11)
+TIFF_ASSEMBLE = 1
+TIFF_PAGE_BYTES, TIFF_INFO_BYTES = 72, 40
 
 
 def _stream_ptr():
@@ -319,6 +324,75 @@ class ZipDirectory:
         raise KeyError(name)
 
 
+class TiffFile:
+    """A TIFF file as zmi_tiff_directory_dev lists it (include/zmi355.h).  data: the file on the device; pages: uint8 [n, 72], the
+    device table of zmi_tiff_page records; info: the host copy of zmi_tiff_info as a dict.  The table is copied to the host once, when
+    the first geometry is asked for."""
+    _FIELDS = [("offsets_pos", "<u8"), ("counts_pos", "<u8"), ("width", "<u4"), ("height", "<u4"), ("seg_w", "<u4"), ("seg_h", "<u4"),
+               ("segs_across", "<u4"), ("segs_down", "<u4"), ("n_segs", "<u4"), ("seg_bytes", "<u4"), ("bits", "<u2"), ("samples", "<u2"),
+               ("sample_format", "<u2"), ("predictor", "<u2"), ("compression", "<u2"), ("photometric", "<u2"), ("extra_samples", "<u2"),
+               ("sample_bytes", "u1"), ("big_endian", "u1"), ("bigtiff", "u1"), ("tiled", "u1"), ("offsets_type", "u1"),
+               ("counts_type", "u1"), ("status", "<i4")]
+
+    def __init__(self, data, pages, info):
+        self.data, self.pages, self.info = data, pages, info
+        self._host = None
+
+    @property
+    def n_pages(self):
+        """the pages listed (info["n_pages"]: the pages the file has)"""
+        return int(self.pages.shape[0])
+
+    @property
+    def status(self):
+        """int32 [n]: 0 = readable, else the TP_* reason"""
+        return self.pages.view(torch.int32)[:, 17]
+
+    @property
+    def readable(self):
+        return self.status == 0
+
+    def record(self, p):
+        """the host copy of record p as a dict"""
+        if self._host is None:
+            import numpy as np
+            self._host = self.pages.cpu().numpy().view(np.dtype(self._FIELDS)).reshape(-1)
+        r = self._host[p]
+        return {name: int(r[name]) for name, _ in self._FIELDS}
+
+    def shape(self, p):
+        r = self.record(p)
+        return (r["height"], r["width"], r["samples"])
+
+    def tile_shape(self, p):
+        """[rows, columns, samples] of a full segment: a tile, or a strip of seg_h rows"""
+        r = self.record(p)
+        return (r["seg_h"], r["seg_w"], r["samples"])
+
+    def grid(self, p):
+        """(segments down, segments across); segment k stands at divmod(k, across)"""
+        r = self.record(p)
+        return (r["segs_down"], r["segs_across"])
+
+    def dtype(self, p):
+        """the torch dtype of a sample: SampleFormat 2 signed, 3 float (16 / 32 / 64 bits), everything else unsigned"""
+        r = self.record(p)
+        sb = r["sample_bytes"]
+        if r["sample_format"] == 3 and sb >= 2:
+            return {2: torch.float16, 4: torch.float32, 8: torch.float64}[sb]
+        if r["sample_format"] == 2:
+            return {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}.get(sb, torch.uint8)
+        return {1: torch.uint8, 2: torch.uint16, 4: torch.uint32, 8: torch.uint64}.get(sb, torch.uint8)
+
+    def segment_bytes(self, p, k):
+        """decoded bytes of segment k of page p: seg_bytes, but the rows left for the last strip; 0 for what cannot be read"""
+        r = self.record(p)
+        if r["status"] != 0 or not 0 <= k < r["n_segs"]:
+            return 0
+        rows = r["seg_h"] if r["tiled"] else min(r["seg_h"], r["height"] - (k // r["segs_across"]) * r["seg_h"])
+        return rows * r["seg_w"] * r["samples"] * r["sample_bytes"]
+
+
 class Engine:
     def __init__(self, device=None, scratch_bytes=None):
         if not torch.cuda.is_available():
@@ -330,6 +404,7 @@ class Engine:
         _lib.check(self.L.zmi_ctx_create(C.byref(self._ctx), self.device.index), "zmi_ctx_create")
         self.last_png_detail = None      # png_decode: the PE_* tensor of the last call
         self.last_png_written = None     # png_encode: the table zmi_png_headers_dev would list for the files of the last call
+        self.last_tiff_detail = None     # tiff_read: the TP_* / TE_* tensor of the last call
         if scratch_bytes:
             _lib.check(self.L.zmi_ctx_set_scratch_limit(self._ctx, int(scratch_bytes)), "zmi_ctx_set_scratch_limit")
 
@@ -1097,8 +1172,94 @@ class Engine:
         call(out)
         return out, out_off, out_len, status
 
+    # ---- TIFF files (include/zmi355.h) ----
+    def tiff_directory(self, data, cap=None):
+        """The IFD chain of the TIFF file `data` (a uint8 device tensor, or bytes / numpy, which are uploaded) -> TiffFile.  cap: pages
+        to make room for; the default, 64, is raised to the count the first call reports where the file has more.  One
+        synchronisation per call: the info is read; a file whose header or chain is broken raises."""
+        data = self._zip_data(data)
+        n = int(data.numel())
+        grow = cap is None
+        cap = 64 if cap is None else int(cap)
+        while True:
+            pages = torch.zeros((cap, TIFF_PAGE_BYTES), dtype=torch.uint8, device=self.device)
+            meta = torch.zeros(TIFF_INFO_BYTES // 8, dtype=torch.int64, device=self.device)
+            _lib.check(self.L.zmi_tiff_directory_dev(self._ctx, data.data_ptr() if n else None, n, pages.data_ptr() if cap else None, cap,
+                                                     meta.data_ptr(), _stream_ptr()), "zmi_tiff_directory_dev")
+            n_pages, n_listed, first, eb, sd = meta.tolist()
+            st = sd & 0xFFFFFFFF
+            info = {"n_pages": n_pages, "n_listed": n_listed, "first_ifd": first, "big_endian": eb & 0xFFFFFFFF, "bigtiff": (eb >> 32) & 0xFFFFFFFF,
+                    "status": st - (1 << 32) if st >= 1 << 31 else st, "detail": (sd >> 32) & 0xFFFFFFFF}
+            if info["status"] != 0:
+                raise RuntimeError("zmi_tiff_directory_dev: status %d (case %d, IFD %d)" % (info["status"], info["detail"] & 0xFF,
+                                                                                           info["detail"] >> 8))
+            if n_pages <= cap or not grow:
+                return TiffFile(data, pages[:n_listed], info)
+            cap = n_pages
+
+    def tiff_read(self, data, tf=None, page=0, segments=None, assemble=True, align=16, out=None):
+        """Strips or tiles of one page of a TIFF file, inflated (or copied, compression 1), the predictor undone, every sample
+        little-endian.  tf: the TiffFile of tiff_directory (None: made here from data; with it, data may be None); segments (a list or
+        an int32 device tensor) select, None: every segment of the page.  assemble=True -> (image, status): the page as one [H, W, C]
+        tensor in the page's dtype -- every selected segment at its place, cropped at the edges; what no selected segment covers is
+        zero in a tensor allocated here and untouched in `out` -- and status int32 [n_sel].  assemble=False -> (out, out_off int64
+        [n_sel + 1], out_len int32 [n_sel], status) as png_decode returns them: slot j is the whole segment, padding included, a
+        [rows, seg_w, C] tensor at out[out_off[j] : out_off[j] + out_len[j]].  status 0: every check passed; nothing is raised for a
+        segment or for a page the directory flagged (Z_DATA_ERROR / Z_VERSION_ERROR in every slot).  last_tiff_detail keeps the TP_* /
+        TE_* tensor (TE_SPARSE with status 0: a segment of byte count 0, all zeros).  out: a contiguous uint8 tensor."""
+        t = tf if tf is not None else self.tiff_directory(data)
+        if align < 1 or align > 4096 or align & (align - 1):
+            raise ValueError("align must be a power of two, 1 .. 4096")
+        if out is not None and (out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous()):
+            raise ValueError("tiff_read: out must be a contiguous uint8 tensor on %s" % (self.device,))
+        page = int(page)
+        r = t.record(page) if 0 <= page < t.n_pages else None
+        ok = r is not None and r["status"] == 0
+        sel = None
+        if segments is not None:
+            sel = segments if isinstance(segments, torch.Tensor) else torch.tensor(list(segments), dtype=torch.int32, device=self.device)
+            sel = sel.to(device=self.device, dtype=torch.int32).contiguous()
+        n_sel = int(sel.numel()) if sel is not None else (r["n_segs"] if ok else 1)
+        if not ok:
+            decoded, sizes = 0, [0] * n_sel
+        elif sel is None:
+            sizes = [t.segment_bytes(page, k) for k in range(n_sel)] if not r["tiled"] else [r["seg_bytes"]] * n_sel
+            decoded = sum(sizes)
+        elif isinstance(segments, torch.Tensor):
+            sizes, decoded = None, n_sel * r["seg_bytes"]                 # (a bound: the indices stay on the device)
+        else:
+            sizes = [t.segment_bytes(page, int(k)) for k in segments]
+            decoded = sum(sizes)
+        out_off = torch.zeros(n_sel + 1, dtype=torch.int64, device=self.device)
+        out_len = torch.zeros(n_sel, dtype=torch.int32, device=self.device)
+        status = torch.zeros(n_sel, dtype=torch.int32, device=self.device)
+        detail = torch.zeros(n_sel, dtype=torch.int32, device=self.device)
+        self.last_tiff_detail = detail
+
+        def call(buf):
+            _lib.check(self.L.zmi_tiff_read_dev(self._ctx, t.data.data_ptr() if t.data.numel() else None, int(t.data.numel()),
+                                                t.pages.data_ptr() if t.n_pages else None, t.n_pages, page,
+                                                sel.data_ptr() if sel is not None and n_sel else None, n_sel, int(decoded),
+                                                TIFF_ASSEMBLE if assemble else 0, int(align), buf.data_ptr() if buf.numel() else None,
+                                                int(buf.numel()), out_off.data_ptr(), out_len.data_ptr(), status.data_ptr(), detail.data_ptr(),
+                                                _stream_ptr()), "zmi_tiff_read_dev")
+
+        if assemble:
+            size = r["height"] * r["width"] * r["samples"] * r["sample_bytes"] if ok else 0
+            if out is None:
+                out = (torch.zeros if sel is not None else torch.empty)(size, dtype=torch.uint8, device=self.device)
+            call(out)
+            if not ok or int(out.numel()) < size:
+                return out[:0], status
+            return out[:size].view(t.dtype(page)).view(t.shape(page)), status
+        if out is None:
+            guess = n_sel * (-(-r["seg_bytes"] // align) * align) if sizes is None else sum(-(-s // align) * align for s in sizes)
+            out = torch.empty(guess if ok else 0, dtype=torch.uint8, device=self.device)
+        call(out)
+        return out, out_off, out_len, status
+
     # ---- writing PNG images (include/zmi355.h, DESIGN.md section 23) ----
-    _PNG_FILTERS = {"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
+    _PNG_FILTERS ={"none": 0, "sub": 1, "up": 2, "average": 3, "paeth": 4, "adaptive": 5}
     _PNG_COLOUR = {1: 0, 2: 4, 3: 2, 4: 6}
 
     def png_bound(self, n_images, scan_bytes, piece_bytes=1 << 20, align=1, level=6):

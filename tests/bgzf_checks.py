@@ -75,12 +75,10 @@ def make(kind, n, block_bytes=BLOCK_MAX, seed=1):
 
 
 def reproducible(level, strategy):
-    """May two calls be compared byte for byte?  Not at level 1: levels 1 and 3 run the match search with three hash-building waves
-    (zmi_deflate_impl: chain budgets of 2 and below), and on the MI355X which candidates a position sees then depends on the schedule
-    of the waves -- five zmi_deflate_batch_dev(raw) calls on the same text give different, equally valid streams there, and the same
-    bytes every time with ZMI_PRODUCERS=2 or 1 (the CPU emulator runs one schedule).  Level-1 files are judged
-    by the walker and gzip alone; levels 0, 6 and 9 and the strategies at level 6 are also compared exactly."""
-    return level not in (1, 3)
+    """May two calls be compared byte for byte?  At every level.  (Until a producer of the match search waited for BOTH chunks its tile
+    reads, levels 1 and 3 -- three hash-building waves -- gave different, equally valid streams from call to call on the MI355X, and
+    this returned False for them: DESIGN.md section 19, csrc/lz77.hip; tests/test_gpu_schedule.py holds the device to it.)"""
+    return True
 
 
 def kind_of_block(kind, i):

@@ -11,6 +11,41 @@ dim3 blockDim, gridDim;
 
 static const size_t kStack = 256 * 1024;
 
+// ---- schedule knob (hip_emu.h: ZMI_EMU_SCHED) ----
+static Sched g_sched;
+
+static void sched_bad(const char* e) {
+    fprintf(stderr, "[hip_emu] ZMI_EMU_SCHED=%s: expected hold:<wave>:<from_pass>:<passes> or seed:<s>[:<permille>]\n", e);
+    abort();
+}
+static Sched sched_from_env() {
+    Sched s;
+    const char* e = getenv("ZMI_EMU_SCHED");
+    if (!e || !*e) return s;
+    unsigned long a = 0, b = 0, c = 0;
+    char tail = 0;
+    if (sscanf(e, "hold:%lu:%lu:%lu%c", &a, &b, &c, &tail) == 3 && b >= 1) {
+        s.mode = Sched::HOLD; s.wave = (unsigned)a; s.from = b; s.passes = c;
+    } else if (sscanf(e, "seed:%lu:%lu%c", &a, &b, &tail) == 2 && b <= 1000) {
+        s.mode = Sched::SEED; s.seed = a; s.permille = (unsigned)b;
+    } else if (sscanf(e, "seed:%lu%c", &a, &tail) == 1) {
+        s.mode = Sched::SEED; s.seed = a; s.permille = 250;
+    } else {
+        sched_bad(e);
+    }
+    return s;
+}
+// is `wave` of block `bx` held back in this pass (the block's passes count from 1)?
+static bool sched_holds(const Sched& s, unsigned bx, unsigned long pass, unsigned wave) {
+    if (s.mode == Sched::HOLD) return wave == s.wave && pass >= s.from && pass - s.from < s.passes;
+    uint64_t x = s.seed * 0x9E3779B97F4A7C15ull + bx;   // splitmix64 finaliser over (seed, block, pass, wave)
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull + pass;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull + wave;
+    x = (x ^ (x >> 31)) * 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 29;
+    return x % 1000u < s.permille;
+}
+
 #ifdef EMU_FAST_SWITCH
 // save the callee-saved registers on the current stack, park its stack pointer in *save, continue on `load`
 extern "C" void emu_switch(void** save, void* load);
@@ -52,8 +87,8 @@ static void fiber_entry() {
     WaveSync& w = g.waves[f.tid >> 6];
     w.live--;
     // if the peers were only waiting for this lane, release them
-    if (w.live > 0 && w.arrived == w.live) { w.arrived = 0; w.gen++; }
-    if (g.live_threads > 0 && g.bar_arrived == g.live_threads) { g.bar_arrived = 0; g.bar_gen++; }
+    if (w.live > 0 && w.arrived == w.live) { w.arrived = 0; w.gen++; w.release_pass = g.pass_counter; }
+    if (g.live_threads > 0 && g.bar_arrived == g.live_threads) { g.bar_arrived = 0; g.bar_gen++; g.bar_release_pass = g.pass_counter; }
     EMU_TO_SCHED(f);
     abort();   // a finished fiber is never resumed
 }
@@ -72,6 +107,7 @@ static void run_block(dim3 block, unsigned bx, size_t shmem) {
     g.waves.assign((n + 63) / 64, WaveSync());
     g.bar_arrived = 0;
     g.bar_gen = 0;
+    g.bar_release_pass = -1;
     g.live_threads = (int)n;
     // exactly-sized heap block so ASan sees LDS overruns
     unsigned char* smem = shmem ? (unsigned char*)aligned_alloc(16, (shmem + 15) & ~(size_t)15) : nullptr;
@@ -106,18 +142,34 @@ static void run_block(dim3 block, unsigned bx, size_t shmem) {
     }
     blockIdx.x = bx; blockIdx.y = 0; blockIdx.z = 0;
     unsigned remaining = n;
-    unsigned long idle_passes = 0, spin_passes = 0;
+    unsigned long idle_passes = 0, spin_passes = 0, pass = 0;
+    const Sched sched = g_sched;
     while (remaining) {
         bool progressed = false;
         bool real_progress = false;
         g.pass_counter = g.pass_counter + 1;
+        ++pass;
+        unsigned asked_wave = ~0u, held_wave = ~0u;   // decided once per wave and pass, at the wave's first runnable lane
         for (unsigned t = 0; t < n; ++t) {
             Fiber& f = g.fibers[t];
             if (f.done) continue;
-            if (f.wait_var) {
-                if (*f.wait_var == f.wait_val) continue;  // still parked
-                f.wait_var = nullptr;
+            if (f.wait_var && *f.wait_var == f.wait_val) continue;  // still parked
+            if (sched.mode != Sched::NONE) {
+                // a perturbed schedule holds whole waves back, never single lanes: every lane of the wave whose wait is over
+                // stays where it is for this pass.  That is progress to the DEADLOCK detector (the lane could have run); a
+                // bounded hold is progress to the LIVELOCK detector as well, a seeded one leaves its count alone -- a block
+                // whose runnable lanes all only spin is still reported.
+                if ((t >> 6) != asked_wave) {
+                    asked_wave = t >> 6;
+                    if (sched_holds(sched, bx, pass, asked_wave)) held_wave = asked_wave;
+                }
+                if ((t >> 6) == held_wave) {
+                    progressed = true;
+                    if (sched.mode == Sched::HOLD) real_progress = true;
+                    continue;
+                }
             }
+            f.wait_var = nullptr;
             g.cur = t;
             threadIdx.x = t; threadIdx.y = 0; threadIdx.z = 0;
             g.last_yield_was_spin = false;
@@ -155,6 +207,7 @@ void launch(dim3 grid, dim3 block, size_t shmem, std::function<void()> body) {
     // globals, while the stream ABI runs device work of different host threads side by side
     static std::mutex one_launch;
     std::lock_guard<std::mutex> lk(one_launch);
+    g_sched = sched_from_env();   // read per launch: a test changes it between two calls of one process
     g.body = body;
     blockDim = block;
     gridDim = grid;

@@ -50,6 +50,7 @@ struct WaveSync {
     int arrived = 0;
     int gen = 0;
     int live = 0;
+    int release_pass = -1;   // scheduler pass in which the last rendezvous was released
     uint64_t vals[2][64];
     uint64_t pred[2];
 };
@@ -63,6 +64,7 @@ struct State {
     std::vector<WaveSync> waves;
     int bar_arrived = 0;
     int bar_gen = 0;
+    int bar_release_pass = -1;   // scheduler pass in which the last barrier was released
     int live_threads = 0;
     unsigned cur = 0;
     unsigned char* dyn_smem = nullptr;
@@ -70,11 +72,37 @@ struct State {
     volatile int pass_counter = 0;   // bumped once per scheduler pass (spin_yield parks for one pass)
     bool last_yield_was_spin = false;
 };
+// Schedule knob.  The scheduler runs ONE schedule: every pass resumes the runnable fibers in thread order.  What a kernel with
+// LDS flags and spin waits between its waves computes must not depend on that order, and the environment variable
+// ZMI_EMU_SCHED, read at every launch, perturbs it (unset: exactly the schedule above):
+//   hold:<wave>:<from_pass>:<passes>   that wave of every block sits out passes from_pass .. from_pass + passes - 1 (a block's
+//                                      passes count from 1)
+//   seed:<s>[:<permille>]              every wave sits out every pass with that probability (default 250), decided by a hash of
+//                                      (s, block, pass, wave)
+// A wave is always held as a whole -- every lane of it whose wait is over stays parked for the pass -- never lane by lane: the
+// lanes of a wave run in lockstep on the hardware.  A held lane counts as progress (the DEADLOCK report is for blocks in which
+// nothing CAN run, and it still comes under a perturbed schedule).  tests/test_emu_schedule.py is the user.
+struct Sched {
+    enum Mode { NONE, HOLD, SEED } mode = NONE;
+    unsigned wave = 0;
+    unsigned long from = 0, passes = 0;
+    uint64_t seed = 0;
+    unsigned permille = 0;
+};
 extern State g;
 extern uint3_emu threadIdx, blockIdx;
 extern dim3 blockDim, gridDim;
 
 void yield_wait(volatile int* var, int val);
+// After a release (barrier or rendezvous) every lane resumes in a LATER pass than the one the release happened in.  The scheduler
+// walks the threads in order, so the lanes above the releasing one would otherwise wake in the pass of the release itself and from
+// then on run a pass AHEAD of the lanes below them -- a wave out of step with itself, which the hardware does not have.  Kernels
+// lean on the lockstep: the lanes of one LDS store instruction to one address apply in lane order (lz77.hip's 16-bit hash heads),
+// and an out-of-step lane 63 lost its bucket to lane 62.  The plain schedule hid this (its last arriver is always the highest
+// thread, and only in the last wave of a block); a held wave 0 exposed it (tests/test_emu_schedule.py).
+inline void resume_in_a_later_pass(const int& release_pass) {
+    while (g.pass_counter == release_pass) yield_wait(&g.pass_counter, g.pass_counter);
+}
 // polling loops (LDS flags between waves) must give the other fibers a turn
 void launch(dim3 grid, dim3 block, size_t shmem, std::function<void()> body);
 
@@ -90,13 +118,12 @@ inline int wave_rendezvous(uint64_t v, bool p) {
     if (++w.arrived == w.live) {
         w.arrived = 0;
         w.gen = gen + 1;
-        // the releasing lane parks for one scheduler pass too, so that after every rendezvous the
-        // lanes resume in lane order (same-address LDS atomics of one wave instruction then apply
-        // in lane order, as on the hardware)
-        yield_wait(&w.gen, gen);
-    } else {
-        yield_wait(&w.gen, gen);
+        w.release_pass = g.pass_counter;
     }
+    // the releasing lane parks as well: after every rendezvous the lanes resume in one pass, in lane order (same-address LDS
+    // writes and atomics of one wave instruction then apply in lane order, as on the hardware)
+    yield_wait(&w.gen, gen);
+    resume_in_a_later_pass(w.release_pass);
     return gen & 1;
 }
 inline void spin_yield() {
@@ -164,9 +191,11 @@ inline void __syncthreads() {
     if (++emu::g.bar_arrived == emu::g.live_threads) {
         emu::g.bar_arrived = 0;
         emu::g.bar_gen = gen + 1;
+        emu::g.bar_release_pass = emu::g.pass_counter;
     } else {
         emu::yield_wait(&emu::g.bar_gen, gen);
     }
+    emu::resume_in_a_later_pass(emu::g.bar_release_pass);   // the last arriver too: it stays in step with its wave
 }
 
 // ---- wave-level primitives (64 lanes) ----

@@ -104,7 +104,7 @@ def test_arguments(target):
 
 
 def test_determinism(target):
-    assert K.determinism(target, levels=(0, 6)) == 6
+    assert K.determinism(target, levels=(0, 1, 6)) == 9
 
 
 # ---- the judges ----------------------------------------------------------------------------------------------------------------------------

@@ -78,7 +78,7 @@ def test_capacity(target):
 
 
 def test_determinism(target):
-    assert K.determinism(target, _setenv) == 12
+    assert K.determinism(target, _setenv, levels=(6, 1, 3)) == 18
 
 
 @pytest.mark.parametrize("native16", [True, False])

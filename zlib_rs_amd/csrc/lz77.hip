@@ -59,7 +59,8 @@
 // few bits per match) and the HIGHEST lane -- the most recent position -- becomes the new head: gfx950 applies the lanes
 // of one ds_write_b16 to the same address in lane order (tools/lds_winner.hip, profiles/r03_lds_winner.txt: contiguous and
 // strided groups of 2..64 lanes, always the highest lane's value stays), which is also what the CPU emulator of the tests
-// does, so the compressed bytes are defined by the algorithm, not by the schedule.
+// does, so the compressed bytes are defined by the algorithm, not by the schedule (held to that by
+// tests/test_emu_schedule.py -- the emulator under perturbed schedules -- and tests/test_gpu_schedule.py).
 #define LZ_HBITS 14
 #define LZ_HSIZE (1u << LZ_HBITS)
 #define LZ_MIRROR 32u
@@ -74,10 +75,11 @@
 struct LzCtl {
     uint32_t ready;  // positions < ready are searchable (chain built, look-ahead bytes loaded)
     uint32_t next;   // next unclaimed position
-    uint32_t atok;   // two producers: the tile whose hash-head atomics may be issued next (keeps them in position order)
+    uint32_t atok;   // two to four producers: the tile whose hash-head inserts may be issued next (keeps them in position order)
     uint32_t pad;
     uint32_t wmin[LZ_NW];  // per wave: lower bound of its oldest in-flight position
-    uint32_t stored[4];    // per producer wave: input bytes [.., stored) of its last chunk are in the ring
+    uint32_t stored[4];    // per producer wave: input bytes [.., stored) of its last chunk are in the ring (only grows).  A tile's hashes
+                           // read the chunks of the two rounds before it: its producer waits for both (one is its own with two producers)
 };
 
 #ifdef ZMI_EMU
@@ -369,8 +371,15 @@ __global__ void __launch_bounds__(1024) zmi_lz77_kernel_t(const uint8_t* __restr
             zmi_wave_sync();
             if (P > 1u) {
                 if (lane == 0) lz_st_rel(&ctl->stored[wave], E);
-                // hashing tile k reads bytes up to (k+1)*T + 7: the chunk the other wave stored in its round k-1
+                // hashing tile k reads bytes [k*T, (k+1)*T + 8): the end of the chunk of round k-2 (bytes up to k*T + 16) and the
+                // chunk of round k-1.  With two producers round k-2 was this wave's own; with three or four it is a third wave's,
+                // which nothing else orders before this point -- the wave of round k-1 publishes its own chunk BEFORE it waits for
+                // round k-2 -- and the first 16 positions of the tile were hashed from whatever the ring held there (stale bytes
+                // of the lap before, in the first lap uninitialised LDS): valid streams, but other links, other matches and other
+                // bytes from call to call.  Both waits are on counters that only grow, and what they wait for (a chunk store
+                // behind the ring throttle of an EARLIER round) does not depend on anything this wave does later.
                 if (k > 0u) while (lz_ld_acq(&ctl->stored[(wave + P - 1u) % P]) < (k + 1u) * LZ_T + 16u) lz_pause();
+                if (P > 2u && k > 1u) while (lz_ld_acq(&ctl->stored[(wave + P - 2u) % P]) < k * LZ_T + 16u) lz_pause();
             }
             lz_build_tile<H6>(win, prev, head, head4, c4, k, n, prm.max_dist, ctl, P);
             zmi_wave_sync();

@@ -1039,6 +1039,77 @@ int zmi_tiff_read_dev(zmi_ctx* ctx, const void* d_in, uint64_t in_len, const zmi
                       uint64_t out_cap, uint64_t* d_out_off /* n_sel + 1 */, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail,
                       void* stream);
 
+/* ---- writing TIFF files with Deflate compression: the forward predictor, deflate in pieces, the IFD -------------------------------------
+ * The inverse of the two calls above: one page in device memory becomes one complete little-endian (II) TIFF file in device memory,
+ * one asynchronous call on `stream` that never synchronises with the host.  The geometry is the caller's (*w is host memory, read during
+ * the call), so n_segs, the decoded size of every segment and the length of the metadata follow on the host and every table is sized
+ * exactly; the geometry words are the reader's: seg_w, seg_h, segs_across, segs_down, n_segs, seg_bytes.  Not written: big-endian files,
+ * several pages, compression 1 and LZW, PlanarConfiguration 2, depths below 8, sparse segments, ancillary tags, SubIFDs.
+ *
+ *   Arguments   ZMI_E_ARG as the return value, with a zmi_last_error text and nothing launched: a dimension of 0; bits not 8 / 16 / 32 / 64;
+ *               samples 0 or above 8; extra_samples >= samples; predictor outside 1 .. 3; sample_format outside 1 .. 3; predictor 3
+ *               without sample_format 3 or with bits < 16; exactly one of tile_w / tile_h being 0; a tile size that is not a multiple
+ *               of 16 (TIFF 6.0 section 15); a segment whose decoded size passes ZMI_PNG_SCAN_MAX; piece_bytes outside 1 .. 2^30; level
+ *               outside -1 .. 9; strategy outside 0 .. 4; out_align not a power of two in 1 .. 4096; an unknown flag; more than
+ *               2^31 - 1 pieces (n_segs + the page's decoded bytes / piece_bytes).
+ *   Input       default (dense): segment k is the bytes d_in[d_in_off[k] ..) -- exactly the region zmi_tiff_read_dev writes in dense
+ *               mode: [rows, seg_w, C] little-endian samples, the last strip only the rows left, edge tiles with their padding as
+ *               given.  flags & ZMI_TIFF_ASSEMBLE: d_in is the [height, width, C] image, d_in_off is not read; the predict kernel cuts
+ *               the segments itself and the padding samples of edge tiles are 0.  d_in may stand at any alignment.
+ *   File        every byte is fixed:
+ *                 classic   49 49 2A 00 08 00 00 00 | the IFD at 8: u16 count, entries of 12 bytes, u32 0
+ *                 BigTIFF   49 49 2B 00 08 00 00 00 | u64 16 | the IFD at 16: u64 count, entries of 20 bytes, u64 0
+ *               The entries stand ascending by tag ("seg" = LONG, in BigTIFF LONG8): 256 LONG width; 257 LONG height; 258 SHORT x
+ *               samples; 259 SHORT 8; 262 SHORT photometric; strips: 273 seg x n_segs; 277 SHORT samples; strips: 278 LONG seg_h,
+ *               279 seg x n_segs; 284 SHORT 1; 317 SHORT predictor (always); tiles: 322 LONG seg_w, 323 LONG seg_h, 324 and 325 seg x
+ *               n_segs; 338 SHORT x extra_samples, each extra_kind, only where extra_samples > 0; 339 SHORT x samples.  Values that fit
+ *               the 4-byte value field (BigTIFF: 8) stand in it, left-justified and zero-filled -- the two arrays of a one-segment
+ *               page too --, the others follow the IFD in tag order, each at the next even position.  Segment 0 starts at the next
+ *               multiple of out_align, every further segment at the next multiple behind its predecessor; every gap byte is 0; the
+ *               file ends with the last byte of the last segment.
+ *   Segment     one zlib stream: the two header bytes zmi_deflate_stream_dev writes for ZMI_WRAP_ZLIB at that level and strategy; the
+ *               predicted bytes cut into pieces of piece_bytes, each compressed exactly as zmi_deflate_pieces_dev(
+ *               ZMI_STREAM_INDEPENDENT) does with max_len = piece_bytes -- every piece but the last ends with the flush marker, the
+ *               last ends the stream --; the big-endian Adler-32 of the predicted bytes: the IDAT payload of zmi_png_encode_dev.
+ *               Level 0 is stored blocks through the same path.  A file's bytes are a function of the pixels and *w alone -- not of
+ *               the alignment of d_in, the scratch limit, the launch grouping or the wave schedule.
+ *   Predictor   the inverse of what the reader undoes.  1 copies; 2: d[i] = x[i] - x[i - samples] mod 2^bits along a row, the first
+ *               pixel as it is, integer arithmetic on the bits whatever sample_format says; 3 (Technical Note 3): byte b of sample k,
+ *               b = 0 the most significant, goes to p[b * N + k] with N = seg_w * samples, then q[j] = p[j] - p[j - samples] mod 256 over
+ *               the row's bytes.
+ *   Words       *d_file_len = the length the file needs, whether or not it fitted; d_seg_len[k] (the table may be NULL) = the byte count
+ *               of segment k; d_status[k] = the first encoder status of its pieces, or 0; *d_file_status = the first of these that holds:
+ *               ZMI_E_ARG where a classic file would pass 2^32 - 1 bytes, Z_BUF_ERROR where the file does not fit out_cap, the first
+ *               segment status that is not 0, 0.  Nothing at or behind d_out + out_cap is written; with Z_BUF_ERROR nothing is promised
+ *               about the bytes in front of it.  d_written (NULL or one record) = what zmi_tiff_directory_dev would list for page 0 of
+ *               the written file, every field; all zeros with the file status where that is not 0.
+ *   zmi_tiff_bound   room that always suffices (not tight); 0 where *w is not valid.
+ *   Plan        zmi_png_encode_dev's with segments in place of images: one piece table of exactly the page's pieces (at most n_segs +
+ *               decoded bytes / piece_bytes), launch groups within the scratch limit, the running offset kept in a device word; the hole
+ *               in front of a segment's first piece is the 2 header bytes (and the pad in front of them), the one behind its last the
+ *               4 of the Adler-32, the metadata is the hole in front of segment 0.  A piece's slot and match scratch are sized for
+ *               min(seg_bytes, piece_bytes), the longest piece the page has; the bytes are those of pieces of piece_bytes all the same.
+ *   Scratch of the context: the predicted segments, every one at a multiple of 16, NOT capped by the scratch limit (the whole page is
+ *   predicted before the first group is encoded); 8 bytes per segment, 40 bytes and 1 bit per piece, 12 bytes per slot of a group; one
+ *   group's slots as in zmi_zip_write_dev.  Scratch that cannot be reserved is ZMI_E_NOMEM.
+ *   Event timing, as zmi_png_encode_dev: 3 = the predict kernel (the decoder's slot is idle on every write path), 0 = Adler-32 of the
+ *   pieces and the fold per segment, 1 / 5 / 2 = match search, parse, encode, 7 = the piece table, places and pack, 4 = the file's fixed
+ *   bytes, the segments' frames and array entries, the words. */
+#define ZMI_TIFF_BIGTIFF 2u          /* flags; ZMI_TIFF_ASSEMBLE (1u) keeps its meaning: the input is the page as one image */
+typedef struct zmi_tiff_write {     /* host memory, read during the call */
+    uint32_t width, height;
+    uint32_t tile_w, tile_h;          /* both 0: strips */
+    uint32_t rows_per_strip;          /* strips only; 0 or >= height: one strip */
+    uint16_t bits, samples, sample_format, predictor, photometric, extra_samples, extra_kind;
+    uint32_t flags, piece_bytes, out_align;
+    int32_t  level, strategy;
+} zmi_tiff_write;
+uint32_t zmi_tiff_predict_tile(void);   /* bytes of a row one trip of the predict kernel covers per wave (for tests that place row lengths around it) */
+uint64_t zmi_tiff_bound(const zmi_tiff_write* w);      /* room that always suffices; 0 where w is not valid */
+int zmi_tiff_write_dev(zmi_ctx* ctx, const zmi_tiff_write* w, const void* d_in, const uint64_t* d_in_off /* n_segs, NULL with ASSEMBLE */,
+                       void* d_out, uint64_t out_cap, uint64_t* d_file_len, uint32_t* d_seg_len /* NULL or n_segs */,
+                       int32_t* d_status /* n_segs */, int32_t* d_file_status, zmi_tiff_page* d_written /* NULL or 1 */, void* stream);
+
 /* ---- host-buffer convenience wrappers: copy in, run the batch on the GPU, copy back ---- */
 int zmi_deflate_batch(zmi_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_shards,
                       int level, int strategy, int wrap, uint8_t* out, uint64_t out_stride, uint32_t* out_len,

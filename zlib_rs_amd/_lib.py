@@ -8,6 +8,14 @@ from ._build import LIB
 _lib = None
 
 
+class TiffWrite(C.Structure):
+    """zmi_tiff_write (include/zmi355.h): host memory, read during zmi_tiff_bound / zmi_tiff_write_dev"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("tile_w", C.c_uint32), ("tile_h", C.c_uint32), ("rows_per_strip", C.c_uint32),
+                ("bits", C.c_uint16), ("samples", C.c_uint16), ("sample_format", C.c_uint16), ("predictor", C.c_uint16),
+                ("photometric", C.c_uint16), ("extra_samples", C.c_uint16), ("extra_kind", C.c_uint16), ("flags", C.c_uint32),
+                ("piece_bytes", C.c_uint32), ("out_align", C.c_uint32), ("level", C.c_int32), ("strategy", C.c_int32)]
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -96,6 +104,12 @@ def lib():
     L.zmi_tiff_row_tile.argtypes = []
     L.zmi_tiff_directory_dev.argtypes = [vp, vp, u64, vp, u32, vp, vp]
     L.zmi_tiff_read_dev.argtypes = [vp, vp, u64, vp, u32, u32, vp, u32, u64, u32, u32, vp, u64, vp, vp, vp, vp, vp]
+    # writing TIFF files: the forward predictor, deflate in pieces, the IFD (csrc/tiff_write_kernels.h, zmi_api.hip); w: a TiffWrite
+    L.zmi_tiff_predict_tile.restype = u32
+    L.zmi_tiff_predict_tile.argtypes = []
+    L.zmi_tiff_bound.restype = u64
+    L.zmi_tiff_bound.argtypes = [C.POINTER(TiffWrite)]
+    L.zmi_tiff_write_dev.argtypes = [vp, C.POINTER(TiffWrite), vp, vp, vp, u64, vp, vp, vp, vp, vp, vp]
     # the multi-GPU stitch (csrc/exchange.hip); RCCL itself is loaded by the library on first use
     L.zmi_comm_unique_id.argtypes = [vp]
     L.zmi_comm_create.argtypes = [C.POINTER(vp), vp, i32, i32, vp]

@@ -1194,3 +1194,6 @@ extern "C" int zmi_launch_zip_close(uint8_t* d_out, uint64_t out_cap, const uint
 
 // ---- reading TIFF files (zmi_tiff_directory_dev / zmi_tiff_read_dev) ---------------------------------------------------------------------
 #include "tiff_kernels.h"
+
+// ---- writing TIFF files (zmi_tiff_write_dev) ------------------------------------------------------------------------------------------------
+#include "tiff_write_kernels.h"

@@ -107,6 +107,7 @@ struct zmi_ctx {
     zmi_buf zip_dir, zip_sel;           // zmi_zip_directory_dev: four words, the chain positions, four words per segment; zmi_zip_inflate_dev: the slots' tables
     zmi_buf tiff_dir;                   // zmi_tiff_directory_dev: the positions of the listed IFDs
     zmi_buf tiff;                       // zmi_tiff_read_dev: the slots' tables | the still-predicted segments
+    zmi_buf tiff_w;                     // zmi_tiff_write_dev: the piece table | the predicted segments
     zmi_buf png;                        // zmi_png_decode_dev: the slots' tables | the gathered IDAT streams | the filtered scanlines
     zmi_buf dict;                       // the shared-dictionary batch calls: layout words and DICTID | deflate image | inflate image (zmi_sd_*)
 };
@@ -171,6 +172,7 @@ extern "C" int zmi_ctx_destroy(zmi_ctx* c) {
     if (c->png.p) (void)hipFree(c->png.p);
     if (c->tiff.p) (void)hipFree(c->tiff.p);
     if (c->tiff_dir.p) (void)hipFree(c->tiff_dir.p);
+    if (c->tiff_w.p) (void)hipFree(c->tiff_w.p);
     if (c->mm_scan.p) (void)hipFree(c->mm_scan.p);
     if (c->mm_meta.p) (void)hipFree(c->mm_meta.p);
     for (int k = 0; k < 2; ++k) if (c->st_pin[k].p) (void)hipHostFree(c->st_pin[k].p);
@@ -1830,6 +1832,251 @@ extern "C" int zmi_png_encode_dev(zmi_ctx* c, const void* d_in, const uint64_t* 
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
         zmi_launch_png_wfinish(d_images, d_in_len, n, d_neff, d_first, d_pos, d_olen, d_st, d_iadler, d_icrc, (uint32_t)level, (uint32_t)strategy,
                                (uint8_t*)d_out, out_cap, d_out_off, d_out_len, d_status, d_written, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+// ---- writing TIFF files (include/zmi355.h; the kernels: tiff_write_kernels.h, checksum.hip) -------------------------
+// zmi_png_encode_dev's plan with the predicted segments in place of the filtered scanlines.  The geometry is host data, so the plan,
+// the metadata's bytes and the record of the written page are made here (zmi_tiff_wplan) and handed to the kernels by value.
+static void zmi_tw_le(uint8_t* p, uint64_t v, uint32_t nb) { for (uint32_t i = 0; i < nb; ++i) p[i] = (uint8_t)(v >> (8u * i)); }
+// NULL, or what is wrong with *w
+static const char* zmi_tiff_wplan(const zmi_tiff_write* w, int* level_out, zmi_tw_plan* g, zmi_tw_meta* m) {
+    if (!w) return "zmi_tiff_write: null";
+    if (w->width == 0u || w->height == 0u) return "zmi_tiff_write: a dimension of 0";
+    if (w->bits != 8u && w->bits != 16u && w->bits != 32u && w->bits != 64u) return "zmi_tiff_write: bits must be 8, 16, 32 or 64";
+    if (w->samples == 0u || w->samples > 8u) return "zmi_tiff_write: samples must be 1 .. 8";
+    if (w->extra_samples >= w->samples) return "zmi_tiff_write: extra_samples must be below samples";
+    if (w->predictor < 1u || w->predictor > 3u) return "zmi_tiff_write: predictor must be 1 .. 3";
+    if (w->sample_format < 1u || w->sample_format > 3u) return "zmi_tiff_write: sample_format must be 1 .. 3";
+    if (w->predictor == 3u && (w->sample_format != 3u || w->bits < 16u)) return "zmi_tiff_write: predictor 3 needs sample_format 3 and bits >= 16";
+    if ((w->tile_w == 0u) != (w->tile_h == 0u)) return "zmi_tiff_write: tile_w and tile_h must both be 0 or both be set";
+    if (w->tile_w % 16u != 0u || w->tile_h % 16u != 0u) return "zmi_tiff_write: a tile size must be a multiple of 16";
+    const bool tiled = w->tile_w != 0u;
+    const uint32_t sb = w->bits / 8u, pb = sb * w->samples;
+    const uint32_t seg_w = tiled ? w->tile_w : w->width;
+    const uint32_t seg_h = tiled ? w->tile_h : (w->rows_per_strip == 0u || w->rows_per_strip >= w->height ? w->height : w->rows_per_strip);
+    const uint64_t rb = (uint64_t)seg_w * pb, seg_bytes = rb * seg_h;
+    if (seg_bytes > ZMI_PNG_SCAN_MAX) return "zmi_tiff_write: a segment's decoded size passes ZMI_PNG_SCAN_MAX";
+    if (w->piece_bytes == 0u || w->piece_bytes > (1u << 30)) return "zmi_tiff_write: piece_bytes must be 1 .. 2^30";
+    int level = w->level;
+    if (level == -1) level = 6;
+    if (level < 0 || level > 9) return "zmi_tiff_write: level must be -1 .. 9";
+    if (w->strategy < 0 || w->strategy > 4) return "zmi_tiff_write: strategy must be 0 .. 4";
+    if (w->out_align == 0u || w->out_align > 4096u || (w->out_align & (w->out_align - 1u)) != 0u)
+        return "zmi_tiff_write: out_align must be a power of two, 1 .. 4096";
+    if (w->flags & ~(ZMI_TIFF_ASSEMBLE | ZMI_TIFF_BIGTIFF)) return "zmi_tiff_write: unknown flag";
+    const uint64_t across = ((uint64_t)w->width + seg_w - 1u) / seg_w, down = ((uint64_t)w->height + seg_h - 1u) / seg_h;
+    const uint64_t n_segs = across * down;
+    const uint32_t last_rows = tiled ? seg_h : (uint32_t)(w->height - (down - 1u) * seg_h);
+    const uint64_t last_bytes = rb * last_rows;
+    if (n_segs > 0x7FFFFFFFull) return "zmi_tiff_write: more than 2^31 - 1 pieces";
+    const uint64_t scan = (n_segs - 1u) * seg_bytes + last_bytes;
+    if (n_segs + scan / w->piece_bytes > 0x7FFFFFFFull) return "zmi_tiff_write: more than 2^31 - 1 pieces";
+    const bool big = (w->flags & ZMI_TIFF_BIGTIFF) != 0u;
+    *level_out = level;
+    memset(g, 0, sizeof *g);
+    memset(m, 0, sizeof *m);
+    g->width = w->width; g->height = w->height; g->seg_w = seg_w; g->seg_h = seg_h; g->across = (uint32_t)across; g->n_segs = (uint32_t)n_segs;
+    g->sb = sb; g->spp = w->samples; g->pb = pb; g->rb = (uint32_t)rb;
+    g->pred = w->predictor; g->assemble = (w->flags & ZMI_TIFF_ASSEMBLE) ? 1u : 0u; g->big = big ? 1u : 0u;
+    g->seg_bytes = (uint32_t)seg_bytes; g->last_bytes = (uint32_t)last_bytes;
+    g->ss = (uint32_t)((seg_bytes + 15u) & ~15ull);
+    g->piece_bytes = w->piece_bytes;
+    g->ppf = (uint32_t)((seg_bytes + w->piece_bytes - 1u) / w->piece_bytes);
+    g->ppl = (uint32_t)((last_bytes + w->piece_bytes - 1u) / w->piece_bytes);
+    g->np = (uint32_t)((n_segs - 1u) * g->ppf + g->ppl);
+    // a band of rows, the predict kernel's work item: about 8 KiB of a segment, one row at least, 8 at most
+    g->band_rows = rb >= 8192u ? 1u : (8192u / (uint32_t)rb > 8u ? 8u : 8192u / (uint32_t)rb);
+    g->bands = (seg_h + g->band_rows - 1u) / g->band_rows;
+
+    // the entries, ascending by tag: {tag, type (3 SHORT, 4 LONG, 16 LONG8), count, the value repeated `count` times}; the two arrays are
+    // written by the segments' kernel where `arr` says so
+    struct ent { uint32_t tag, type; uint64_t count, value; bool arr; };
+    const uint32_t seg_t = big ? 16u : 4u;
+    ent e[14];
+    uint32_t ne = 0;
+    e[ne++] = {256u, 4u, 1u, w->width, false};
+    e[ne++] = {257u, 4u, 1u, w->height, false};
+    e[ne++] = {258u, 3u, w->samples, w->bits, false};
+    e[ne++] = {259u, 3u, 1u, 8u, false};
+    e[ne++] = {262u, 3u, 1u, w->photometric, false};
+    if (!tiled) e[ne++] = {273u, seg_t, n_segs, 0u, true};
+    e[ne++] = {277u, 3u, 1u, w->samples, false};
+    if (!tiled) {
+        e[ne++] = {278u, 4u, 1u, seg_h, false};
+        e[ne++] = {279u, seg_t, n_segs, 0u, true};
+    }
+    e[ne++] = {284u, 3u, 1u, 1u, false};
+    e[ne++] = {317u, 3u, 1u, w->predictor, false};
+    if (tiled) {
+        e[ne++] = {322u, 4u, 1u, seg_w, false};
+        e[ne++] = {323u, 4u, 1u, seg_h, false};
+        e[ne++] = {324u, seg_t, n_segs, 0u, true};
+        e[ne++] = {325u, seg_t, n_segs, 0u, true};
+    }
+    if (w->extra_samples) e[ne++] = {338u, 3u, w->extra_samples, w->extra_kind, false};
+    e[ne++] = {339u, 3u, w->samples, w->sample_format, false};
+    const uint32_t os = big ? 8u : 4u, es = big ? 20u : 12u, cs = big ? 8u : 2u, ifd = big ? 16u : 8u;
+    uint8_t* b = m->b;
+    b[0] = b[1] = 0x49u; b[2] = big ? 0x2Bu : 0x2Au; b[4] = 8u;
+    if (big) zmi_tw_le(b + 8, 16u, 8u);
+    zmi_tw_le(b + ifd, ne, cs);
+    uint64_t at = ifd + cs + (uint64_t)ne * es + os;     // where the next out-of-line value goes (always even: every value is 2, 4 or 8 bytes)
+    m->a_len = (uint32_t)at;
+    bool behind = false;                                 // behind the two arrays: part b of the metadata
+    uint64_t arr_pos[2] = {0u, 0u};
+    uint32_t n_arr = 0;
+    for (uint32_t q = 0; q < ne; ++q) {
+        uint8_t* f = b + ifd + cs + (size_t)q * es;
+        const uint32_t ts = e[q].type == 3u ? 2u : (e[q].type == 4u ? 4u : 8u);
+        const uint64_t bytes = e[q].count * ts;
+        zmi_tw_le(f, e[q].tag, 2u);
+        zmi_tw_le(f + 2, e[q].type, 2u);
+        zmi_tw_le(f + 4, e[q].count, os);
+        uint64_t vpos = ifd + cs + (uint64_t)q * es + 4u + os;   // inline
+        if (bytes > os) {
+            vpos = at;
+            zmi_tw_le(f + 4 + os, at, os);
+            at += bytes;
+        }
+        if (e[q].arr) {
+            arr_pos[n_arr++] = vpos;
+            if (bytes > os) { behind = true; m->b_pos = at; }
+            continue;
+        }
+        uint8_t* v;
+        if (bytes <= os) v = f + 4 + os;
+        else if (!behind) { v = b + vpos; m->a_len = (uint32_t)at; }
+        else { v = b + m->a_len + (vpos - m->b_pos); m->b_len = (uint32_t)(at - m->b_pos); }
+        for (uint64_t i = 0; i < e[q].count; ++i) zmi_tw_le(v + i * ts, e[q].value, ts);
+    }
+    g->off_pos = arr_pos[0]; g->cnt_pos = arr_pos[1];
+    g->meta_end = at;
+    g->seg0 = (at + w->out_align - 1u) & ~(uint64_t)(w->out_align - 1u);
+
+    zmi_tiff_page r;
+    memset(&r, 0, sizeof r);
+    r.offsets_pos = arr_pos[0]; r.counts_pos = arr_pos[1];
+    r.width = w->width; r.height = w->height; r.seg_w = seg_w; r.seg_h = seg_h;
+    r.segs_across = (uint32_t)across; r.segs_down = (uint32_t)down; r.n_segs = (uint32_t)n_segs; r.seg_bytes = (uint32_t)seg_bytes;
+    r.bits = w->bits; r.samples = w->samples; r.sample_format = w->sample_format; r.predictor = w->predictor; r.compression = 8u;
+    r.photometric = w->photometric; r.extra_samples = w->extra_samples;
+    r.sample_bytes = (uint8_t)sb; r.big_endian = 0u; r.bigtiff = big ? 1u : 0u; r.tiled = tiled ? 1u : 0u;
+    r.offsets_type = r.counts_type = (uint8_t)seg_t;
+    static_assert(sizeof r == sizeof m->rec, "zmi_tiff_page is 72 bytes");
+    memcpy(m->rec, &r, sizeof r);
+    return nullptr;
+}
+
+extern "C" uint64_t zmi_tiff_bound(const zmi_tiff_write* w) {
+    zmi_tw_plan g;
+    zmi_tw_meta m;
+    int level;
+    if (zmi_tiff_wplan(w, &level, &g, &m)) return 0;
+    // the metadata and its pad; the zlib frame and the pad per segment; per piece the slot of zmi_deflate_pieces_stride and the block
+    // headers of its regions, as zmi_png_bound
+    const uint64_t scan = (uint64_t)(g.n_segs - 1u) * g.seg_bytes + g.last_bytes;
+    return g.seg0 + (uint64_t)g.n_segs * (6u + (uint64_t)(w->out_align - 1u)) + scan + (scan >> 3) + (uint64_t)g.np * 160u;
+}
+
+extern "C" int zmi_tiff_write_dev(zmi_ctx* c, const zmi_tiff_write* w, const void* d_in, const uint64_t* d_in_off, void* d_out, uint64_t out_cap,
+                                  uint64_t* d_file_len, uint32_t* d_seg_len, int32_t* d_status, int32_t* d_file_status, zmi_tiff_page* d_written,
+                                  void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    zmi_tw_plan g;
+    zmi_tw_meta meta;
+    int level = 0;
+    if (const char* what = zmi_tiff_wplan(w, &level, &g, &meta)) return zmi_fail(ZMI_E_ARG, what);
+    if (!d_in || (!g.assemble && !d_in_off) || (out_cap && !d_out) || !d_file_len || !d_status || !d_file_status)
+        return zmi_fail(ZMI_E_ARG, "null argument");
+    const int strategy = w->strategy;
+    const uint32_t piece_bytes = w->piece_bytes, n = g.n_segs, np = g.np;
+    if ((uint64_t)n * g.ss > (1ull << 44)) return zmi_fail(ZMI_E_NOMEM, "the page's decoded bytes size the scratch");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+
+    // launch groups and slots: as zmi_png_encode_dev, but the host knows the longest piece there is -- a full segment, or piece_bytes
+    // where that is less -- so slots and match scratch follow the segments (a 192 KiB tile under piece_bytes of 1 MiB takes a fifth of
+    // what a 1 MiB piece would) while geom_len = piece_bytes keeps the bytes those of pieces of piece_bytes
+    const uint32_t max_len = g.seg_bytes < piece_bytes ? g.seg_bytes : piece_bytes;
+    const uint32_t regions = zmi_enc_regions(piece_bytes, zmi_deflate_pieces_stride(piece_bytes), 65536u, kLevels[level].tok, false);
+    const uint64_t hold = (uint64_t)regions * ((zmi_enc_region_worst(max_len, regions, kLevels[level].tok, false) + 15u) & ~15ull);
+    uint64_t stride = zmi_deflate_pieces_stride(max_len);
+    if (stride < hold) stride = hold;
+    const uint64_t match_per = ((((uint64_t)max_len + 63u) & ~63ull) ? (((uint64_t)max_len + 63u) & ~63ull) : 64u) * 4u;
+    uint64_t group = c->scratch_limit / (stride + match_per + match_per / 16u);
+    if (const char* gv = zmi_tune("ZMI_STREAM_GROUP")) if (atoll(gv) > 0) group = (uint64_t)atoll(gv);
+    if (group == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one piece");
+    if (group > np) group = np;
+    int rc = zmi_reserve(c->sd_slots, (size_t)(group * stride));
+    if (rc) return rc;
+    const uint32_t wpg = (uint32_t)((group + 31u) / 32u);                       // bitmap words per group
+    const uint64_t n_groups = (np + group - 1u) / group;
+    const size_t bm_words = (size_t)(n_groups * wpg);
+
+    // tables: u64 first piece [n + 1] | piece offsets in the scratch [np] | piece places [np + 1] | slot offsets [group] | four words
+    // (the segments that are live: all; the first segment with a status) | u32 Adler-32 per segment [n] | piece lengths, holes, encoder
+    // sizes, statuses, Adler-32 [np each] | a table the slot layout fills [group] | the bitmap; then the predicted segments, every one
+    // at a multiple of 16, 64 bytes clear of either end
+    const size_t tab_bytes = (((size_t)n + 1u) * 8u + (size_t)np * 16u + 8u + (size_t)group * 8u + 16u + (size_t)n * 4u + (size_t)np * 20u +
+                              (size_t)group * 4u + bm_words * 4u + 16u + 255u) & ~(size_t)255u;
+    rc = zmi_reserve(c->tiff_w, tab_bytes + 64u + (size_t)n * g.ss + 64u);
+    if (rc) return rc;
+    uint64_t* d_first = (uint64_t*)c->tiff_w.p;
+    uint64_t* d_poff = d_first + n + 1u;
+    uint64_t* d_pos = d_poff + np;
+    uint64_t* d_slot_off = d_pos + np + 1u;
+    uint32_t* d_neff = (uint32_t*)(d_slot_off + group);
+    uint32_t* d_bad = d_neff + 1u;
+    uint32_t* d_sadler = d_neff + 4u;
+    uint32_t* d_plen = d_sadler + n;
+    uint32_t* d_head = d_plen + np;
+    uint32_t* d_olen = d_head + np;
+    int32_t* d_st = (int32_t*)(d_olen + np);
+    uint32_t* d_padler = (uint32_t*)(d_st + np);
+    uint32_t* d_slot_len = d_padler + np;
+    uint32_t* d_ends = d_slot_len + group;
+    uint8_t* d_scan = (uint8_t*)c->tiff_w.p + tab_bytes + 64u;
+
+    ZMI_HIP(hipMemsetAsync(d_bad, 0xFF, 4, stream));
+    ZMI_HIP(hipMemsetAsync(d_ends, 0, bm_words * 4u, stream));
+    {
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_tiff_wpieces(g, (uint32_t)group, wpg, d_poff, d_plen, d_head, d_ends, d_first, d_neff, d_pos, stream);
+        zmi_launch_piece_layout(group * stride, (uint32_t)stride, (uint32_t)group, d_slot_off, d_slot_len, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_INFLATE, stream);
+        zmi_launch_tiff_predict(g, (const uint8_t*)d_in, d_in_off, d_scan, stream);
+    }
+    rc = zmi_piece_checks(c, d_scan, d_poff, d_plen, np, ZMI_WRAP_ZLIB, d_padler, stream);
+    if (rc) return rc;
+    for (uint64_t first = 0; first < np; first += group) {
+        const uint32_t cnt = (uint32_t)(np - first < group ? np - first : group);
+        const uint32_t* d_gends = d_ends + (first / group) * wpg;
+        rc = zmi_deflate_impl(c, {.d_in = d_scan, .d_in_off = d_poff + first, .d_in_len = d_plen + first, .n = cnt, .max_len = max_len,
+                                  .level = level, .strategy = strategy, .wrap = ZMI_WRAP_RAW, .chain_mode = 2u, .d_out = c->sd_slots.p,
+                                  .out_stride = stride, .d_out_len = d_olen + first, .d_status = d_st + first, .stream = stream_, .carry = 0,
+                                  .ends = d_gends, .geom_len = piece_bytes});
+        if (rc) return rc;
+        // the group's pieces go behind the previous group's, the running offset never leaves the device
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_tiff_place(d_head + first, d_olen + first, d_gends, cnt, w->out_align, d_pos + first, stream);
+        zmi_launch_zip_pack(nullptr, d_poff + first, d_head + first, (const uint8_t*)c->sd_slots.p, stride, d_olen + first, cnt,
+                            stride > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)stride, (uint8_t*)d_out, d_pos + first, out_cap, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_CHECKSUM, stream);
+        zmi_launch_combine_segments_adler(d_padler, d_plen, d_first, n, d_neff, d_sadler, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_tiff_wmeta(meta, (uint8_t*)d_out, out_cap, stream);
+        zmi_launch_tiff_wsegs(g, d_pos, d_olen, d_st, d_sadler, (uint32_t)level, (uint32_t)strategy, (uint8_t*)d_out, out_cap, d_seg_len, d_status,
+                              d_bad, stream);
+        zmi_launch_tiff_wclose(g, meta, d_pos, d_olen, d_status, d_bad, out_cap, d_file_len, d_file_status, d_written, stream);
     }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;

@@ -68,6 +68,28 @@ struct zmi_png_image;
 struct zmi_tiff_page;
 struct zmi_tiff_info;
 
+// zmi_tiff_write_dev: what the host works out of *w (the geometry is the caller's, so nothing of it is a device value); the kernels of
+// tiff_write_kernels.h take it by value
+struct zmi_tw_plan {
+    uint32_t width, height, seg_w, seg_h, across, n_segs;
+    uint32_t sb, spp, pb, rb;          // bytes of a sample, samples of a pixel, bytes of a pixel, bytes of a segment's row
+    uint32_t pred, assemble, big;
+    uint32_t seg_bytes, last_bytes;    // decoded bytes of a full segment and of the last one (the last strip holds the rows left)
+    uint32_t ss;                       // the segments stand in the scratch at multiples of this: seg_bytes rounded up to 16
+    uint32_t piece_bytes, ppf, ppl, np;   // pieces of a full segment, of the last one, of the page
+    uint32_t band_rows, bands;         // rows of a work item of the predict kernel, items per segment
+    uint64_t off_pos, cnt_pos;         // file positions of the values of the two arrays (inside the entry where n_segs is 1)
+    uint64_t meta_end, seg0;           // where the metadata ends and where segment 0 starts: the next multiple of out_align
+};
+// ... and the file's bytes that follow from *w alone: b[0 .. a_len) stands at 0 (header, IFD, the values of tag 258), b[a_len .. a_len +
+// b_len) at b_pos (the values of tags 338 and 339, behind the two arrays); rec = the zmi_tiff_page of the written file
+struct zmi_tw_meta {
+    uint8_t b[400];
+    uint8_t rec[72];
+    uint32_t a_len, b_len;
+    uint64_t b_pos;
+};
+
 extern "C" {
 int zmi_launch_gen(uint8_t* d_out, uint64_t seed, uint32_t first_shard, uint32_t n_shards, uint32_t shard_bytes,
                    hipStream_t stream);
@@ -335,4 +357,23 @@ int zmi_launch_tiff_finish(const zmi_tiff_page* d_pages, uint32_t n_pages, uint3
                            uint64_t in_len, uint32_t assemble, uint64_t out_cap, uint64_t decoded_bytes, const uint64_t* d_pix_off,
                            const uint64_t* d_out_off, const uint32_t* d_ssz, const uint32_t* d_slen, const int32_t* d_sst,
                            const uint32_t* d_fl, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, hipStream_t stream);
+// writing TIFF files (tiff_write_kernels.h, compiled into pack.hip; the payload copies are zmi_launch_zip_pack, the fold per segment
+// zmi_launch_combine_segments_adler): the piece table, which follows from the plan alone (d_first: n_segs + 1 words, *d_n_eff = n_segs,
+// d_pos[0] = where segment 0 starts); the forward predictor into the scratch, segment k at k * plan.ss; one launch group's places
+// (zmi_launch_png_place with a tail of 4 bytes in place of 20); the fixed bytes that follow from *w alone; per segment the zlib frame,
+// the gap in front, its two array entries and its words (*d_bad, set to all ones by the caller: the first segment whose status is not
+// 0); the file's words
+uint32_t zmi_tiff_predict_tile(void);
+int zmi_launch_tiff_wpieces(zmi_tw_plan plan, uint32_t group, uint32_t wpg, uint64_t* d_p_off, uint32_t* d_p_len, uint32_t* d_head,
+                            uint32_t* d_ends, uint64_t* d_first, uint32_t* d_n_eff, uint64_t* d_pos, hipStream_t stream);
+int zmi_launch_tiff_predict(zmi_tw_plan plan, const uint8_t* d_in, const uint64_t* d_in_off, uint8_t* d_scan, hipStream_t stream);
+int zmi_launch_tiff_place(const uint32_t* d_head, const uint32_t* d_olen, const uint32_t* d_ends, uint32_t n, uint32_t align, uint64_t* d_pos,
+                          hipStream_t stream);
+int zmi_launch_tiff_wmeta(zmi_tw_meta meta, uint8_t* d_out, uint64_t out_cap, hipStream_t stream);
+int zmi_launch_tiff_wsegs(zmi_tw_plan plan, const uint64_t* d_pos, const uint32_t* d_olen, const int32_t* d_st, const uint32_t* d_adler,
+                          uint32_t level, uint32_t strategy, uint8_t* d_out, uint64_t out_cap, uint32_t* d_seg_len, int32_t* d_status,
+                          uint32_t* d_bad, hipStream_t stream);
+int zmi_launch_tiff_wclose(zmi_tw_plan plan, zmi_tw_meta meta, const uint64_t* d_pos, const uint32_t* d_olen, const int32_t* d_status,
+                           const uint32_t* d_bad, uint64_t out_cap, uint64_t* d_file_len, int32_t* d_file_status, void* d_written,
+                           hipStream_t stream);
 }

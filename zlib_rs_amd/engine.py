@@ -31,6 +31,7 @@ PNG_IMAGE_BYTES = 48
 TA_HEADER, TA_CHAIN = 1, 2
 TP_TAGS, TP_FORMAT, TP_COMPRESSION, TP_PLANAR, TP_BIG, TE_OUT, TE_BOUNDS, TE_DATA, TE_LENGTH, TE_SPARSE = range(1, 11)
 TIFF_ASSEMBLE = 1
+TIFF_BIGTIFF = 2     # zmi_tiff_write_dev
 TIFF_PAGE_BYTES, TIFF_INFO_BYTES = 72, 40
 
 
@@ -1353,6 +1354,94 @@ class Engine:
         host = torch.stack([ln.to(torch.int64), st.to(torch.int64)]).view(-1).tolist()
         if host[1] != 0:
             raise RuntimeError("zmi_png_encode_dev: status %d" % host[1])
+        return out[:host[0]].cpu().numpy().tobytes()
+
+    # ---- writing TIFF files (include/zmi355.h) ----
+    _TIFF_DTYPES = {torch.uint8: (8, 1), torch.int8: (8, 2), torch.uint16: (16, 1), torch.int16: (16, 2), torch.float16: (16, 3),
+                    torch.uint32: (32, 1), torch.int32: (32, 2), torch.float32: (32, 3), torch.uint64: (64, 1), torch.int64: (64, 2),
+                    torch.float64: (64, 3)}
+
+    def _tiff_desc(self, shape, dtype, tile, rows_per_strip, predictor, level, strategy, piece_bytes, align, bigtiff, photometric, extra_samples,
+                   assemble):
+        """the zmi_tiff_write of a page of `shape` = (H, W, C) and a torch dtype -- those TiffFile.dtype returns"""
+        if dtype not in self._TIFF_DTYPES:
+            raise ValueError("tiff_write: dtype %s is not one a TIFF sample has" % (dtype,))
+        bits, fmt = self._TIFF_DTYPES[dtype]
+        h, w, c = (int(v) for v in shape)
+        if predictor == "auto":
+            predictor = 3 if fmt == 3 else 2
+        if photometric is None:
+            photometric = 2 if c - int(extra_samples) >= 3 else 1
+        tw, th = (0, 0) if tile is None else ((int(tile), int(tile)) if isinstance(tile, int) else (int(tile[0]), int(tile[1])))
+        flags = (TIFF_ASSEMBLE if assemble else 0) | (TIFF_BIGTIFF if bigtiff else 0)
+        return _lib.TiffWrite(w, h, tw, th, int(rows_per_strip or 0), bits, c, fmt, int(predictor), int(photometric), int(extra_samples),
+                              2 if extra_samples else 0, flags, int(piece_bytes), int(align), int(level), int(strategy))
+
+    def tiff_bound(self, shape, dtype, tile=None, rows_per_strip=None, predictor="auto", level=6, strategy=0, piece_bytes=1 << 20, align=16,
+                   bigtiff=False, photometric=None, extra_samples=0):
+        """room that always suffices for the file of a page of shape (H, W, C) and that dtype; keywords as tiff_write's"""
+        import ctypes as C
+        d = self._tiff_desc(shape, dtype, tile, rows_per_strip, predictor, level, strategy, piece_bytes, align, bigtiff, photometric,
+                            extra_samples, True)
+        bound = int(self.L.zmi_tiff_bound(C.byref(d)))
+        if bound == 0:
+            raise ValueError("tiff_bound: these arguments describe no page zmi_tiff_write_dev writes")
+        return bound
+
+    def tiff_write(self, image_or_segments, tile=None, rows_per_strip=None, predictor="auto", level=6, strategy=0, piece_bytes=1 << 20, align=16,
+                   bigtiff=False, photometric=None, extra_samples=0, out=None):
+        """One page as a complete little-endian Deflate TIFF file in device memory -> (out, file_len int64 [1], seg_len int32 [n_segs],
+        status int32 [n_segs + 1]): the file is out[:file_len], file_len the room it needs whether or not it fitted, seg_len the byte
+        counts of its strips or tiles, status[k] segment k's and status[-1] the file's (Z_BUF_ERROR: out is too small).  A device
+        tensor [H, W] or [H, W, C], C 1 .. 8, of a dtype TiffFile.dtype returns is the page as one image: the predict kernel cuts the
+        segments and pads edge tiles with zeros.  The tuple (data, offsets, shape, dtype) is the dense form: segment k is the bytes
+        data[offsets[k]:] as tiff_read(assemble=False) returns them ([rows, seg_w, C], edge tiles with their padding as it stands),
+        shape = (H, W, C).  tile: None for strips of rows_per_strip rows (None: one strip), an int or (tile_w, tile_h), multiples of
+        16.  predictor: 1, 2, 3 or "auto" -- 3 for floating dtypes, 2 otherwise.  align: where every segment starts in the file;
+        extra_samples: how many of the C samples are unassociated alpha (tag 338); photometric None: RGB for 3 colour samples and
+        more, BlackIsZero otherwise.  last_tiff_written keeps the record tiff_directory would list for the file.  No synchronisation."""
+        import ctypes as C
+        if isinstance(image_or_segments, torch.Tensor):
+            t = image_or_segments
+            if t.device != self.device or t.dim() not in (2, 3) or t.numel() == 0:
+                raise ValueError("tiff_write: the image must be a [H, W] or [H, W, C] tensor on %s" % (self.device,))
+            shape, dtype = (int(t.shape[0]), int(t.shape[1]), 1 if t.dim() == 2 else int(t.shape[2])), t.dtype
+            data, offsets, assemble = t.contiguous().view(-1).view(torch.uint8), None, True
+        else:
+            data, offsets, shape, dtype = image_or_segments
+            if not isinstance(data, torch.Tensor) or data.dtype != torch.uint8 or data.device != self.device or not data.is_contiguous():
+                raise ValueError("tiff_write: data must be a contiguous uint8 tensor on %s" % (self.device,))
+            offsets, assemble = offsets.to(device=self.device, dtype=torch.int64).contiguous(), False
+        if out is not None and (out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous()):
+            raise ValueError("tiff_write: out must be a contiguous uint8 tensor on %s" % (self.device,))
+        d = self._tiff_desc(shape, dtype, tile, rows_per_strip, predictor, level, strategy, piece_bytes, align, bigtiff, photometric,
+                            extra_samples, assemble)
+        bound = int(self.L.zmi_tiff_bound(C.byref(d)))
+        if bound == 0:
+            raise ValueError("tiff_write: these arguments describe no page zmi_tiff_write_dev writes")
+        seg_w, seg_h = (d.tile_w, d.tile_h) if d.tile_w else (d.width, d.rows_per_strip if 0 < d.rows_per_strip < d.height else d.height)
+        n = -(-d.width // seg_w) * -(-d.height // seg_h)
+        if offsets is not None and int(offsets.numel()) < n:
+            raise ValueError("tiff_write: %d segments need %d offsets" % (n, n))
+        if out is None:
+            out = torch.empty(bound, dtype=torch.uint8, device=self.device)
+        file_len = torch.zeros(1, dtype=torch.int64, device=self.device)
+        seg_len = torch.zeros(n, dtype=torch.int32, device=self.device)
+        status = torch.zeros(n + 1, dtype=torch.int32, device=self.device)     # the segments' | the file's
+        self.last_tiff_written = written = torch.zeros(TIFF_PAGE_BYTES, dtype=torch.uint8, device=self.device)
+        _lib.check(self.L.zmi_tiff_write_dev(self._ctx, C.byref(d), data.data_ptr(), offsets.data_ptr() if offsets is not None else None,
+                                             out.data_ptr() if out.numel() else None, int(out.numel()), file_len.data_ptr(), seg_len.data_ptr(),
+                                             status.data_ptr(), status.data_ptr() + 4 * n, written.data_ptr(), _stream_ptr()),
+                   "zmi_tiff_write_dev")
+        return out, file_len, seg_len, status
+
+    def save_tiff(self, tensor, **kw):
+        """One image ([H, W] or [H, W, C] on the device) -> the bytes of its .tif file; a status that is not 0 raises.  Keywords as
+        tiff_write's."""
+        out, file_len, seg_len, status = self.tiff_write(tensor, **kw)
+        host = torch.cat([file_len, status[-1:].to(torch.int64)]).tolist()
+        if host[1] != 0:
+            raise RuntimeError("zmi_tiff_write_dev: status %d" % host[1])
         return out[:host[0]].cpu().numpy().tobytes()
 
     # ---- writing ZIP archives (include/zmi355.h, DESIGN.md section 21) ----

@@ -1110,6 +1110,139 @@ int zmi_tiff_write_dev(zmi_ctx* ctx, const zmi_tiff_write* w, const void* d_in, 
                        void* d_out, uint64_t out_cap, uint64_t* d_file_len, uint32_t* d_seg_len /* NULL or n_segs */,
                        int32_t* d_status /* n_segs */, int32_t* d_file_status, zmi_tiff_page* d_written /* NULL or 1 */, void* stream);
 
+/* ---- reading OpenEXR images (ZIP / ZIPS / NONE): the attribute list, a batch inflate of the chunks, the unzip --------------------------
+ * Two calls, both asynchronous on `stream`, neither synchronises with the host, every per-file failure is a device word.  File i is
+ * d_in[d_in_off[i] .. + d_in_len[i]), at any alignment.  OpenEXR is not part of the reference project: the contract is the format, as
+ * stated here.  Not built, each a change of its own: writing EXR; RLE, PIZ, PXR24, B44, DWA; subsampled channels, mip / rip levels,
+ * multi-part and deep files; a selection of rows or tiles inside a file; conversion of HALF to float.
+ *
+ * The format.  All integers and floats are little-endian.
+ *   File        the magic 76 2f 31 01; a version word u32 -- the low byte is the version number (2), the upper bits are flags: 0x200
+ *               single-part tiled, 0x400 long names (up to 255 bytes instead of 31), 0x800 deep data, 0x1000 multi-part --; the header:
+ *               a list of attributes ended by one 00 byte (an empty name); directly behind it the offset table, one u64 file position
+ *               per chunk; the chunks.  An attribute is name\0 | type\0 | i32 size | size bytes of value.
+ *   Attributes  the reader uses these and skips all others by their size, whatever their type:
+ *               channels (chlist)         entries ended by a 00 byte, each name\0 | i32 pixelType (0 UINT 4 bytes, 1 HALF 2 bytes, 2 FLOAT
+ *                                         4 bytes) | u8 pLinear | 3 reserved bytes | i32 xSampling | i32 ySampling.  The order of the
+ *                                         list is the storage order; writers keep it sorted by name, the reader takes it as it stands.
+ *               compression (1 byte)      0 NONE, 1 RLE, 2 ZIPS: 1 scanline per chunk; 3 ZIP: 16; 4 PIZ: 32; 5 PXR24: 16; 6 B44, 7 B44A,
+ *                                         8 DWAA: 32; 9 DWAB: 256
+ *               dataWindow (box2i)        i32 xMin, yMin, xMax, yMax, inclusive, may be negative; W = xMax - xMin + 1, H = yMax - yMin + 1
+ *               displayWindow (box2i)     recorded, not used
+ *               lineOrder (1 byte)        0 increasing y, 1 decreasing y, 2 random y (tiled files only): the PHYSICAL order of the chunks;
+ *                                         the offset table is always in increasing y, or in tile order
+ *               tiles (tiledesc, 9 bytes; required with flag 0x200)   u32 xSize, u32 ySize, u8 mode: level mode = mode & 15 (0 one level,
+ *                                         1 mipmap, 2 ripmap), rounding = mode >> 4
+ *   Chunks      scanline files: ceil(H / lines per chunk) chunks, chunk k = i32 y | i32 dataSize | data with y = yMin + k * lines
+ *               (absolute); the last chunk holds the scanlines that remain.  Tiled files with one level: ceil(W / xSize) x ceil(H / ySize)
+ *               chunks, table index = tileY * tilesX + tileX, each i32 tileX | i32 tileY | i32 levelX | i32 levelY | i32 dataSize | data;
+ *               edge tiles hold only the pixels inside the data window (cropped, not padded).  The UNCOMPRESSED bytes of a chunk
+ *               ("raw"): for every scanline of the chunk (of the tile) in increasing y, for every channel in list order, that
+ *               scanline's pixels of that channel, left to right -- a row is C planar runs of width * size bytes, and the expected raw
+ *               size is n = rows * sum_c width * size_c.  dataSize == n: the raw bytes as they stand (writers store a chunk raw when
+ *               compression does not shrink it, compression NONE always does); dataSize < n: a compressed chunk; dataSize > n: an error.
+ *   ZIP / ZIPS  the data is one zlib stream (RFC 1950) that inflates to exactly n bytes d[0 .. n).  Predictor undo: t[0] = d[0], t[i] =
+ *               (t[i - 1] + d[i] - 128) mod 256 -- equivalently t[i] = (sum_{k <= i} d[k] - 128 i) mod 256: an inclusive byte sum with 128
+ *               subtracted at odd i.  Interleave: with h = (n + 1) / 2, raw[2 i] = t[i] and raw[2 i + 1] = t[h + i].
+ *               Example: d = 00 80 80 80 e6 19 bd 84 82 82 6a gives raw = 00 3c 00 40 00 42 00 44 66 2e ff.
+ *
+ * zmi_exr_headers_dev   one lane per file walks the attributes (the chain is serial; the batch is the parallelism) and writes one
+ *               zmi_exr_image per file and the first chan_cap channels of file i to d_channels[i * chan_cap ..) (the records behind the
+ *               file's last channel are zeros).  The first rule that holds, in this order, is the record's status:
+ *   ZMI_XE_MAGIC        the four magic bytes are wrong, or the file is shorter than 8 bytes
+ *   ZMI_XE_HEADER       a version number other than 2; an attribute or a name that leaves the file; a name (of an attribute, a type or a
+ *                       channel) that is too long, a type name that is empty; a negative size; a missing channels, compression,
+ *                       dataWindow or lineOrder; missing tiles in a tiled file; a wrong value size for a used attribute (a channel list
+ *                       that does not end with its attribute); an inverted window; a pixel type above 2; zero channels; a sampling below
+ *                       1; a compression above 9; a line order above 2; a tile size of 0, a level mode above 2 or a rounding above 1; an
+ *                       offset table that leaves the file; more than ZMI_EXR_ATTRS_MAX attributes (the walk is one lane's: it ends
+ *                       there, as the TIFF chain ends at 65 535 IFDs).  Only version, the tiled flag and the status are set.
+ *   ZMI_XE_KIND         deep or multi-part flags
+ *   ZMI_XE_COMPRESSION  anything but 0, 2, 3: the file is listed with its dimensions and channels, and flagged
+ *   ZMI_XE_SAMPLING     a sampling other than 1
+ *   ZMI_XE_LEVELS       mipmap or ripmap (n_chunks: those of level 0)
+ *   ZMI_XE_CHANNELS     more than chan_cap channels; n_channels still holds the true count, row_bytes and region_bytes are 0
+ *   ZMI_XE_BIG          W, H, W * H, a chunk's raw size or the region's size does not fit 32 bits
+ *   An attribute that stands twice: the first counts.
+ *
+ * zmi_exr_read_dev      slot j reads file d_sel[j] of the table (d_sel NULL: slot j = file j); duplicates are allowed; an index >= n_files,
+ *               and a record no headers call would write for that file (every size and position is derived again from the windows, the
+ *               compression, the tile description and the channel types and compared; the offset table must stand inside the file),
+ *               get ZMI_E_ARG in the slot's status and nothing of them is read.  chunk_cap and decoded_bytes are the host's bounds on
+ *               the chunks and on the raw bytes (height * row_bytes) of the readable files of the selection, summed in slot order; they
+ *               size the tables and the scratch, and every slot from the first whose running sum passes either bound on gets ZMI_E_ARG.
+ *   Region      the channels' planes in list order; plane c is [H, W] of its type, little-endian, at zmi_exr_channel.plane_off, the
+ *               next multiple of 4 bytes (the at most 2 bytes of padding in front of a plane are not written).  With one pixel type
+ *               throughout the region is a [C, H, W] tensor with a plane stride of W * H * size rounded up to 4 bytes: dense, except
+ *               for several HALF channels of an odd W * H, where one unwritten pixel lies between two planes.
+ *   Plan        d_out_off, out_align, out_cap exactly as zmi_png_decode_dev: d_out_off[j] = the region sizes of the readable slots in
+ *               front, each rounded up to out_align; d_out_off[n_sel] = the room the selection needs; a flagged or failed slot has
+ *               length 0; nothing at or behind d_out + out_cap and nothing in the gaps is written.
+ *   Reading     one kernel reads every chunk's table entry and header; compressed chunks go through the batch decoder with
+ *               ZMI_WRAP_ZLIB and capacity n into scratch, every chunk at a multiple of 16, and the decoder checks the
+ *               Adler-32; raw chunks go through the range copy into the same scratch; the unzip kernel (exr_kernels.h) undoes the
+ *               predictor and the interleave and writes every run at its place in its plane; one kernel writes the slot's words.
+ *               flags must be 0.
+ *   d_status / d_detail   after the record's own flag (Z_DATA_ERROR for MAGIC and HEADER, Z_BUF_ERROR for CHANNELS, else
+ *               Z_VERSION_ERROR; detail = the ZMI_XE_* code) the first of these that holds for any chunk of the file; d_detail = the
+ *               code, with the index of the first chunk that has it above the low 8 bits:
+ *               Z_BUF_ERROR / ZMI_XE_OUT        the region does not fit out_cap (no chunk index)
+ *               Z_MEM_ERROR / ZMI_XE_SCRATCH    the decoder could not reserve what the chunk needs
+ *               Z_DATA_ERROR / ZMI_XE_CHUNK     a table entry that leaves the file; a chunk header whose y or tile coordinates are not
+ *                                               the expected ones; a nonzero level; a dataSize that is negative, above n, or leaves the
+ *                                               file; compression NONE with dataSize != n
+ *               Z_DATA_ERROR / ZMI_XE_MISSING   a table entry of 0, the mark of an unfinished file
+ *               Z_DATA_ERROR / ZMI_XE_DATA      a corrupt stream, a wrong Adler-32, FDICT
+ *               Z_DATA_ERROR / ZMI_XE_LENGTH    the stream does not end at exactly n bytes
+ *   d_out_len[j] = the region's size with status 0, otherwise 0.  Never status 0 with wrong bytes; one bad file does not touch its
+ *   neighbours.  n_sel 0 writes d_out_off[0] = 0 and nothing else.  Bytes and words do not depend on the alignment of d_in, on the
+ *   slot index, on n_files or on the decode-kernel selection.
+ *   Scratch of the context: 40 bytes per slot, 80 per chunk of chunk_cap, 8 per 1024 bytes of decoded_bytes; the inflated chunks,
+ *   decoded_bytes + 16 bytes per chunk + 96; and the decoder's, sized by this call.  Scratch that cannot be reserved is ZMI_E_NOMEM.
+ *   Event timing: 5 = headers; slot and chunk tables, plans, 3 / 6 = decode, resolve, 7 = the copies of raw chunks, 2 = block sums, their
+ *   scans and the unzip, 4 = the slot words. */
+#define ZMI_XE_MAGIC 1        /* zmi_exr_image.status and the slot's detail: Z_DATA_ERROR */
+#define ZMI_XE_HEADER 2       /* Z_DATA_ERROR */
+#define ZMI_XE_KIND 3         /* Z_VERSION_ERROR */
+#define ZMI_XE_COMPRESSION 4  /* Z_VERSION_ERROR */
+#define ZMI_XE_SAMPLING 5     /* Z_VERSION_ERROR */
+#define ZMI_XE_LEVELS 6       /* Z_VERSION_ERROR */
+#define ZMI_XE_CHANNELS 7     /* Z_BUF_ERROR */
+#define ZMI_XE_BIG 8          /* Z_VERSION_ERROR */
+#define ZMI_XE_OUT 9          /* slots only, from here on: Z_BUF_ERROR */
+#define ZMI_XE_SCRATCH 10     /* Z_MEM_ERROR */
+#define ZMI_XE_CHUNK 11       /* Z_DATA_ERROR */
+#define ZMI_XE_MISSING 12
+#define ZMI_XE_DATA 13
+#define ZMI_XE_LENGTH 14
+#define ZMI_EXR_ATTRS_MAX 65535u
+typedef struct zmi_exr_channel {    /* 24 bytes */
+    uint32_t name_pos, name_len;      /* the name's position in the file and its bytes (no 0) */
+    int32_t  pixel_type;              /* 0 UINT, 1 HALF, 2 FLOAT */
+    int32_t  x_sampling, y_sampling;
+    uint32_t plane_off;               /* byte offset of the channel's [H, W] plane inside the file's region */
+} zmi_exr_channel;
+typedef struct zmi_exr_image {      /* 88 bytes */
+    uint32_t version;                 /* the version word: number and flags */
+    uint8_t  compression, line_order, tile_mode, tiled;
+    int32_t  data_window[4], display_window[4];   /* xMin, yMin, xMax, yMax */
+    uint32_t width, height, lines_per_chunk;
+    uint32_t tile_w, tile_h;          /* 0 in scanline files */
+    uint32_t n_channels, n_chunks;
+    uint32_t row_bytes;               /* sum over the channels of width * size */
+    uint32_t region_bytes;            /* the file's region: the planes, each at the next multiple of 4 */
+    int32_t  status;                  /* 0: readable by zmi_exr_read_dev; otherwise the ZMI_XE_* reason */
+    uint64_t table_pos;               /* file position of the offset table */
+} zmi_exr_image;
+uint32_t zmi_exr_trip(void);    /* output bytes one trip of the unzip kernel covers per wave (for tests that place run lengths around it) */
+uint32_t zmi_exr_piece(void);   /* the longest piece of a run one work item of the unzip kernel writes: a whole number of trips */
+int zmi_exr_headers_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_files,
+                        zmi_exr_image* d_images, zmi_exr_channel* d_channels /* n_files * chan_cap */, uint32_t chan_cap, void* stream);
+int zmi_exr_read_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, const zmi_exr_image* d_images,
+                     const zmi_exr_channel* d_channels, uint32_t chan_cap, uint32_t n_files, const uint32_t* d_sel, uint32_t n_sel,
+                     uint32_t chunk_cap, uint64_t decoded_bytes, uint32_t flags, uint32_t out_align, void* d_out, uint64_t out_cap,
+                     uint64_t* d_out_off /* n_sel + 1 */, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, void* stream);
+
 /* ---- host-buffer convenience wrappers: copy in, run the batch on the GPU, copy back ---- */
 int zmi_deflate_batch(zmi_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_shards,
                       int level, int strategy, int wrap, uint8_t* out, uint64_t out_stride, uint32_t* out_len,

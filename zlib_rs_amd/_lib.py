@@ -104,6 +104,13 @@ def lib():
     L.zmi_tiff_row_tile.argtypes = []
     L.zmi_tiff_directory_dev.argtypes = [vp, vp, u64, vp, u32, vp, vp]
     L.zmi_tiff_read_dev.argtypes = [vp, vp, u64, vp, u32, u32, vp, u32, u64, u32, u32, vp, u64, vp, vp, vp, vp, vp]
+    # reading OpenEXR images: the attribute list, a batch inflate of the chunks, the unzip (csrc/exr_kernels.h, zmi_api.hip)
+    L.zmi_exr_trip.restype = u32
+    L.zmi_exr_trip.argtypes = []
+    L.zmi_exr_piece.restype = u32
+    L.zmi_exr_piece.argtypes = []
+    L.zmi_exr_headers_dev.argtypes = [vp, vp, vp, vp, u32, vp, vp, u32, vp]
+    L.zmi_exr_read_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, u32, u32, u64, u32, u32, vp, u64, vp, vp, vp, vp, vp]
     # writing TIFF files: the forward predictor, deflate in pieces, the IFD (csrc/tiff_write_kernels.h, zmi_api.hip); w: a TiffWrite
     L.zmi_tiff_predict_tile.restype = u32
     L.zmi_tiff_predict_tile.argtypes = []

@@ -1197,3 +1197,6 @@ extern "C" int zmi_launch_zip_close(uint8_t* d_out, uint64_t out_cap, const uint
 
 // ---- writing TIFF files (zmi_tiff_write_dev) ------------------------------------------------------------------------------------------------
 #include "tiff_write_kernels.h"
+
+// ---- reading OpenEXR images (zmi_exr_headers_dev / zmi_exr_read_dev) ----------------------------------------------------------------------
+#include "exr_kernels.h"

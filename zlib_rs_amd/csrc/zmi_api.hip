@@ -108,6 +108,7 @@ struct zmi_ctx {
     zmi_buf tiff_dir;                   // zmi_tiff_directory_dev: the positions of the listed IFDs
     zmi_buf tiff;                       // zmi_tiff_read_dev: the slots' tables | the still-predicted segments
     zmi_buf tiff_w;                     // zmi_tiff_write_dev: the piece table | the predicted segments
+    zmi_buf exr;                        // zmi_exr_read_dev: the slots', chunks' and blocks' tables | the inflated chunks
     zmi_buf png;                        // zmi_png_decode_dev: the slots' tables | the gathered IDAT streams | the filtered scanlines
     zmi_buf dict;                       // the shared-dictionary batch calls: layout words and DICTID | deflate image | inflate image (zmi_sd_*)
 };
@@ -173,6 +174,7 @@ extern "C" int zmi_ctx_destroy(zmi_ctx* c) {
     if (c->tiff.p) (void)hipFree(c->tiff.p);
     if (c->tiff_dir.p) (void)hipFree(c->tiff_dir.p);
     if (c->tiff_w.p) (void)hipFree(c->tiff_w.p);
+    if (c->exr.p) (void)hipFree(c->exr.p);
     if (c->mm_scan.p) (void)hipFree(c->mm_scan.p);
     if (c->mm_meta.p) (void)hipFree(c->mm_meta.p);
     for (int k = 0; k < 2; ++k) if (c->st_pin[k].p) (void)hipHostFree(c->st_pin[k].p);
@@ -1686,6 +1688,119 @@ extern "C" int zmi_tiff_read_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, 
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
         zmi_launch_tiff_finish(d_pages, n_pages, page, d_sel, n_sel, in_len, assemble, out_cap, decoded_bytes, d_pix_off, d_out_off, d_ssz, d_slen,
                                d_sst, d_fl, d_out_len, d_status, d_detail, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+// ---- OpenEXR images (include/zmi355.h; kernels in exr_kernels.h) ----------------------------------------------------
+extern "C" int zmi_exr_headers_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_files,
+                                   zmi_exr_image* d_images, zmi_exr_channel* d_channels, uint32_t chan_cap, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (n_files == 0) return ZMI_E_OK;
+    if (!d_in || !d_in_off || !d_in_len || !d_images || (chan_cap && !d_channels)) return zmi_fail(ZMI_E_ARG, "null argument");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    {
+        zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
+        zmi_launch_exr_headers((const uint8_t*)d_in, d_in_off, d_in_len, n_files, d_images, d_channels, chan_cap, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
+extern "C" int zmi_exr_read_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, const zmi_exr_image* d_images,
+                                const zmi_exr_channel* d_channels, uint32_t chan_cap, uint32_t n_files, const uint32_t* d_sel, uint32_t n_sel,
+                                uint32_t chunk_cap, uint64_t decoded_bytes, uint32_t flags, uint32_t out_align, void* d_out, uint64_t out_cap,
+                                uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    if (flags != 0u) return zmi_fail(ZMI_E_ARG, "unknown flag");
+    if (out_align == 0u || out_align > 4096u || (out_align & (out_align - 1u)) != 0u)
+        return zmi_fail(ZMI_E_ARG, "out_align must be a power of two, 1 .. 4096");
+    if (!d_out_off) return zmi_fail(ZMI_E_ARG, "d_out_off is required");
+    if (n_sel > 0x7FFFFFFFu || chunk_cap > 0x7FFFFFFFu) return zmi_fail(ZMI_E_ARG, "n_sel and chunk_cap must be below 2^31");
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    if (n_sel == 0) {
+        ZMI_HIP(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), stream));
+        return ZMI_E_OK;
+    }
+    if (!d_out_len || !d_status || !d_detail) return zmi_fail(ZMI_E_ARG, "d_out_len, d_status and d_detail are required");
+    if ((n_files && (!d_images || !d_channels || !d_in || !d_in_off || !d_in_len)) || (out_cap && !d_out)) return zmi_fail(ZMI_E_ARG, "null argument");
+    if (decoded_bytes > (1ull << 40)) return zmi_fail(ZMI_E_NOMEM, "decoded_bytes sizes the scratch: give the sum there is");
+    // The inflated chunks stand in scratch, every one at a multiple of 16 (the decoder's own plan over d_csz), 16 bytes of margin at
+    // either end of the scratch: the unzip loads whole dwords around a stream and whole 16-byte lines for its carries.
+    const size_t n = n_sel, cc = chunk_cap;
+    const uint64_t nblk = decoded_bytes / 1024u + cc;                 // (EXR_BLOCK: every chunk ends with at most one short block)
+    const uint64_t scan_cap = decoded_bytes + 16ull * cc + 64ull;
+    const size_t tab_bytes = ((2u * (n + 1u) + 4u * (cc + 1u)) * 8u + (6u * n + 12u * cc + 2u * nblk) * 4u + 255u) & ~(size_t)255u;
+    int rc = zmi_reserve(c->exr, tab_bytes + 16u + scan_cap + 16u);
+    if (rc) return rc;
+    uint64_t* d_ch_off = (uint64_t*)c->exr.p;                    // the scan of d_nch: the chunks of slot j are d_ch_off[j] .. d_ch_off[j + 1)
+    uint64_t* d_raw_off = d_ch_off + n + 1;                      // the scan of d_rawb: what decoded_bytes bounds
+    uint64_t* d_soff = d_raw_off + n + 1;                        // where a chunk stands in scratch (the decoder's plan over d_csz)
+    uint64_t* d_item_off = d_soff + cc + 1;                      // the scan of d_items
+    uint64_t* d_blk_off = d_item_off + cc + 1;                   // the scan of d_nblk
+    uint64_t* d_zin_off = d_blk_off + cc + 1;                    // the chunk's data in d_in
+    uint32_t* d_size = (uint32_t*)(d_zin_off + cc + 1);          // per slot: the region of a readable file, else 0
+    uint32_t* d_pcap = d_size + n;                               // ... where it fits out_cap, else 0
+    uint32_t* d_nch = d_pcap + n;                                // its chunks
+    uint32_t* d_rawb = d_nch + n;                                // its raw bytes
+    uint32_t* d_kind = d_rawb + n;
+    uint32_t* d_live = d_kind + n;
+    uint32_t* d_zin_len = d_live + n;                            // per chunk: dataSize of a compressed chunk
+    uint32_t* d_csz = d_zin_len + cc;                            // the raw size n of a chunk whose header is right
+    uint32_t* d_scap = d_csz + cc;
+    uint32_t* d_rawlen = d_scap + cc;                            // n of a chunk stored raw: the copy's length
+    uint32_t* d_fl = d_rawlen + cc;                              // EXR_FL_*
+    uint32_t* d_items = d_fl + cc;                               // the pieces of the chunk's runs
+    uint32_t* d_nblk = d_items + cc;                             // the blocks of byte sums of a compressed chunk
+    uint32_t* d_cslot = d_nblk + cc;                             // the chunk's slot
+    uint32_t* d_slen = d_cslot + cc;                             // the decoder's words
+    uint32_t* d_sused = d_slen + cc;
+    int32_t* d_sst = (int32_t*)(d_sused + cc);
+    int32_t* d_sdet = d_sst + cc;
+    uint32_t* d_bsum = (uint32_t*)(d_sdet + cc);                 // one byte sum per block
+    uint32_t* d_bpre = d_bsum + nblk;                            // ... and the sums in front of it inside its chunk
+    uint8_t* d_sbuf = (uint8_t*)c->exr.p + tab_bytes + 16u;
+    const uint8_t* in = (const uint8_t*)d_in;
+    {
+        zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
+        zmi_launch_exr_slots(d_in_len, d_images, d_channels, chan_cap, n_files, d_sel, n_sel, 0u, chunk_cap, decoded_bytes, nullptr, nullptr, nullptr,
+                             d_size, d_nch, d_rawb, d_kind, d_live, stream);
+        zmi_launch_inflate_pack_plan(d_size, n_sel, out_align, out_cap, d_out_off, d_pcap, stream);
+        zmi_launch_scan_sizes(d_nch, n_sel, d_ch_off, stream);
+        zmi_launch_scan_sizes(d_rawb, n_sel, d_raw_off, stream);
+        zmi_launch_exr_slots(d_in_len, d_images, d_channels, chan_cap, n_files, d_sel, n_sel, 1u, chunk_cap, decoded_bytes, d_pcap, d_ch_off, d_raw_off,
+                             d_size, d_nch, d_rawb, d_kind, d_live, stream);
+        if (chunk_cap) {
+            zmi_launch_exr_chunks(in, d_in_off, d_in_len, d_images, d_channels, chan_cap, d_sel, n_sel, d_ch_off, d_live, chunk_cap, d_zin_off, d_zin_len,
+                                  d_csz, d_rawlen, d_fl, d_items, d_nblk, d_cslot, stream);
+            zmi_launch_scan_sizes(d_items, chunk_cap, d_item_off, stream);
+            zmi_launch_scan_sizes(d_nblk, chunk_cap, d_blk_off, stream);
+        }
+    }
+    if (chunk_cap) {
+        rc = zmi_inflate_packed_body(c, d_in, d_zin_off, d_zin_len, chunk_cap, ZMI_WRAP_ZLIB, nullptr, 0u, d_csz, d_scap, 16u, d_sbuf, scan_cap, d_soff,
+                                     d_slen, d_sst, d_sused, d_sdet, ZMI_K_PARSE, stream_);
+        if (rc) return rc;
+        {
+            // chunks stored raw: their bytes as they stand (max_len only shapes the launch)
+            zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+            zmi_launch_copy_ranges(in, d_zin_off, 0u, d_rawlen, chunk_cap, d_sbuf, d_soff, scan_cap,
+                                   decoded_bytes > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)decoded_bytes, stream);
+        }
+        {
+            zmi_scope_timer tm(c, ZMI_K_ENCODE, stream);
+            zmi_launch_exr_blocksum(d_sbuf, d_soff, d_csz, d_scap, d_blk_off, chunk_cap, nblk, d_bsum, d_bpre, stream);
+            zmi_launch_exr_unzip(d_images, d_channels, chan_cap, d_sel, d_ch_off, d_cslot, chunk_cap, d_item_off, decoded_bytes / 2u, d_sbuf,
+                                 d_soff, d_csz, d_scap, d_slen, d_sst, d_rawlen, d_blk_off, d_bpre, (uint8_t*)d_out, d_out_off, stream);
+        }
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_exr_finish(d_images, d_sel, n_sel, d_kind, d_size, d_pcap, d_ch_off, d_raw_off, chunk_cap, decoded_bytes, d_csz, d_scap, d_rawlen,
+                              d_fl, d_slen, d_sst, d_out_len, d_status, d_detail, stream);
     }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;

@@ -67,6 +67,8 @@ struct zmi_zip_info;
 struct zmi_png_image;
 struct zmi_tiff_page;
 struct zmi_tiff_info;
+struct zmi_exr_image;
+struct zmi_exr_channel;
 
 // zmi_tiff_write_dev: what the host works out of *w (the geometry is the caller's, so nothing of it is a device value); the kernels of
 // tiff_write_kernels.h take it by value
@@ -376,4 +378,31 @@ int zmi_launch_tiff_wsegs(zmi_tw_plan plan, const uint64_t* d_pos, const uint32_
 int zmi_launch_tiff_wclose(zmi_tw_plan plan, zmi_tw_meta meta, const uint64_t* d_pos, const uint32_t* d_olen, const int32_t* d_status,
                            const uint32_t* d_bad, uint64_t out_cap, uint64_t* d_file_len, int32_t* d_file_status, void* d_written,
                            hipStream_t stream);
+// OpenEXR images (exr_kernels.h, compiled into pack.hip): the records; the slots' sizes (pass 0, in front of the plan and the scans of the
+// chunk counts and raw bytes) and which of them are read (pass 1); the chunks' tables over chunk_cap entries; one byte sum per block of
+// every inflated chunk and their scan per chunk (bound: the words of d_bsum and of d_bpre); the unzip over the items -- d_item_off the
+// scan of d_items -- from the scratch at d_soff to the planes; the slots' final words
+uint32_t zmi_exr_trip(void);
+uint32_t zmi_exr_piece(void);
+int zmi_launch_exr_headers(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n, zmi_exr_image* d_images,
+                           zmi_exr_channel* d_chans, uint32_t chan_cap, hipStream_t stream);
+int zmi_launch_exr_slots(const uint32_t* d_in_len, const zmi_exr_image* d_images, const zmi_exr_channel* d_chans, uint32_t chan_cap,
+                         uint32_t n_files, const uint32_t* d_sel, uint32_t n_sel, uint32_t pass, uint64_t chunk_cap, uint64_t decoded_bytes,
+                         const uint32_t* d_pcap, const uint64_t* d_ch_off, const uint64_t* d_raw_off, uint32_t* d_size, uint32_t* d_nch,
+                         uint32_t* d_rawb, uint32_t* d_kind, uint32_t* d_live, hipStream_t stream);
+int zmi_launch_exr_chunks(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, const zmi_exr_image* d_images,
+                          const zmi_exr_channel* d_chans, uint32_t chan_cap, const uint32_t* d_sel, uint32_t n_sel, const uint64_t* d_ch_off,
+                          const uint32_t* d_live, uint32_t chunk_cap, uint64_t* d_zin_off, uint32_t* d_zin_len, uint32_t* d_csz,
+                          uint32_t* d_rawlen, uint32_t* d_fl, uint32_t* d_items, uint32_t* d_nblk, uint32_t* d_cslot, hipStream_t stream);
+int zmi_launch_exr_blocksum(const uint8_t* d_sbuf, const uint64_t* d_soff, const uint32_t* d_csz, const uint32_t* d_scap,
+                            const uint64_t* d_blk_off, uint32_t chunk_cap, uint64_t bound, uint32_t* d_bsum, uint32_t* d_bpre, hipStream_t stream);
+int zmi_launch_exr_unzip(const zmi_exr_image* d_images, const zmi_exr_channel* d_chans, uint32_t chan_cap, const uint32_t* d_sel,
+                         const uint64_t* d_ch_off, const uint32_t* d_cslot, uint32_t chunk_cap, const uint64_t* d_item_off, uint64_t bound,
+                         const uint8_t* d_sbuf, const uint64_t* d_soff, const uint32_t* d_csz, const uint32_t* d_scap, const uint32_t* d_slen,
+                         const int32_t* d_sst, const uint32_t* d_rawlen, const uint64_t* d_blk_off, const uint32_t* d_bpre, uint8_t* d_out,
+                         const uint64_t* d_out_off, hipStream_t stream);
+int zmi_launch_exr_finish(const zmi_exr_image* d_images, const uint32_t* d_sel, uint32_t n_sel, const uint32_t* d_kind, const uint32_t* d_size,
+                          const uint32_t* d_pcap, const uint64_t* d_ch_off, const uint64_t* d_raw_off, uint64_t chunk_cap, uint64_t decoded_bytes,
+                          const uint32_t* d_csz, const uint32_t* d_scap, const uint32_t* d_rawlen, const uint32_t* d_fl, const uint32_t* d_slen,
+                          const int32_t* d_sst, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, hipStream_t stream);
 }

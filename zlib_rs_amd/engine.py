@@ -33,6 +33,10 @@ TP_TAGS, TP_FORMAT, TP_COMPRESSION, TP_PLANAR, TP_BIG, TE_OUT, TE_BOUNDS, TE_DAT
 TIFF_ASSEMBLE = 1
 TIFF_BIGTIFF = 2     # zmi_tiff_write_dev
 TIFF_PAGE_BYTES, TIFF_INFO_BYTES = 72, 40
+# zmi_exr_headers_dev / zmi_exr_read_dev (include/zmi355.h ZMI_XE_*)
+(XE_MAGIC, XE_HEADER, XE_KIND, XE_COMPRESSION, XE_SAMPLING, XE_LEVELS, XE_CHANNELS, XE_BIG, XE_OUT, XE_SCRATCH, XE_CHUNK, XE_MISSING,
+ XE_DATA, XE_LENGTH) = range(1, 15)
+EXR_IMAGE_BYTES, EXR_CHANNEL_BYTES = 88, 24
 
 
 def _stream_ptr():
@@ -261,6 +265,105 @@ class PngBatch:
         return table[idx.to(torch.int64).clamp(0, table.shape[0] - 1)]
 
 
+class ExrBatch:
+    """A batch of OpenEXR files as zmi_exr_headers_dev lists them (include/zmi355.h).  data: the files on the device; offsets int64 [n] /
+    lengths int32 [n]: file i is data[offsets[i] : + lengths[i]]; images: uint8 [n, 88], the device table of zmi_exr_image records;
+    chans: uint8 [n, chan_cap, 24], the zmi_exr_channel records.  Everything below reads ONE host copy of both tables, made at the
+    first use (one synchronisation)."""
+    _DTYPES = {0: torch.int32, 1: torch.float16, 2: torch.float32}       # UINT leaves as int32 bits
+
+    def __init__(self, data, offsets, lengths, images, chans, chan_cap, host_data=None):
+        self.data, self.offsets, self.lengths, self.images, self.chans, self.chan_cap = data, offsets, lengths, images, chans, chan_cap
+        self._host_data, self._host = host_data, None
+
+    def _tables(self):
+        if self._host is None:
+            import numpy as np
+            img = np.dtype([("version", "<u4"), ("compression", "u1"), ("line_order", "u1"), ("tile_mode", "u1"), ("tiled", "u1"),
+                            ("data_window", "<i4", 4), ("display_window", "<i4", 4), ("width", "<u4"), ("height", "<u4"),
+                            ("lines_per_chunk", "<u4"), ("tile_w", "<u4"), ("tile_h", "<u4"), ("n_channels", "<u4"), ("n_chunks", "<u4"),
+                            ("row_bytes", "<u4"), ("region_bytes", "<u4"), ("status", "<i4"), ("table_pos", "<u8")])
+            ch = np.dtype([("name_pos", "<u4"), ("name_len", "<u4"), ("pixel_type", "<i4"), ("x_sampling", "<i4"), ("y_sampling", "<i4"),
+                           ("plane_off", "<u4")])
+            both = torch.cat([self.images.reshape(-1), self.chans.reshape(-1)]).cpu().numpy()
+            n = self.n
+            self._host = (both[:n * EXR_IMAGE_BYTES].view(img), both[n * EXR_IMAGE_BYTES:].view(ch).reshape(n, self.chan_cap),
+                          self.offsets.cpu().tolist() if n else [])
+        return self._host
+
+    @property
+    def n(self):
+        return int(self.images.shape[0])
+
+    def record(self, i):
+        """record i as a dict of Python values"""
+        r = self._tables()[0][i]
+        return {k: (tuple(int(x) for x in r[k]) if r[k].ndim else int(r[k])) for k in r.dtype.names}
+
+    def status(self, i):
+        """0 = readable, else the XE_* reason the headers call gives"""
+        return int(self._tables()[0][i]["status"])
+
+    @property
+    def readable(self):
+        return [int(s) == 0 for s in self._tables()[0]["status"]]
+
+    def _listed(self, i):
+        return min(int(self._tables()[0][i]["n_channels"]), self.chan_cap)
+
+    def channels(self, i):
+        """[(name, dtype)] in storage order (the first chan_cap of them)"""
+        rec, ch, offs = self._tables()
+        out = []
+        for c in range(self._listed(i)):
+            at, ln = offs[i] + int(ch[i][c]["name_pos"]), int(ch[i][c]["name_len"])
+            raw = bytes(self._host_data[at:at + ln]) if self._host_data is not None else bytes(self.data[at:at + ln].cpu().numpy().tobytes())
+            out.append((raw.decode("latin-1"), self._DTYPES[int(ch[i][c]["pixel_type"])]))
+        return out
+
+    def shape(self, i):
+        """(C, H, W)"""
+        r = self._tables()[0][i]
+        return int(r["n_channels"]), int(r["height"]), int(r["width"])
+
+    def windows(self, i):
+        """(dataWindow, displayWindow), each (xMin, yMin, xMax, yMax)"""
+        r = self._tables()[0][i]
+        return tuple(int(x) for x in r["data_window"]), tuple(int(x) for x in r["display_window"])
+
+    def tiled(self, i):
+        """(xSize, ySize) of a tiled file, None for scanlines"""
+        r = self._tables()[0][i]
+        return (int(r["tile_w"]), int(r["tile_h"])) if int(r["tiled"]) else None
+
+    def image(self, out, out_off, j, file=None):
+        """Slot j of an exr_read result as a zero-copy [C, H, W] view of `out` in the channels' common dtype; raises ValueError where
+        the types differ.  The planes stand at multiples of 4 bytes, so with several HALF channels of an odd W * H one unwritten
+        pixel lies between two planes: the view is then strided (plane stride W * H + 1), dense in every other case.  file: the index
+        of the file the slot read (default: j, the whole batch in order)."""
+        i = j if file is None else file
+        chans = self.channels(i)
+        if len({d for _, d in chans}) != 1:
+            raise ValueError("image: the channels of file %d differ in type, use channel()" % i)
+        c, h, w = self.shape(i)
+        at = int(out_off[j])
+        dt = chans[0][1]
+        size = 2 if dt == torch.float16 else 4
+        pitch = -(-h * w * size // 4) * 4 // size                        # a plane's pixels and its padding, as plane_off places them
+        flat = out[at:at + int(self._tables()[0][i]["region_bytes"])].view(dt)
+        return torch.as_strided(flat, (c, h, w), (pitch, w, 1))
+
+    def channel(self, out, out_off, j, name, file=None):
+        """channel `name` of slot j as a zero-copy [H, W] view of `out` in the channel's dtype (float16, float32, int32 bits for UINT)"""
+        i = j if file is None else file
+        _, h, w = self.shape(i)
+        for c, (nm, dt) in enumerate(self.channels(i)):
+            if nm == name:
+                at = int(out_off[j]) + int(self._tables()[1][i][c]["plane_off"])
+                return out[at:at + h * w * (2 if dt == torch.float16 else 4)].view(dt).view(h, w)
+        raise KeyError(name)
+
+
 class ZipDirectory:
     """The central directory of a ZIP archive as zmi_zip_directory_dev lists it (include/zmi355.h).  entries: uint8 [n_listed, 48], the
     device table of zmi_zip_entry records; info: the host copy of zmi_zip_info as a dict; data: the archive on the device.  The int32
@@ -406,6 +509,7 @@ class Engine:
         self.last_png_detail = None      # png_decode: the PE_* tensor of the last call
         self.last_png_written = None     # png_encode: the table zmi_png_headers_dev would list for the files of the last call
         self.last_tiff_detail = None     # tiff_read: the TP_* / TE_* tensor of the last call
+        self.last_exr_detail = None      # exr_read: the XE_* tensor of the last call (the first bad chunk above the low 8 bits)
         if scratch_bytes:
             _lib.check(self.L.zmi_ctx_set_scratch_limit(self._ctx, int(scratch_bytes)), "zmi_ctx_set_scratch_limit")
 
@@ -1257,6 +1361,84 @@ class Engine:
             guess = n_sel * (-(-r["seg_bytes"] // align) * align) if sizes is None else sum(-(-s // align) * align for s in sizes)
             out = torch.empty(guess if ok else 0, dtype=torch.uint8, device=self.device)
         call(out)
+        return out, out_off, out_len, status
+
+    # ---- OpenEXR images (include/zmi355.h) ----
+    def exr_headers(self, files, offsets=None, lengths=None, chan_cap=32):
+        """The attribute lists of a batch of OpenEXR files -> ExrBatch.  files: a list of bytes objects or uint8 tensors (concatenated
+        and uploaded where they are not on the device), one bytes object, or one uint8 device tensor with offsets / lengths (int64 /
+        int32 tables, file i = data[offsets[i] : + lengths[i]]; neither: the tensor is ONE file).  chan_cap: channels listed per
+        file.  No synchronisation; a file the call flags (XE_*) is listed and raises nothing."""
+        host = None
+        if isinstance(files, (list, tuple)):
+            import numpy as np
+            sizes = [int(b.numel()) if isinstance(b, torch.Tensor) else len(b) for b in files]
+            offs = np.zeros(len(files), dtype=np.int64)
+            if len(files) > 1:
+                np.cumsum(sizes[:-1], out=offs[1:])
+            offsets, lengths = torch.from_numpy(offs), torch.tensor(sizes, dtype=torch.int32)
+            if files and all(isinstance(b, torch.Tensor) for b in files):
+                files = torch.cat([b.to(self.device).reshape(-1) for b in files]).contiguous()
+            else:
+                files = host = b"".join(bytes(b.cpu().numpy().tobytes()) if isinstance(b, torch.Tensor) else bytes(b) for b in files)
+        elif isinstance(files, (bytes, bytearray, memoryview)):
+            host = bytes(files)
+        data = self._zip_data(files)
+        if offsets is None:
+            offsets = torch.zeros(1, dtype=torch.int64)
+            lengths = torch.tensor([int(data.numel())], dtype=torch.int32)
+        offsets = offsets.to(device=self.device, dtype=torch.int64).contiguous()
+        lengths = lengths.to(device=self.device, dtype=torch.int32).contiguous()
+        n, chan_cap = int(lengths.numel()), int(chan_cap)
+        if int(offsets.numel()) < n:
+            raise ValueError("exr_headers: %d lengths need %d offsets" % (n, n))
+        if chan_cap < 1:
+            raise ValueError("exr_headers: chan_cap must be at least 1")
+        images = torch.zeros((n, EXR_IMAGE_BYTES), dtype=torch.uint8, device=self.device)
+        chans = torch.zeros((n, chan_cap, EXR_CHANNEL_BYTES), dtype=torch.uint8, device=self.device)
+        _lib.check(self.L.zmi_exr_headers_dev(self._ctx, data.data_ptr() if data.numel() else None, offsets.data_ptr() if n else None,
+                                              lengths.data_ptr() if n else None, n, images.data_ptr() if n else None,
+                                              chans.data_ptr() if n else None, chan_cap, _stream_ptr()), "zmi_exr_headers_dev")
+        return ExrBatch(data, offsets, lengths, images, chans, chan_cap, host)
+
+    def exr_read(self, batch, sel=None, align=16, out=None):
+        """Files of an ExrBatch, inflated, unzipped and cut into channel planes, densely in one buffer -> (out, out_off int64 [n_sel +
+        1], out_len int32 [n_sel], status int32 [n_sel]).  Slot j stands at out[out_off[j] : out_off[j] + out_len[j]]: the channels'
+        [H, W] planes in list order (ExrBatch.image / ExrBatch.channel give the views); out_off[-1] is the room the selection needs.
+        sel (a list or an int32 tensor) selects, None: every file.  status 0: every check passed; every other status has length 0 and
+        nothing is raised for a file.  last_exr_detail keeps the XE_* tensor.  The bounds the call needs -- chunks, raw bytes, room --
+        come from the host copy of the batch's tables (one synchronisation the first time the batch is used)."""
+        b = batch
+        if align < 1 or align > 4096 or align & (align - 1):
+            raise ValueError("align must be a power of two, 1 .. 4096")
+        if out is not None and (out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous()):
+            raise ValueError("exr_read: out must be a contiguous uint8 tensor on %s" % (self.device,))
+        n = b.n
+        picks = list(range(n)) if sel is None else [int(k) for k in (sel.tolist() if isinstance(sel, torch.Tensor) else sel)]
+        d_sel = None
+        if sel is not None:
+            d_sel = (sel if isinstance(sel, torch.Tensor) else torch.tensor(picks, dtype=torch.int64)).to(device=self.device, dtype=torch.int32).contiguous()
+        n_sel = len(picks)
+        rec = b._tables()[0] if n else None
+        chunks = decoded = room = 0
+        for k in picks:
+            if 0 <= k < n and int(rec[k]["status"]) == 0:
+                chunks += int(rec[k]["n_chunks"])
+                decoded += int(rec[k]["height"]) * int(rec[k]["row_bytes"])
+                room += -(-int(rec[k]["region_bytes"]) // align) * align
+        out_off = torch.zeros(n_sel + 1, dtype=torch.int64, device=self.device)
+        out_len = torch.zeros(n_sel, dtype=torch.int32, device=self.device)
+        status = torch.zeros(n_sel, dtype=torch.int32, device=self.device)
+        detail = torch.zeros(n_sel, dtype=torch.int32, device=self.device)
+        self.last_exr_detail = detail
+        if out is None:
+            out = torch.empty(room, dtype=torch.uint8, device=self.device)
+        _lib.check(self.L.zmi_exr_read_dev(self._ctx, b.data.data_ptr() if n else None, b.offsets.data_ptr() if n else None,
+                                           b.lengths.data_ptr() if n else None, b.images.data_ptr() if n else None,
+                                           b.chans.data_ptr() if n else None, b.chan_cap, n,
+                                           d_sel.data_ptr() if d_sel is not None and n_sel else None, n_sel, chunks, decoded, 0, int(align),
+                                           out.data_ptr() if out.numel() else None, int(out.numel()), out_off.data_ptr(), out_len.data_ptr(),
+                                           status.data_ptr(), detail.data_ptr(), _stream_ptr()), "zmi_exr_read_dev")
         return out, out_off, out_len, status
 
     # ---- writing PNG images (include/zmi355.h, DESIGN.md section 23) ----

@@ -7,6 +7,7 @@
 // batch is cut into groups that fit it.  No CPU fallback exists: without a HIP device every entry
 // point fails with ZMI_E_NODEVICE.
 #include "zmi_kernels.h"
+#include "zmi_scratch.h"
 #include "../../include/zmi355.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -121,6 +122,46 @@ static int zmi_reserve(zmi_buf& b, size_t bytes) {
     if (e != hipSuccess) return zmi_fail(ZMI_E_NOMEM, "hipMalloc(scratch)", e);
     b.cap = want;
     return 0;
+}
+
+// A call's tables in one context buffer: `layout` (zmi_scratch.h: a function of a carver that takes every table once and returns the
+// carver's end) sizes the reservation, then yields the pointers.  The capacity the emulator build holds the takes to is the size
+// that was asked for, not what zmi_reserve rounded it up to.
+template <class L> static int zmi_carve(zmi_buf& b, L&& layout) {
+    const size_t bytes = layout(zmi_carver());
+    int rc = zmi_reserve(b, bytes);
+    if (rc) return rc;
+    layout(zmi_carver(b.p, bytes));
+    return 0;
+}
+
+// ---- the argument checks the container calls share (the texts are part of the interface: tests and callers match on them) ----
+static int zmi_check_out_align(uint32_t out_align) {
+    if (out_align == 0u || out_align > 4096u || (out_align & (out_align - 1u)) != 0u)
+        return zmi_fail(ZMI_E_ARG, "out_align must be a power of two, 1 .. 4096");
+    return ZMI_E_OK;
+}
+static int zmi_check_level_strategy(int& level, int strategy) {   // (-1: the default level, 6)
+    if (level == -1) level = 6;
+    if (level < 0 || level > 9) return zmi_fail(ZMI_E_ARG, "level must be -1..9");
+    if (strategy < 0 || strategy > 4) return zmi_fail(ZMI_E_ARG, "strategy must be 0..4");
+    return ZMI_E_OK;
+}
+static int zmi_check_piece_bytes(uint32_t piece_bytes) {
+    if (piece_bytes == 0 || piece_bytes > (1u << 30)) return zmi_fail(ZMI_E_ARG, "piece_bytes must be 1 .. 2^30");
+    return ZMI_E_OK;
+}
+// The readers' empty selection (ZIP, PNG, TIFF, EXR): nothing is read, d_out_off[0] = 0 is the whole result and the call is *done;
+// any other selection needs the result arrays.
+static int zmi_empty_selection(uint32_t n_sel, uint64_t* d_out_off, const void* d_out_len, const void* d_status, const void* d_detail,
+                               hipStream_t stream, bool* done) {
+    *done = n_sel == 0;
+    if (n_sel == 0) {
+        ZMI_HIP(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), stream));
+        return ZMI_E_OK;
+    }
+    if (!d_out_len || !d_status || !d_detail) return zmi_fail(ZMI_E_ARG, "d_out_len, d_status and d_detail are required");
+    return ZMI_E_OK;
 }
 
 extern "C" const char* zmi_version(void) { return "zmi355 0.1.0 (gfx950; zlib ABI 1.3.0-zlib-rs-0.6.7 compatible)"; }
@@ -442,6 +483,26 @@ static uint32_t zmi_enc_regions(uint32_t max_len, uint64_t out_stride, uint32_t 
     // every piece region must hold its worst case (stored blocks + marker) and stay 16-byte aligned
     while (pieces > 1u && ((out_stride / pieces) & ~15ull) < zmi_enc_region_worst(max_len, pieces, block_tokens, dictid)) --pieces;
     return pieces;
+}
+// The slot of a piece of at most max_len bytes that is encoded in the regions of a piece_bytes shard (zmi_deflate_impl, geom_len =
+// piece_bytes: bytes that depend on piece_bytes alone, slots that follow the data): zmi_deflate_pieces_stride(max_len), more only where
+// sixteen regions' worst cases do not fit that (pieces of a few KiB)
+static uint64_t zmi_piece_slot_stride(uint32_t max_len, uint32_t piece_bytes, int level) {
+    const uint32_t regions = zmi_enc_regions(piece_bytes, zmi_deflate_pieces_stride(piece_bytes), 65536u, kLevels[level].tok, false);
+    const uint64_t hold = (uint64_t)regions * ((zmi_enc_region_worst(max_len, regions, kLevels[level].tok, false) + 15u) & ~15ull);
+    return std::max<uint64_t>(zmi_deflate_pieces_stride(max_len), hold);
+}
+// ZMI_STREAM_GROUP (tests, probes): the pieces per launch group, whatever the scratch limit says; 0: not set
+static uint64_t zmi_group_override() {
+    const char* gv = zmi_tune("ZMI_STREAM_GROUP");
+    return gv && atoll(gv) > 0 ? (uint64_t)atoll(gv) : 0u;
+}
+// The launch groups of np pieces (zmi_scratch.h: one group's output slots and the encoder's match scratch together stay within the
+// scratch limit) and one group's slots in c->sd_slots
+static int zmi_plan_slots(zmi_ctx* c, uint64_t np, uint32_t max_len, uint64_t stride, const char* too_small, zmi_group_plan* plan) {
+    *plan = zmi_plan_groups(c->scratch_limit, zmi_group_override(), np, max_len, stride);
+    if (np && plan->group == 0) return zmi_fail(ZMI_E_NOMEM, too_small);
+    return zmi_reserve(c->sd_slots, (size_t)(plan->group * stride));
 }
 
 // carry: -1 = what chain_mode implies, 0 = segments forget history (independent pieces of one stream), 1 = window carry-over.
@@ -812,12 +873,12 @@ extern "C" int zmi_deflate_stream_dev(zmi_ctx* c, const void* d_in, uint64_t n, 
                                       uint32_t flags, void* d_out, uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_piece_off,
                                       int32_t* d_status, void* stream_) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
-    if (piece_bytes == 0 || piece_bytes > (1u << 30)) return zmi_fail(ZMI_E_ARG, "piece_bytes must be 1 .. 2^30");
+    int rc = zmi_check_piece_bytes(piece_bytes);
+    if (rc) return rc;
     if (flags & ~(uint32_t)ZMI_STREAM_INDEPENDENT) return zmi_fail(ZMI_E_ARG, "zmi_deflate_stream_dev: unknown flags");
     if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_GZIP) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip");
-    if (level == -1) level = 6;
-    if (level < 0 || level > 9) return zmi_fail(ZMI_E_ARG, "level must be -1..9");
-    if (strategy < 0 || strategy > 4) return zmi_fail(ZMI_E_ARG, "strategy must be 0..4");
+    rc = zmi_check_level_strategy(level, strategy);
+    if (rc) return rc;
     if ((n && !d_in) || !d_out || !d_out_len || !d_status) return zmi_fail(ZMI_E_ARG, "null argument");
     const uint64_t np64 = n ? (n + piece_bytes - 1u) / piece_bytes : 1u;
     if (np64 > 0x7FFFFFFFull) return zmi_fail(ZMI_E_ARG, "zmi_deflate_stream_dev: more than 2^31 - 1 pieces");
@@ -826,30 +887,26 @@ extern "C" int zmi_deflate_stream_dev(zmi_ctx* c, const void* d_in, uint64_t n, 
     hipStream_t stream = (hipStream_t)stream_;
     ZMI_ON_DEVICE(c);
 
-    // per-piece tables: in_off u64 | piece offsets u64 [np + 1] (unless the caller's index holds them) | raw total u64 |
-    // in_len u32 | out_len u32 | status i32 | check u32 | combined check u32
-    const size_t own_off = d_piece_off ? 0u : ((size_t)np + 1u) * 8u;
-    int rc = zmi_reserve(c->sd_meta, (size_t)np * 8u + own_off + 8u + (size_t)np * 16u + 16u);
+    uint64_t *d_off, *d_poff, *d_raw;
+    uint32_t *d_len, *d_olen, *d_chk, *d_comb;
+    int32_t* d_st;
+    rc = zmi_carve(c->sd_meta, [&](zmi_carver k) {
+        k.take(np, d_off);                                  // the pieces' places in d_in
+        k.take_unless(d_piece_off, np + 1u, d_poff);        // ... in the payload (the caller's index holds them if there is one)
+        k.take(1u, d_raw);                                  // the raw total
+        k.take(np, d_len, d_olen, d_st, d_chk);             // per piece: raw and compressed size, status, check value
+        k.take(1u, d_comb);                                 // the combined check
+        k.skip(12u);                                        // (spare: the reservation has always ended with it)
+        return k.end();
+    });
     if (rc) return rc;
-    uint64_t* d_off = (uint64_t*)c->sd_meta.p;
-    uint64_t* d_poff = d_piece_off ? d_piece_off : d_off + np;
-    uint64_t* d_raw = (uint64_t*)((uint8_t*)c->sd_meta.p + (size_t)np * 8u + own_off);
-    uint32_t* d_len = (uint32_t*)(d_raw + 1);
-    uint32_t* d_olen = d_len + np;
-    int32_t* d_st = (int32_t*)(d_olen + np);
-    uint32_t* d_chk = (uint32_t*)(d_st + np);
-    uint32_t* d_comb = d_chk + np;
 
-    // launch groups: one group's output slots and the encoder's match scratch together stay within the scratch limit
     const uint32_t max_len = n < piece_bytes ? (uint32_t)n : piece_bytes;
     const uint64_t stride = zmi_deflate_pieces_stride(max_len);
-    const uint64_t match_per = ((((uint64_t)max_len + 63u) & ~63ull) ? (((uint64_t)max_len + 63u) & ~63ull) : 64u) * 4u;
-    uint64_t group = c->scratch_limit / (stride + match_per + match_per / 16u);
-    if (const char* gv = zmi_tune("ZMI_STREAM_GROUP")) if (atoll(gv) > 0) group = (uint64_t)atoll(gv);
-    if (group == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one piece");
-    if (group > np) group = np;
-    rc = zmi_reserve(c->sd_slots, (size_t)(group * stride));
+    zmi_group_plan plan;
+    rc = zmi_plan_slots(c, np, max_len, stride, "scratch limit too small for one piece", &plan);
     if (rc) return rc;
+    const uint64_t group = plan.group;
 
     ZMI_HIP(hipMemsetAsync(d_status, 0, 4, stream));
     ZMI_HIP(hipMemsetAsync(d_poff, 0, 8, stream));   // where the first group's pack starts
@@ -900,25 +957,26 @@ extern "C" uint64_t zmi_bgzf_bound(uint64_t n, uint32_t block_bytes) {
 }
 
 // Blocks d_len[0 .. n) (every length <= max_len <= ZMI_BGZF_BLOCK_MAX: the callers saw to that) framed and packed into d_out from
-// *d_boff on, which the caller zeroed; d_boff[1 .. n] and d_blen[0 .. n) are written.  d_tab: four u32[n] tables (the encoder's
-// sizes and statuses, the CRC-32 values, the stored flags).  The first non-zero encoder status lands in *d_status.
+// *d_boff on, which the caller zeroed; d_boff[1 .. n] and d_blen[0 .. n) are written.  The body's own tables are part of the caller's
+// layout (zmi_bgzf_tabs).  The first non-zero encoder status lands in *d_status.
+struct zmi_bgzf_tabs {
+    uint32_t *olen, *crc, *stored;
+    int32_t* st;
+    // the encoder's sizes and statuses, the blocks' CRC-32 values, the stored flags
+    void take(zmi_carver& k, size_t n) { k.take(n, olen, st, crc, stored); }
+};
 static int zmi_bgzf_body(zmi_ctx* c, const void* d_in, const uint64_t* d_off, const uint32_t* d_len, uint32_t n, uint32_t max_len, int level,
-                         int strategy, void* d_out, uint64_t out_cap, uint64_t* d_boff, uint32_t* d_blen, uint32_t* d_tab, int32_t* d_status,
+                         int strategy, void* d_out, uint64_t out_cap, uint64_t* d_boff, uint32_t* d_blen, const zmi_bgzf_tabs& tab, int32_t* d_status,
                          hipStream_t stream) {
     if (n == 0) return ZMI_E_OK;
-    uint32_t* d_olen = d_tab;
-    int32_t* d_st = (int32_t*)(d_tab + n);
-    uint32_t* d_crc = d_tab + 2u * (size_t)n;
-    uint32_t* d_stored = d_tab + 3u * (size_t)n;
-    // launch groups: one group's output slots and the encoder's match scratch together stay within the scratch limit
+    uint32_t *const d_olen = tab.olen, *const d_crc = tab.crc, *const d_stored = tab.stored;
+    int32_t* const d_st = tab.st;
+    // (a block's slot is the batch encoder's bound, not the slot of a stream's piece)
     const uint64_t stride = zmi_deflate_bound(max_len, ZMI_WRAP_RAW);
-    const uint64_t match_per = ((((uint64_t)max_len + 63u) & ~63ull) ? (((uint64_t)max_len + 63u) & ~63ull) : 64u) * 4u;
-    uint64_t group = c->scratch_limit / (stride + match_per + match_per / 16u);
-    if (const char* gv = zmi_tune("ZMI_STREAM_GROUP")) if (atoll(gv) > 0) group = (uint64_t)atoll(gv);
-    if (group == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one block");
-    if (group > n) group = n;
-    int rc = zmi_reserve(c->sd_slots, (size_t)(group * stride));
+    zmi_group_plan plan;
+    int rc = zmi_plan_slots(c, n, max_len, stride, "scratch limit too small for one block", &plan);
     if (rc) return rc;
+    const uint64_t group = plan.group;
     rc = zmi_piece_checks(c, d_in, d_off, d_len, n, ZMI_WRAP_GZIP, d_crc, stream);
     if (rc) return rc;
     for (uint64_t first = 0; first < n; first += group) {
@@ -938,35 +996,32 @@ static int zmi_bgzf_body(zmi_ctx* c, const void* d_in, const uint64_t* d_off, co
     return ZMI_E_OK;
 }
 
-static int zmi_bgzf_check_args(int& level, int strategy) {
-    if (level == -1) level = 6;
-    if (level < 0 || level > 9) return zmi_fail(ZMI_E_ARG, "level must be -1..9");
-    if (strategy < 0 || strategy > 4) return zmi_fail(ZMI_E_ARG, "strategy must be 0..4");
-    return ZMI_E_OK;
-}
-
 extern "C" int zmi_bgzf_blocks_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n,
                                    uint32_t max_len, int level, int strategy, void* d_out, uint64_t out_cap, uint64_t* d_block_off,
                                    uint32_t* d_block_len, int32_t* d_status, void* stream_) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (max_len > ZMI_BGZF_BLOCK_MAX) return zmi_fail(ZMI_E_ARG, "zmi_bgzf_blocks_dev: max_len must be <= ZMI_BGZF_BLOCK_MAX");
-    int rc = zmi_bgzf_check_args(level, strategy);
+    int rc = zmi_check_level_strategy(level, strategy);
     if (rc) return rc;
     if (!d_block_off || !d_status || (out_cap && !d_out) || (n && (!d_in_off || !d_in_len || (max_len && !d_in))))
         return zmi_fail(ZMI_E_ARG, "null argument");
     if (n > 0x7FFFFFFFu) return zmi_fail(ZMI_E_ARG, "zmi_bgzf_blocks_dev: more than 2^31 - 1 blocks");
     hipStream_t stream = (hipStream_t)stream_;
     ZMI_ON_DEVICE(c);
-    // per-block tables: checked lengths u32 | block sizes u32 (unless the caller's table holds them) | the body's four
-    rc = zmi_reserve(c->sd_meta, (size_t)n * (d_block_len ? 20u : 24u) + 16u);
+    uint32_t *d_len, *d_blen;
+    zmi_bgzf_tabs tab;
+    rc = zmi_carve(c->sd_meta, [&](zmi_carver k) {
+        k.take(n, d_len);                            // the checked lengths
+        k.take_unless(d_block_len, n, d_blen);       // the block sizes (the caller's table holds them if there is one)
+        tab.take(k, n);
+        k.skip(16u);                                 // (spare: the reservation has always ended with it)
+        return k.end();
+    });
     if (rc) return rc;
-    uint32_t* d_len = (uint32_t*)c->sd_meta.p;
-    uint32_t* d_blen = d_block_len ? d_block_len : d_len + n;
-    uint32_t* d_tab = d_len + (size_t)n * (d_block_len ? 1u : 2u);
     ZMI_HIP(hipMemsetAsync(d_status, 0, 4, stream));
     ZMI_HIP(hipMemsetAsync(d_block_off, 0, 8, stream));
     zmi_launch_bgzf_lens(d_in_len, n, max_len, d_len, d_status, stream);
-    rc = zmi_bgzf_body(c, d_in, d_in_off, d_len, n, max_len, level, strategy, d_out, out_cap, d_block_off, d_blen, d_tab, d_status, stream);
+    rc = zmi_bgzf_body(c, d_in, d_in_off, d_len, n, max_len, level, strategy, d_out, out_cap, d_block_off, d_blen, tab, d_status, stream);
     if (rc) return rc;
     {
         zmi_scope_timer tm(c, ZMI_K_PACK, stream);
@@ -980,7 +1035,7 @@ extern "C" int zmi_bgzf_deflate_dev(zmi_ctx* c, const void* d_in, uint64_t n, ui
                                     uint64_t out_cap, uint64_t* d_out_len, uint64_t* d_block_off, int32_t* d_status, void* stream_) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (block_bytes == 0 || block_bytes > ZMI_BGZF_BLOCK_MAX) return zmi_fail(ZMI_E_ARG, "zmi_bgzf_deflate_dev: block_bytes must be 1 .. ZMI_BGZF_BLOCK_MAX");
-    int rc = zmi_bgzf_check_args(level, strategy);
+    int rc = zmi_check_level_strategy(level, strategy);
     if (rc) return rc;
     if ((n && !d_in) || (out_cap && !d_out) || !d_out_len || !d_status) return zmi_fail(ZMI_E_ARG, "null argument");
     const uint64_t nb64 = n / block_bytes + (n % block_bytes ? 1u : 0u);
@@ -988,21 +1043,24 @@ extern "C" int zmi_bgzf_deflate_dev(zmi_ctx* c, const void* d_in, uint64_t n, ui
     const uint32_t nb = (uint32_t)nb64;
     hipStream_t stream = (hipStream_t)stream_;
     ZMI_ON_DEVICE(c);
-    // per-block tables: in_off u64 | block offsets u64 [nb + 1] (unless the caller's index holds them) | in_len u32 | block sizes
-    // u32 | the body's four
-    const size_t own_off = d_block_off ? 0u : ((size_t)nb + 1u) * 8u;
-    rc = zmi_reserve(c->sd_meta, (size_t)nb * 8u + own_off + (size_t)nb * 24u + 16u);
+    uint64_t *d_off, *d_boff;
+    uint32_t *d_len, *d_blen;
+    zmi_bgzf_tabs tab;
+    rc = zmi_carve(c->sd_meta, [&](zmi_carver k) {
+        k.take(nb, d_off);                           // the blocks' places in d_in
+        k.take_unless(d_block_off, nb + 1u, d_boff); // ... in the file (the caller's index holds them if there is one)
+        k.take(nb, d_len);
+        k.take(nb, d_blen);                          // the block sizes
+        tab.take(k, nb);
+        k.skip(16u);                                 // (spare: the reservation has always ended with it)
+        return k.end();
+    });
     if (rc) return rc;
-    uint64_t* d_off = (uint64_t*)c->sd_meta.p;
-    uint64_t* d_boff = d_block_off ? d_block_off : d_off + nb;
-    uint32_t* d_len = (uint32_t*)((uint8_t*)c->sd_meta.p + (size_t)nb * 8u + own_off);
-    uint32_t* d_blen = d_len + nb;
-    uint32_t* d_tab = d_blen + nb;
     ZMI_HIP(hipMemsetAsync(d_status, 0, 4, stream));
     ZMI_HIP(hipMemsetAsync(d_boff, 0, 8, stream));   // where the first group's pack starts
     zmi_launch_piece_layout(n, block_bytes, nb, d_off, d_len, stream);
     const uint32_t max_len = n < block_bytes ? (uint32_t)n : block_bytes;
-    rc = zmi_bgzf_body(c, d_in, d_off, d_len, nb, max_len, level, strategy, d_out, out_cap, d_boff, d_blen, d_tab, d_status, stream);
+    rc = zmi_bgzf_body(c, d_in, d_off, d_len, nb, max_len, level, strategy, d_out, out_cap, d_boff, d_blen, tab, d_status, stream);
     if (rc) return rc;
     {
         zmi_scope_timer tm(c, ZMI_K_PACK, stream);
@@ -1031,8 +1089,8 @@ extern "C" int zmi_zip_write_dev(zmi_ctx* c, const void* d_in, const uint64_t* d
                                  uint32_t piece_bytes, int level, int strategy, uint64_t base, void* d_out, uint64_t out_cap,
                                  uint64_t* d_out_len, zmi_zip_entry* d_entries, zmi_zip_info* d_info, int32_t* d_status, void* stream_) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
-    if (piece_bytes == 0 || piece_bytes > (1u << 30)) return zmi_fail(ZMI_E_ARG, "piece_bytes must be 1 .. 2^30");
-    int rc = zmi_bgzf_check_args(level, strategy);
+    int rc = zmi_check_piece_bytes(piece_bytes);
+    if (!rc) rc = zmi_check_level_strategy(level, strategy);
     if (rc) return rc;
     if (n > 0x7FFFFFFFu) return zmi_fail(ZMI_E_ARG, "zmi_zip_write_dev: more than 2^31 - 1 entries");
     if (!d_out_len || !d_status || (out_cap && !d_out) || (n && (!d_in_off || !d_in_len || !d_name_off || (in_bytes && !d_in))))
@@ -1043,54 +1101,40 @@ extern "C" int zmi_zip_write_dev(zmi_ctx* c, const void* d_in, const uint64_t* d
     hipStream_t stream = (hipStream_t)stream_;
     ZMI_ON_DEVICE(c);
 
-    // launch groups: one group's output slots and the encoder's match scratch together stay within the scratch limit.  A slot holds a
-    // piece of max_len = min(piece_bytes, in_bytes) bytes in the regions of a piece_bytes shard (zmi_deflate_impl, geom_len): those of
-    // zmi_deflate_pieces_stride(max_len), more only where sixteen regions' worst cases do not fit that (pieces of a few KiB)
+    // A slot holds a piece of max_len = min(piece_bytes, in_bytes) bytes in the regions of a piece_bytes shard.  Level 0 has no slots:
+    // the pieces are copied as they stand, in one group.  (No entries: no pieces, no group; what follows writes the end record alone.)
     const uint32_t max_len = in_bytes < piece_bytes ? (uint32_t)in_bytes : piece_bytes;
-    uint64_t stride = 0, group = np;
+    uint64_t stride = 0;
+    zmi_group_plan plan;
     if (level != 0) {
-        const uint32_t regions = zmi_enc_regions(piece_bytes, zmi_deflate_pieces_stride(piece_bytes), 65536u, kLevels[level].tok, false);
-        const uint64_t hold = (uint64_t)regions * ((zmi_enc_region_worst(max_len, regions, kLevels[level].tok, false) + 15u) & ~15ull);
-        stride = zmi_deflate_pieces_stride(max_len);
-        if (stride < hold) stride = hold;
-        const uint64_t match_per = ((((uint64_t)max_len + 63u) & ~63ull) ? (((uint64_t)max_len + 63u) & ~63ull) : 64u) * 4u;
-        group = c->scratch_limit / (stride + match_per + match_per / 16u);
-    }
-    if (const char* gv = zmi_tune("ZMI_STREAM_GROUP")) if (atoll(gv) > 0) group = (uint64_t)atoll(gv);
-    if (np && group == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one piece");
-    if (group > np) group = np;   // (no entries: no pieces, no group; what follows writes the end record alone)
-    if (level != 0) {
-        rc = zmi_reserve(c->sd_slots, (size_t)(group * stride));
+        stride = zmi_piece_slot_stride(max_len, piece_bytes, level);
+        rc = zmi_plan_slots(c, np, max_len, stride, "scratch limit too small for one piece", &plan);
         if (rc) return rc;
+    } else {
+        plan = zmi_plan_groups_per(c->scratch_limit, zmi_group_override(), np, 0u);
     }
-    const uint32_t wpg = (uint32_t)((group + 31u) / 32u);                       // bitmap words per group
-    const uint64_t n_groups = group ? (np + group - 1u) / group : 0u;
-    const size_t bm_words = (size_t)(n_groups * wpg);
+    const uint64_t group = plan.group;
+    const uint32_t wpg = plan.wpg;
+    const size_t bm_words = plan.bm_words;
 
-    // tables, 36 bytes per entry and 40 bytes + 1 bit per piece: u64 first piece [n + 1] | central offsets [n + 1] | piece input
-    // offsets [np] | piece places [np + 1] | four words (the count that is listed; the sum of the lengths, u64) | u32 checked lengths,
-    // name lengths, piece counts, CRC-32 values, central sizes [n each] | piece lengths, holes, encoder sizes, statuses, CRC-32
-    // values, places' sizes [np each] | the bitmap
-    rc = zmi_reserve(c->sd_meta, ((size_t)n + 1u) * 16u + (size_t)np * 16u + 8u + 16u + (size_t)n * 20u + (size_t)np * 24u + bm_words * 4u + 16u);
+    uint64_t *d_first, *d_coff, *d_poff, *d_pos;
+    zmi_words4 neff;
+    uint32_t *d_elen, *d_nlen, *d_npc, *d_ecrc, *d_csz, *d_plen, *d_head, *d_olen, *d_pcrc, *d_psz, *d_ends;
+    int32_t* d_st;
+    rc = zmi_carve(c->sd_meta, [&](zmi_carver k) {
+        k.take(n + 1u, d_first, d_coff);                             // per entry: its first piece, its central record's offset
+        k.take(np, d_poff);                                          // per piece: its place in d_in
+        k.take(np + 1u, d_pos);                                      // ... and in the archive
+        k.take(neff);                                                // the count that is listed; the sum of the checked lengths (u64)
+        k.take(n, d_elen, d_nlen, d_npc, d_ecrc, d_csz);             // per entry: checked length, name length, pieces, CRC-32, central size
+        k.take(np, d_plen, d_head, d_olen, d_st, d_pcrc, d_psz);     // per piece: length, hole, encoder's size and status, CRC-32, place's size
+        k.take(bm_words, d_ends);                                    // the bitmap of the pieces that end an entry's stream
+        k.skip(16u);                                                 // (spare: the reservation has always ended with it)
+        return k.end();
+    });
     if (rc) return rc;
-    uint64_t* d_first = (uint64_t*)c->sd_meta.p;
-    uint64_t* d_coff = d_first + n + 1u;
-    uint64_t* d_poff = d_coff + n + 1u;
-    uint64_t* d_pos = d_poff + np;
-    uint32_t* d_neff = (uint32_t*)(d_pos + np + 1u);
-    uint64_t* d_sum = (uint64_t*)(d_neff + 2u);       // the sum of the checked lengths (zmi_zip_layout_kernel)
-    uint32_t* d_elen = d_neff + 4u;
-    uint32_t* d_nlen = d_elen + n;
-    uint32_t* d_npc = d_nlen + n;
-    uint32_t* d_ecrc = d_npc + n;
-    uint32_t* d_csz = d_ecrc + n;
-    uint32_t* d_plen = d_csz + n;
-    uint32_t* d_head = d_plen + np;
-    uint32_t* d_olen = d_head + np;
-    int32_t* d_st = (int32_t*)(d_olen + np);
-    uint32_t* d_pcrc = (uint32_t*)(d_st + np);
-    uint32_t* d_psz = d_pcrc + np;
-    uint32_t* d_ends = d_psz + np;
+    uint32_t* const d_neff = neff.w;
+    uint64_t* const d_sum = neff.upper64();
 
     ZMI_HIP(hipMemsetAsync(d_status, 0, 4, stream));
     ZMI_HIP(hipMemsetAsync(d_pos, 0, 8, stream));     // where the first group's pack starts
@@ -1405,8 +1449,8 @@ extern "C" int zmi_inflate_batch_packed_dev(zmi_ctx* c, const void* d_in, const 
                                             uint32_t* d_in_used, int32_t* d_detail, void* stream_) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (wrap < ZMI_WRAP_RAW || wrap > ZMI_WRAP_AUTO) return zmi_fail(ZMI_E_ARG, "wrap must be raw/zlib/gzip/auto");
-    if (out_align == 0u || out_align > 4096u || (out_align & (out_align - 1u)) != 0u)
-        return zmi_fail(ZMI_E_ARG, "out_align must be a power of two, 1 .. 4096");
+    int rc = zmi_check_out_align(out_align);
+    if (rc) return rc;
     const bool dict = d_dict != nullptr && dict_len != 0u;
     if (dict && wrap != ZMI_WRAP_RAW && wrap != ZMI_WRAP_ZLIB)
         return zmi_fail(ZMI_E_ARG, "a preset dictionary needs wrap raw or zlib (a gzip member has no dictionary field)");
@@ -1418,7 +1462,7 @@ extern "C" int zmi_inflate_batch_packed_dev(zmi_ctx* c, const void* d_in, const 
         return ZMI_E_OK;
     }
     if (!d_out_len || !d_status) return zmi_fail(ZMI_E_ARG, "d_out_len and d_status are required");
-    int rc = zmi_reserve(c->pk, (size_t)n * 8u);
+    rc = zmi_reserve(c->pk, (size_t)n * 8u);
     if (rc) return rc;
     uint32_t* d_size = (uint32_t*)c->pk.p;
     uint32_t* d_cap = d_size + n;
@@ -1458,26 +1502,27 @@ extern "C" int zmi_zip_inflate_dev(zmi_ctx* c, const void* d_in, uint64_t in_len
                                    const uint32_t* d_sel, uint32_t n_sel, uint32_t out_align, void* d_out, uint64_t out_cap,
                                    uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, void* stream_) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
-    if (out_align == 0u || out_align > 4096u || (out_align & (out_align - 1u)) != 0u)
-        return zmi_fail(ZMI_E_ARG, "out_align must be a power of two, 1 .. 4096");
+    int rc = zmi_check_out_align(out_align);
+    if (rc) return rc;
     if (!d_out_off) return zmi_fail(ZMI_E_ARG, "d_out_off is required");
     hipStream_t stream = (hipStream_t)stream_;
     ZMI_ON_DEVICE(c);
-    if (n_sel == 0) {
-        ZMI_HIP(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), stream));
-        return ZMI_E_OK;
-    }
-    if (!d_out_len || !d_status || !d_detail) return zmi_fail(ZMI_E_ARG, "d_out_len, d_status and d_detail are required");
+    bool done;
+    rc = zmi_empty_selection(n_sel, d_out_off, d_out_len, d_status, d_detail, stream, &done);
+    if (rc || done) return rc;
     if ((n_entries && !d_entries) || (in_len && !d_in) || (out_cap && !d_out)) return zmi_fail(ZMI_E_ARG, "null argument");
-    int rc = zmi_reserve(c->zip_sel, (size_t)n_sel * 32u);
+    uint64_t* d_in_off;
+    uint32_t *d_in_n, *d_size, *d_slen, *d_cap, *d_used, *d_crc;
+    rc = zmi_carve(c->zip_sel, [&](zmi_carver k) {
+        k.take(n_sel, d_in_off);     // the entry's first data byte
+        k.take(n_sel, d_in_n);       // csize of a deflated slot, 0 for every other
+        k.take(n_sel, d_size);       // usize of a readable slot: the plan's sizes
+        k.take(n_sel, d_slen);       // usize of a stored slot: the copy's lengths
+        k.take(n_sel, d_cap);        // the planned size where the region fits out_cap, else 0
+        k.take(n_sel, d_used, d_crc);
+        return k.end();
+    });
     if (rc) return rc;
-    uint64_t* d_in_off = (uint64_t*)c->zip_sel.p;                 // the entry's first data byte
-    uint32_t* d_in_n = (uint32_t*)(d_in_off + n_sel);            // csize of a deflated slot, 0 for every other
-    uint32_t* d_size = d_in_n + n_sel;                           // usize of a readable slot: the plan's sizes
-    uint32_t* d_slen = d_size + n_sel;                           // usize of a stored slot: the copy's lengths
-    uint32_t* d_cap = d_slen + n_sel;                            // the planned size where the region fits out_cap, else 0
-    uint32_t* d_used = d_cap + n_sel;
-    uint32_t* d_crc = d_used + n_sel;
     {
         zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
         zmi_launch_zip_prep(d_entries, n_entries, d_sel, n_sel, in_len, d_in_off, d_in_n, d_size, d_slen, stream);
@@ -1523,18 +1568,16 @@ extern "C" int zmi_png_decode_dev(zmi_ctx* c, const void* d_in, const uint64_t* 
                                   uint32_t n_images, const uint32_t* d_sel, uint32_t n_sel, uint32_t flags, uint32_t out_align, void* d_out,
                                   uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, void* stream_) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
-    if (out_align == 0u || out_align > 4096u || (out_align & (out_align - 1u)) != 0u)
-        return zmi_fail(ZMI_E_ARG, "out_align must be a power of two, 1 .. 4096");
+    int rc = zmi_check_out_align(out_align);
+    if (rc) return rc;
     if (flags & ~(ZMI_PNG_NATIVE16 | ZMI_PNG_NO_CRC)) return zmi_fail(ZMI_E_ARG, "unknown flag");
     if (!d_out_off) return zmi_fail(ZMI_E_ARG, "d_out_off is required");
     if (n_sel > 0x7FFFFFFFu) return zmi_fail(ZMI_E_ARG, "n_sel must be below 2^31");
     hipStream_t stream = (hipStream_t)stream_;
     ZMI_ON_DEVICE(c);
-    if (n_sel == 0) {
-        ZMI_HIP(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), stream));
-        return ZMI_E_OK;
-    }
-    if (!d_out_len || !d_status || !d_detail) return zmi_fail(ZMI_E_ARG, "d_out_len, d_status and d_detail are required");
+    bool done;
+    rc = zmi_empty_selection(n_sel, d_out_off, d_out_len, d_status, d_detail, stream, &done);
+    if (rc || done) return rc;
     if ((n_images && (!d_images || !d_in || !d_in_off || !d_in_len)) || (out_cap && !d_out)) return zmi_fail(ZMI_E_ARG, "null argument");
     if (out_cap > (1ull << 44)) return zmi_fail(ZMI_E_NOMEM, "out_cap sizes the scratch: give the room there is");
     // Everything is sized from out_cap and n_sel: no size of the input is known here.  Scanlines: 1 + row_bytes <= 2 * row_bytes, and
@@ -1544,29 +1587,30 @@ extern "C" int zmi_png_decode_dev(zmi_ctx* c, const void* d_in, const uint64_t* 
     // (the gather buffer is this call's own addition to what the decoder needs: it stays under the context's scratch limit)
     uint64_t gather_cap = 2ull * out_cap + (out_cap >> 3) + 1024ull * n + (64ull << 10);
     if (gather_cap > c->scratch_limit) gather_cap = c->scratch_limit;
-    const size_t tab_bytes = ((4u * n + 3u) * 8u + 13u * n * 4u + 255u) & ~(size_t)255u;
-    const size_t gather_at = tab_bytes, scan_at = (gather_at + gather_cap + 16u + 255u) & ~(size_t)255u;
-    int rc = zmi_reserve(c->png, scan_at + 16u + scan_cap + 16u);
+    uint64_t *d_goff, *d_soff, *d_item_off, *d_zin_off;
+    uint32_t *d_pix, *d_pcap, *d_ssz, *d_scap, *d_gsz, *d_gcap, *d_items, *d_fl, *d_zin_len, *d_slen, *d_sused;
+    int32_t *d_sst, *d_sdet;
+    uint8_t *d_gbuf, *d_sbuf;
+    rc = zmi_carve(c->png, [&](zmi_carver k) {
+        k.take(n + 1, d_goff);           // where the gathered stream of a slot stands (the plan over d_gsz)
+        k.take(n + 1, d_soff);           // ... its filtered scanlines (the decoder's own plan over d_ssz)
+        k.take(n + 1, d_item_off);       // the scan of d_items
+        k.take(n, d_zin_off);            // where the decoder reads the slot's zlib stream
+        k.take(n, d_pix);                // height * row_bytes of a readable slot, else 0
+        k.take(n, d_pcap);               // ... where the region fits out_cap, else 0
+        k.take(n, d_ssz, d_scap);        // (1 + row_bytes) * height of a slot that is decoded, else 0; its planned capacity
+        k.take(n, d_gsz, d_gcap);        // idat_bytes of a decoded slot with several IDAT chunks, else 0; its planned capacity
+        k.take(n, d_items);              // bands of 64 rows
+        k.take(n, d_fl, d_zin_len);      // PNG_FL_*: set by the walk and the unfilter; the zlib stream's length
+        k.take(n, d_slen, d_sused, d_sst, d_sdet);   // the decoder's words
+        k.align(256u);
+        k.take(gather_cap, d_gbuf);      // the gathered streams
+        k.skip(16u);
+        k.align(256u);
+        k.region(d_sbuf, scan_cap, 16u); // the filtered scanlines (the unfilter reads whole dwords around a row: 16 bytes of margin)
+        return k.end();
+    });
     if (rc) return rc;
-    uint64_t* d_goff = (uint64_t*)c->png.p;                      // where the gathered stream of a slot stands (the plan over d_gsz)
-    uint64_t* d_soff = d_goff + n + 1;                           // ... its filtered scanlines (the decoder's own plan over d_ssz)
-    uint64_t* d_item_off = d_soff + n + 1;                       // the scan of d_items
-    uint64_t* d_zin_off = d_item_off + n + 1;                    // where the decoder reads the slot's zlib stream
-    uint32_t* d_pix = (uint32_t*)(d_zin_off + n);                // height * row_bytes of a readable slot, else 0
-    uint32_t* d_pcap = d_pix + n;                                // ... where the region fits out_cap, else 0
-    uint32_t* d_ssz = d_pcap + n;                                // (1 + row_bytes) * height of a slot that is decoded, else 0
-    uint32_t* d_scap = d_ssz + n;
-    uint32_t* d_gsz = d_scap + n;                                // idat_bytes of a decoded slot with several IDAT chunks, else 0
-    uint32_t* d_gcap = d_gsz + n;
-    uint32_t* d_items = d_gcap + n;                              // bands of 64 rows
-    uint32_t* d_fl = d_items + n;                                // PNG_FL_*: set by the walk and the unfilter
-    uint32_t* d_zin_len = d_fl + n;
-    uint32_t* d_slen = d_zin_len + n;                            // the decoder's words
-    uint32_t* d_sused = d_slen + n;
-    int32_t* d_sst = (int32_t*)(d_sused + n);
-    int32_t* d_sdet = d_sst + n;
-    uint8_t* d_gbuf = (uint8_t*)c->png.p + gather_at;
-    uint8_t* d_sbuf = (uint8_t*)c->png.p + scan_at + 16u;        // (the unfilter reads whole dwords around a row: 16 bytes of margin)
     uint32_t split = 1u;
     if (const char* sv = zmi_tune("ZMI_PNG_SPLIT")) split = (uint32_t)atoi(sv);   // (the probe: a chain per image instead of per None / Sub row)
     {
@@ -1622,43 +1666,44 @@ extern "C" int zmi_tiff_read_dev(zmi_ctx* c, const void* d_in, uint64_t in_len, 
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (flags & ~ZMI_TIFF_ASSEMBLE) return zmi_fail(ZMI_E_ARG, "unknown flag");
     const uint32_t assemble = (flags & ZMI_TIFF_ASSEMBLE) ? 1u : 0u;
-    if (!assemble && (out_align == 0u || out_align > 4096u || (out_align & (out_align - 1u)) != 0u))
-        return zmi_fail(ZMI_E_ARG, "out_align must be a power of two, 1 .. 4096");
+    int rc = assemble ? ZMI_E_OK : zmi_check_out_align(out_align);
+    if (rc) return rc;
     if (!d_out_off) return zmi_fail(ZMI_E_ARG, "d_out_off is required");
     if (n_sel > 0x7FFFFFFFu) return zmi_fail(ZMI_E_ARG, "n_sel must be below 2^31");
     hipStream_t stream = (hipStream_t)stream_;
     ZMI_ON_DEVICE(c);
-    if (n_sel == 0) {
-        ZMI_HIP(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), stream));
-        return ZMI_E_OK;
-    }
-    if (!d_out_len || !d_status || !d_detail) return zmi_fail(ZMI_E_ARG, "d_out_len, d_status and d_detail are required");
+    bool done;
+    rc = zmi_empty_selection(n_sel, d_out_off, d_out_len, d_status, d_detail, stream, &done);
+    if (rc || done) return rc;
     if ((n_pages && !d_pages) || (in_len && !d_in) || (out_cap && !d_out)) return zmi_fail(ZMI_E_ARG, "null argument");
     if (decoded_bytes > (1ull << 44)) return zmi_fail(ZMI_E_NOMEM, "decoded_bytes sizes the scratch: give the sum there is");
     // The still-predicted segments stand in scratch, every one at a multiple of 16 (the decoder's own plan over d_ssz), 16 bytes of
     // margin on either side: the unpredict stages whole dwords around a row.
     const size_t n = n_sel;
     const uint64_t scan_cap = decoded_bytes + 16ull * n + 64ull;
-    const size_t tab_bytes = ((4u * n + 3u) * 8u + 14u * n * 4u + 255u) & ~(size_t)255u;
-    int rc = zmi_reserve(c->tiff, tab_bytes + 16u + scan_cap + 16u);
+    uint64_t *d_soff, *d_item_off, *d_pix_off, *d_zin_off;
+    uint32_t *d_pix, *d_pcap, *d_ssz, *d_scap, *d_zin_len, *d_rawlen, *d_items, *d_fl, *d_slen, *d_sused;
+    int32_t *d_sst, *d_sdet;
+    uint8_t* d_sbuf;
+    rc = zmi_carve(c->tiff, [&](zmi_carver k) {
+        k.take(n + 1, d_soff);           // where the segment of a slot stands in scratch (the decoder's plan over d_ssz)
+        k.take(n + 1, d_item_off);       // the scan of d_items
+        k.take(n + 1, d_pix_off);        // the scan of d_pix: its last word is the sum decoded_bytes bounds
+        k.take(n, d_zin_off);            // the segment's place in the file
+        k.take(n, d_pix);                // the decoded size of a slot that reads a segment, else 0
+        k.take(n, d_pcap);               // ... where its region fits out_cap, else 0
+        k.take(n, d_ssz, d_scap);        // ... where its bytes are fetched: not sparse, inside the file; its planned capacity
+        k.take(n, d_zin_len);            // the byte count of a deflated slot
+        k.take(n, d_rawlen);             // the bytes to copy for a slot of compression 1
+        k.take(n, d_items);              // groups of TIFF_ROWS rows
+        k.take(n, d_fl);                 // TIFF_FL_*
+        k.take(n, d_slen, d_sused, d_sst, d_sdet);   // the decoder's words
+        k.skip(8u * n);                  // (spare: the reservation has always counted two tables more than there are)
+        k.align(256u);
+        k.region(d_sbuf, scan_cap, 16u); // the still-predicted segments
+        return k.end();
+    });
     if (rc) return rc;
-    uint64_t* d_soff = (uint64_t*)c->tiff.p;                      // where the segment of a slot stands in scratch (the decoder's plan over d_ssz)
-    uint64_t* d_item_off = d_soff + n + 1;                       // the scan of d_items
-    uint64_t* d_pix_off = d_item_off + n + 1;                    // the scan of d_pix: its last word is the sum decoded_bytes bounds
-    uint64_t* d_zin_off = d_pix_off + n + 1;                     // the segment's place in the file
-    uint32_t* d_pix = (uint32_t*)(d_zin_off + n);                // the decoded size of a slot that reads a segment, else 0
-    uint32_t* d_pcap = d_pix + n;                                // ... where its region fits out_cap, else 0
-    uint32_t* d_ssz = d_pcap + n;                                // ... where its bytes are fetched: not sparse, inside the file
-    uint32_t* d_scap = d_ssz + n;
-    uint32_t* d_zin_len = d_scap + n;                            // the byte count of a deflated slot
-    uint32_t* d_rawlen = d_zin_len + n;                          // the bytes to copy for a slot of compression 1
-    uint32_t* d_items = d_rawlen + n;                            // groups of TIFF_ROWS rows
-    uint32_t* d_fl = d_items + n;                                // TIFF_FL_*
-    uint32_t* d_slen = d_fl + n;                                 // the decoder's words
-    uint32_t* d_sused = d_slen + n;
-    int32_t* d_sst = (int32_t*)(d_sused + n);
-    int32_t* d_sdet = d_sst + n;
-    uint8_t* d_sbuf = (uint8_t*)c->tiff.p + tab_bytes + 16u;
     const uint8_t* in = (const uint8_t*)d_in;
     {
         zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
@@ -1715,17 +1760,15 @@ extern "C" int zmi_exr_read_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_
                                 uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, void* stream_) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
     if (flags != 0u) return zmi_fail(ZMI_E_ARG, "unknown flag");
-    if (out_align == 0u || out_align > 4096u || (out_align & (out_align - 1u)) != 0u)
-        return zmi_fail(ZMI_E_ARG, "out_align must be a power of two, 1 .. 4096");
+    int rc = zmi_check_out_align(out_align);
+    if (rc) return rc;
     if (!d_out_off) return zmi_fail(ZMI_E_ARG, "d_out_off is required");
     if (n_sel > 0x7FFFFFFFu || chunk_cap > 0x7FFFFFFFu) return zmi_fail(ZMI_E_ARG, "n_sel and chunk_cap must be below 2^31");
     hipStream_t stream = (hipStream_t)stream_;
     ZMI_ON_DEVICE(c);
-    if (n_sel == 0) {
-        ZMI_HIP(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), stream));
-        return ZMI_E_OK;
-    }
-    if (!d_out_len || !d_status || !d_detail) return zmi_fail(ZMI_E_ARG, "d_out_len, d_status and d_detail are required");
+    bool done;
+    rc = zmi_empty_selection(n_sel, d_out_off, d_out_len, d_status, d_detail, stream, &done);
+    if (rc || done) return rc;
     if ((n_files && (!d_images || !d_channels || !d_in || !d_in_off || !d_in_len)) || (out_cap && !d_out)) return zmi_fail(ZMI_E_ARG, "null argument");
     if (decoded_bytes > (1ull << 40)) return zmi_fail(ZMI_E_NOMEM, "decoded_bytes sizes the scratch: give the sum there is");
     // The inflated chunks stand in scratch, every one at a multiple of 16 (the decoder's own plan over d_csz), 16 bytes of margin at
@@ -1733,36 +1776,38 @@ extern "C" int zmi_exr_read_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_
     const size_t n = n_sel, cc = chunk_cap;
     const uint64_t nblk = decoded_bytes / 1024u + cc;                 // (EXR_BLOCK: every chunk ends with at most one short block)
     const uint64_t scan_cap = decoded_bytes + 16ull * cc + 64ull;
-    const size_t tab_bytes = ((2u * (n + 1u) + 4u * (cc + 1u)) * 8u + (6u * n + 12u * cc + 2u * nblk) * 4u + 255u) & ~(size_t)255u;
-    int rc = zmi_reserve(c->exr, tab_bytes + 16u + scan_cap + 16u);
+    uint64_t *d_ch_off, *d_raw_off, *d_soff, *d_item_off, *d_blk_off, *d_zin_off;
+    uint32_t *d_size, *d_pcap, *d_nch, *d_rawb, *d_kind, *d_live;
+    uint32_t *d_zin_len, *d_csz, *d_scap, *d_rawlen, *d_fl, *d_items, *d_nblk, *d_cslot, *d_slen, *d_sused, *d_bsum, *d_bpre;
+    int32_t *d_sst, *d_sdet;
+    uint8_t* d_sbuf;
+    rc = zmi_carve(c->exr, [&](zmi_carver k) {
+        k.take(n + 1, d_ch_off);         // the scan of d_nch: the chunks of slot j are d_ch_off[j] .. d_ch_off[j + 1)
+        k.take(n + 1, d_raw_off);        // the scan of d_rawb: what decoded_bytes bounds
+        k.take(cc + 1, d_soff);          // where a chunk stands in scratch (the decoder's plan over d_csz)
+        k.take(cc + 1, d_item_off);      // the scan of d_items
+        k.take(cc + 1, d_blk_off);       // the scan of d_nblk
+        k.take(cc + 1, d_zin_off);       // the chunk's data in d_in
+        k.take(n, d_size);               // per slot: the region of a readable file, else 0
+        k.take(n, d_pcap);               // ... where it fits out_cap, else 0
+        k.take(n, d_nch);                // its chunks
+        k.take(n, d_rawb);               // its raw bytes
+        k.take(n, d_kind, d_live);
+        k.take(cc, d_zin_len);           // per chunk: dataSize of a compressed chunk
+        k.take(cc, d_csz, d_scap);       // the raw size n of a chunk whose header is right; its planned capacity
+        k.take(cc, d_rawlen);            // n of a chunk stored raw: the copy's length
+        k.take(cc, d_fl);                // EXR_FL_*
+        k.take(cc, d_items);             // the pieces of the chunk's runs
+        k.take(cc, d_nblk);              // the blocks of byte sums of a compressed chunk
+        k.take(cc, d_cslot);             // the chunk's slot
+        k.take(cc, d_slen, d_sused, d_sst, d_sdet);   // the decoder's words
+        k.take(nblk, d_bsum);            // one byte sum per block
+        k.take(nblk, d_bpre);            // ... and the sums in front of it inside its chunk
+        k.align(256u);
+        k.region(d_sbuf, scan_cap, 16u); // the inflated chunks
+        return k.end();
+    });
     if (rc) return rc;
-    uint64_t* d_ch_off = (uint64_t*)c->exr.p;                    // the scan of d_nch: the chunks of slot j are d_ch_off[j] .. d_ch_off[j + 1)
-    uint64_t* d_raw_off = d_ch_off + n + 1;                      // the scan of d_rawb: what decoded_bytes bounds
-    uint64_t* d_soff = d_raw_off + n + 1;                        // where a chunk stands in scratch (the decoder's plan over d_csz)
-    uint64_t* d_item_off = d_soff + cc + 1;                      // the scan of d_items
-    uint64_t* d_blk_off = d_item_off + cc + 1;                   // the scan of d_nblk
-    uint64_t* d_zin_off = d_blk_off + cc + 1;                    // the chunk's data in d_in
-    uint32_t* d_size = (uint32_t*)(d_zin_off + cc + 1);          // per slot: the region of a readable file, else 0
-    uint32_t* d_pcap = d_size + n;                               // ... where it fits out_cap, else 0
-    uint32_t* d_nch = d_pcap + n;                                // its chunks
-    uint32_t* d_rawb = d_nch + n;                                // its raw bytes
-    uint32_t* d_kind = d_rawb + n;
-    uint32_t* d_live = d_kind + n;
-    uint32_t* d_zin_len = d_live + n;                            // per chunk: dataSize of a compressed chunk
-    uint32_t* d_csz = d_zin_len + cc;                            // the raw size n of a chunk whose header is right
-    uint32_t* d_scap = d_csz + cc;
-    uint32_t* d_rawlen = d_scap + cc;                            // n of a chunk stored raw: the copy's length
-    uint32_t* d_fl = d_rawlen + cc;                              // EXR_FL_*
-    uint32_t* d_items = d_fl + cc;                               // the pieces of the chunk's runs
-    uint32_t* d_nblk = d_items + cc;                             // the blocks of byte sums of a compressed chunk
-    uint32_t* d_cslot = d_nblk + cc;                             // the chunk's slot
-    uint32_t* d_slen = d_cslot + cc;                             // the decoder's words
-    uint32_t* d_sused = d_slen + cc;
-    int32_t* d_sst = (int32_t*)(d_sused + cc);
-    int32_t* d_sdet = d_sst + cc;
-    uint32_t* d_bsum = (uint32_t*)(d_sdet + cc);                 // one byte sum per block
-    uint32_t* d_bpre = d_bsum + nblk;                            // ... and the sums in front of it inside its chunk
-    uint8_t* d_sbuf = (uint8_t*)c->exr.p + tab_bytes + 16u;
     const uint8_t* in = (const uint8_t*)d_in;
     {
         zmi_scope_timer tm(c, ZMI_K_PARSE, stream);
@@ -1826,11 +1871,10 @@ extern "C" int zmi_png_encode_dev(zmi_ctx* c, const void* d_in, const uint64_t* 
                                   uint32_t out_align, void* d_out, uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_out_len,
                                   zmi_png_image* d_written, int32_t* d_status, void* stream_) {
     if (!c) return zmi_fail(ZMI_E_ARG, "null context");
-    if (piece_bytes == 0 || piece_bytes > (1u << 30)) return zmi_fail(ZMI_E_ARG, "piece_bytes must be 1 .. 2^30");
-    int rc = zmi_bgzf_check_args(level, strategy);
+    int rc = zmi_check_piece_bytes(piece_bytes);
+    if (!rc) rc = zmi_check_level_strategy(level, strategy);
+    if (!rc) rc = zmi_check_out_align(out_align);
     if (rc) return rc;
-    if (out_align == 0u || out_align > 4096u || (out_align & (out_align - 1u)) != 0u)
-        return zmi_fail(ZMI_E_ARG, "out_align must be a power of two, 1 .. 4096");
     if (flags & ~ZMI_PNG_NATIVE16) return zmi_fail(ZMI_E_ARG, "unknown flag");
     if (filter > ZMI_PNG_FILTER_ADAPTIVE) return zmi_fail(ZMI_E_ARG, "filter must be 0 .. 4 or ZMI_PNG_FILTER_ADAPTIVE");
     if (n > 0x7FFFFFFFu) return zmi_fail(ZMI_E_ARG, "zmi_png_encode_dev: more than 2^31 - 1 images");
@@ -1848,56 +1892,40 @@ extern "C" int zmi_png_encode_dev(zmi_ctx* c, const void* d_in, const uint64_t* 
         return ZMI_E_OK;
     }
 
-    // launch groups and slots: as zmi_zip_write_dev, at every level (level 0 is deflate stored blocks from the same encoder)
+    // launch groups and slots: zmi_zip_write_dev's, at every level (level 0 is deflate stored blocks from the same encoder)
     const uint32_t max_len = scan_bytes < piece_bytes ? (uint32_t)scan_bytes : piece_bytes;
-    const uint32_t regions = zmi_enc_regions(piece_bytes, zmi_deflate_pieces_stride(piece_bytes), 65536u, kLevels[level].tok, false);
-    const uint64_t hold = (uint64_t)regions * ((zmi_enc_region_worst(max_len, regions, kLevels[level].tok, false) + 15u) & ~15ull);
-    uint64_t stride = zmi_deflate_pieces_stride(max_len);
-    if (stride < hold) stride = hold;
-    const uint64_t match_per = ((((uint64_t)max_len + 63u) & ~63ull) ? (((uint64_t)max_len + 63u) & ~63ull) : 64u) * 4u;
-    uint64_t group = c->scratch_limit / (stride + match_per + match_per / 16u);
-    if (const char* gv = zmi_tune("ZMI_STREAM_GROUP")) if (atoll(gv) > 0) group = (uint64_t)atoll(gv);
-    if (group == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one piece");
-    if (group > np) group = np;
-    rc = zmi_reserve(c->sd_slots, (size_t)(group * stride));
+    const uint64_t stride = zmi_piece_slot_stride(max_len, piece_bytes, level);
+    zmi_group_plan plan;
+    rc = zmi_plan_slots(c, np, max_len, stride, "scratch limit too small for one piece", &plan);
     if (rc) return rc;
-    const uint32_t wpg = (uint32_t)((group + 31u) / 32u);                       // bitmap words per group
-    const uint64_t n_groups = (np + group - 1u) / group;
-    const size_t bm_words = (size_t)(n_groups * wpg);
+    const uint64_t group = plan.group;
+    const uint32_t wpg = plan.wpg;
+    const size_t bm_words = plan.bm_words;
 
-    // tables, 48 bytes per image and 40 bytes + 1 bit per place, 12 bytes per slot of a group: u64 first piece, scanline offset, first item
-    // [n + 1 each] | piece offsets in the scanlines [np] | piece places [np + 1] | slot offsets [group] | four words (the count that is
-    // valid; the sum of the scanline sizes, u64) | u32 scanline sizes, hole lengths, piece counts, bands, Adler-32, CRC-32 [n each] |
-    // piece lengths, holes, encoder sizes, statuses, Adler-32, CRC-32 [np each] | a table the slot layout fills [group] | the bitmap;
-    // then the scanlines, 64 bytes clear of either end
-    const size_t tab_bytes = (((size_t)n + 1u) * 24u + (size_t)np * 16u + 8u + (size_t)group * 8u + 16u + (size_t)n * 24u + (size_t)np * 24u +
-                              (size_t)group * 4u + bm_words * 4u + 16u + 255u) & ~(size_t)255u;
-    rc = zmi_reserve(c->png, tab_bytes + 64u + (size_t)scan_bytes + 64u);
+    uint64_t *d_first, *d_soff, *d_item_off, *d_poff, *d_pos, *d_slot_off;
+    zmi_words4 neff;
+    uint32_t *d_ssz, *d_nlen, *d_npc, *d_bands, *d_iadler, *d_icrc, *d_plen, *d_head, *d_olen, *d_padler, *d_pcrc, *d_slot_len, *d_ends;
+    int32_t* d_st;
+    uint8_t* d_scan;
+    rc = zmi_carve(c->png, [&](zmi_carver k) {
+        k.take(n + 1u, d_first, d_soff, d_item_off);                     // per image: its first piece, scanline offset, first band
+        k.take(np, d_poff);                                              // per piece: its place in the scanlines
+        k.take(np + 1u, d_pos);                                          // ... and in d_out
+        k.take(group, d_slot_off);                                       // the slots of a group
+        k.take(neff);                                                    // the count that is valid; the sum of the scanline sizes (u64)
+        k.take(n, d_ssz, d_nlen, d_npc, d_bands, d_iadler, d_icrc);      // per image: scanline size, hole, pieces, bands, Adler-32, CRC-32
+        k.take(np, d_plen, d_head, d_olen, d_st, d_padler, d_pcrc);      // per piece: length, hole, encoder's size and status, Adler-32, CRC-32
+        k.take(group, d_slot_len);                                       // a table the slot layout fills
+        k.take(bm_words, d_ends);                                        // the bitmap of the pieces that end an image's stream
+        k.skip(16u);                                                     // (spare: the reservation has always had it)
+        k.align(256u);
+        k.region(d_scan, scan_bytes, 64u);                               // the filtered scanlines
+        return k.end();
+    });
     if (rc) return rc;
-    uint64_t* d_first = (uint64_t*)c->png.p;
-    uint64_t* d_soff = d_first + n + 1u;
-    uint64_t* d_item_off = d_soff + n + 1u;
-    uint64_t* d_poff = d_item_off + n + 1u;
-    uint64_t* d_pos = d_poff + np;
-    uint64_t* d_slot_off = d_pos + np + 1u;
-    uint32_t* d_neff = (uint32_t*)(d_slot_off + group);
-    uint64_t* d_sum = (uint64_t*)(d_neff + 2u);       // the sum of the scanline sizes (zmi_png_wlayout_kernel)
-    uint32_t* d_ssz = d_neff + 4u;
-    uint32_t* d_nlen = d_ssz + n;
-    uint32_t* d_npc = d_nlen + n;
-    uint32_t* d_bands = d_npc + n;
-    uint32_t* d_iadler = d_bands + n;
-    uint32_t* d_icrc = d_iadler + n;
-    uint32_t* d_plen = d_icrc + n;
-    uint32_t* d_head = d_plen + np;
-    uint32_t* d_olen = d_head + np;
-    int32_t* d_st = (int32_t*)(d_olen + np);
-    uint32_t* d_padler = (uint32_t*)(d_st + np);
-    uint32_t* d_pcrc = d_padler + np;
-    uint32_t* d_slot_len = d_pcrc + np;
-    uint32_t* d_ends = d_slot_len + group;
-    int32_t* d_call = (int32_t*)(d_neff + 1u);        // the pieces kernel's call-wide status word: the slots carry that here
-    uint8_t* d_scan = (uint8_t*)c->png.p + tab_bytes + 64u;
+    uint32_t* const d_neff = neff.w;
+    uint64_t* const d_sum = neff.upper64();             // (zmi_png_wlayout_kernel)
+    int32_t* const d_call = (int32_t*)neff.word(1);     // (the slots carry the pieces kernel's status here)
 
     ZMI_HIP(hipMemsetAsync(d_pos, 0, 8, stream));     // where the first group's pack starts
     ZMI_HIP(hipMemsetAsync(d_neff, 0, 16, stream));
@@ -2112,48 +2140,41 @@ extern "C" int zmi_tiff_write_dev(zmi_ctx* c, const zmi_tiff_write* w, const voi
     hipStream_t stream = (hipStream_t)stream_;
     ZMI_ON_DEVICE(c);
 
-    // launch groups and slots: as zmi_png_encode_dev, but the host knows the longest piece there is -- a full segment, or piece_bytes
+    // launch groups and slots: zmi_png_encode_dev's, but the host knows the longest piece there is -- a full segment, or piece_bytes
     // where that is less -- so slots and match scratch follow the segments (a 192 KiB tile under piece_bytes of 1 MiB takes a fifth of
     // what a 1 MiB piece would) while geom_len = piece_bytes keeps the bytes those of pieces of piece_bytes
     const uint32_t max_len = g.seg_bytes < piece_bytes ? g.seg_bytes : piece_bytes;
-    const uint32_t regions = zmi_enc_regions(piece_bytes, zmi_deflate_pieces_stride(piece_bytes), 65536u, kLevels[level].tok, false);
-    const uint64_t hold = (uint64_t)regions * ((zmi_enc_region_worst(max_len, regions, kLevels[level].tok, false) + 15u) & ~15ull);
-    uint64_t stride = zmi_deflate_pieces_stride(max_len);
-    if (stride < hold) stride = hold;
-    const uint64_t match_per = ((((uint64_t)max_len + 63u) & ~63ull) ? (((uint64_t)max_len + 63u) & ~63ull) : 64u) * 4u;
-    uint64_t group = c->scratch_limit / (stride + match_per + match_per / 16u);
-    if (const char* gv = zmi_tune("ZMI_STREAM_GROUP")) if (atoll(gv) > 0) group = (uint64_t)atoll(gv);
-    if (group == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one piece");
-    if (group > np) group = np;
-    int rc = zmi_reserve(c->sd_slots, (size_t)(group * stride));
+    const uint64_t stride = zmi_piece_slot_stride(max_len, piece_bytes, level);
+    zmi_group_plan plan;
+    int rc = zmi_plan_slots(c, np, max_len, stride, "scratch limit too small for one piece", &plan);
     if (rc) return rc;
-    const uint32_t wpg = (uint32_t)((group + 31u) / 32u);                       // bitmap words per group
-    const uint64_t n_groups = (np + group - 1u) / group;
-    const size_t bm_words = (size_t)(n_groups * wpg);
+    const uint64_t group = plan.group;
+    const uint32_t wpg = plan.wpg;
+    const size_t bm_words = plan.bm_words;
 
-    // tables: u64 first piece [n + 1] | piece offsets in the scratch [np] | piece places [np + 1] | slot offsets [group] | four words
-    // (the segments that are live: all; the first segment with a status) | u32 Adler-32 per segment [n] | piece lengths, holes, encoder
-    // sizes, statuses, Adler-32 [np each] | a table the slot layout fills [group] | the bitmap; then the predicted segments, every one
-    // at a multiple of 16, 64 bytes clear of either end
-    const size_t tab_bytes = (((size_t)n + 1u) * 8u + (size_t)np * 16u + 8u + (size_t)group * 8u + 16u + (size_t)n * 4u + (size_t)np * 20u +
-                              (size_t)group * 4u + bm_words * 4u + 16u + 255u) & ~(size_t)255u;
-    rc = zmi_reserve(c->tiff_w, tab_bytes + 64u + (size_t)n * g.ss + 64u);
+    uint64_t *d_first, *d_poff, *d_pos, *d_slot_off;
+    zmi_words4 neff;
+    uint32_t *d_sadler, *d_plen, *d_head, *d_olen, *d_padler, *d_slot_len, *d_ends;
+    int32_t* d_st;
+    uint8_t* d_scan;
+    rc = zmi_carve(c->tiff_w, [&](zmi_carver k) {
+        k.take(n + 1u, d_first);         // per segment: its first piece
+        k.take(np, d_poff);              // per piece: its place in the scratch
+        k.take(np + 1u, d_pos);          // ... in d_out
+        k.take(group, d_slot_off);       // the slots of a group
+        k.take(neff);                    // the segments that are live: all | the first segment with a status
+        k.take(n, d_sadler);             // per segment: the Adler-32
+        k.take(np, d_plen, d_head, d_olen, d_st, d_padler);   // per piece: length, hole, encoder's size and status, Adler-32
+        k.take(group, d_slot_len);       // a table the slot layout fills
+        k.take(bm_words, d_ends);        // the bitmap of the pieces that end a segment's stream
+        k.skip(16u);                     // (spare: the reservation has always had it)
+        k.align(256u);
+        k.region(d_scan, (size_t)n * g.ss, 64u);   // the predicted segments, every one at a multiple of 16
+        return k.end();
+    });
     if (rc) return rc;
-    uint64_t* d_first = (uint64_t*)c->tiff_w.p;
-    uint64_t* d_poff = d_first + n + 1u;
-    uint64_t* d_pos = d_poff + np;
-    uint64_t* d_slot_off = d_pos + np + 1u;
-    uint32_t* d_neff = (uint32_t*)(d_slot_off + group);
-    uint32_t* d_bad = d_neff + 1u;
-    uint32_t* d_sadler = d_neff + 4u;
-    uint32_t* d_plen = d_sadler + n;
-    uint32_t* d_head = d_plen + np;
-    uint32_t* d_olen = d_head + np;
-    int32_t* d_st = (int32_t*)(d_olen + np);
-    uint32_t* d_padler = (uint32_t*)(d_st + np);
-    uint32_t* d_slot_len = d_padler + np;
-    uint32_t* d_ends = d_slot_len + group;
-    uint8_t* d_scan = (uint8_t*)c->tiff_w.p + tab_bytes + 64u;
+    uint32_t* const d_neff = neff.w;
+    uint32_t* const d_bad = neff.word(1);
 
     ZMI_HIP(hipMemsetAsync(d_bad, 0xFF, 4, stream));
     ZMI_HIP(hipMemsetAsync(d_ends, 0, bm_words * 4u, stream));
@@ -2338,35 +2359,48 @@ static int zmi_split_core(zmi_ctx* c, const uint8_t* in, uint32_t in_len, uint32
         sbit[j] = j == 0u ? in_bit : (seg_bit ? seg_bit[j] : 0u);
     }
     if (scratch > (3ull << 30)) return zmi_inflate_resume(c, in, in_len, in_bit, hist, hist_len, out, out_cap, out_len, status, detail, in_used, resume);
-    // meta: ioff u64[n] | ooff u64[n] | soff u64[n + 1] | ilen | ocap | hist | bit | olen | status | used | detail (u32[n] each) | resume u32[4n] | one_off u64, one_len u32, err u32
+    // (olen .. res travel back in one copy, `one` goes out in one: consecutive takes of one width are contiguous)
     const size_t n = nseg;
-    const size_t o_ioff = 0, o_ooff = 8 * n, o_soff = 16 * n, o_ilen = 24 * n + 8, o_ocap = o_ilen + 4 * n, o_hist = o_ocap + 4 * n, o_bit = o_hist + 4 * n,
-                 o_olen = o_bit + 4 * n, o_st = o_olen + 4 * n, o_used = o_st + 4 * n, o_det = o_used + 4 * n, o_res = o_det + 4 * n, o_one = ((o_res + 16 * n) + 7) & ~(size_t)7,
-                 meta_bytes = o_one + 32;
+    uint64_t *d_ioff, *d_ooff, *d_soff, *d_one_off;
+    uint32_t *d_ilen, *d_ocap, *d_hist, *d_bit, *d_olen, *d_used, *d_res, *d_one_len, *d_one_err;
+    int32_t *d_st, *d_det;
+    const auto meta = [&](zmi_carver k) {
+        k.take(n, d_ioff, d_ooff);
+        k.take(n + 1, d_soff);                             // where the segments' outputs go in the stitch
+        k.take(n, d_ilen, d_ocap, d_hist, d_bit);          // what the host lays out
+        k.take(n, d_olen, d_st, d_used, d_det);            // what the decode leaves
+        k.take(4 * n, d_res);
+        k.take(1, d_one_off);                              // the stitched output as one stream for the jump resolve
+        k.take(1, d_one_len, d_one_err);
+        k.skip(16u);                                       // (spare: the reservation has always ended with it)
+        return k.end();
+    };
+    const size_t meta_bytes = meta(zmi_carver());
     int rc = zmi_reserve(c->st_in, (size_t)in_len + 64u);
     if (!rc) rc = zmi_reserve(c->st_out, base + (size_t)out_cap + 64u);
-    if (!rc) rc = zmi_reserve(c->st_meta, meta_bytes);
+    if (!rc) rc = zmi_carve(c->st_meta, meta);
     if (!rc) rc = zmi_reserve(c->sp_out, (size_t)scratch + 64u);
     if (rc) return rc;
     hipStream_t hs = c->host_stream;
     uint8_t* d = (uint8_t*)c->st_meta.p;
-    std::vector<uint8_t> hm(meta_bytes, 0);
-    memcpy(hm.data() + o_ioff, ioff.data(), 8 * n); memcpy(hm.data() + o_ooff, ooff.data(), 8 * n);
-    memcpy(hm.data() + o_ilen, ilen.data(), 4 * n); memcpy(hm.data() + o_ocap, ocap.data(), 4 * n);
-    memcpy(hm.data() + o_hist, shist.data(), 4 * n); memcpy(hm.data() + o_bit, sbit.data(), 4 * n);
+    std::vector<uint8_t> hm(meta_bytes, 0);   // the host's image of the tables
+    const auto hm_at = [&](const void* dev) { return hm.data() + ((const uint8_t*)dev - d); };
+    memcpy(hm_at(d_ioff), ioff.data(), 8 * n); memcpy(hm_at(d_ooff), ooff.data(), 8 * n);
+    memcpy(hm_at(d_ilen), ilen.data(), 4 * n); memcpy(hm_at(d_ocap), ocap.data(), 4 * n);
+    memcpy(hm_at(d_hist), shist.data(), 4 * n); memcpy(hm_at(d_bit), sbit.data(), 4 * n);
     if (!in_on_device) ZMI_HIPS(hipMemcpyAsync(c->st_in.p, in, in_len, hipMemcpyHostToDevice, hs));
     if (hist_len) ZMI_HIPS(hipMemcpyAsync((uint8_t*)c->st_out.p + base - hist_len, hist, hist_len, hipMemcpyHostToDevice, hs));
     ZMI_HIPS(hipMemcpyAsync(d, hm.data(), meta_bytes, hipMemcpyHostToDevice, hs));
     zmi_inf_scratch dec;   // (the decode's bitmap goes to the stitch below)
-    rc = zmi_inflate_impl(c, {.d_in = c->st_in.p, .d_in_off = (const uint64_t*)(d + o_ioff), .d_in_len = (const uint32_t*)(d + o_ilen), .n = nseg,
-                              .wrap = ZMI_WRAP_RAW, .d_out = c->sp_out.p, .d_out_off = (const uint64_t*)(d + o_ooff),
-                              .d_out_cap = (const uint32_t*)(d + o_ocap), .d_out_hist = (const uint32_t*)(d + o_hist),
-                              .d_out_len = (uint32_t*)(d + o_olen), .d_status = (int32_t*)(d + o_st), .d_in_used = (uint32_t*)(d + o_used),
-                              .d_detail = (int32_t*)(d + o_det), .d_in_bit = (const uint32_t*)(d + o_bit), .d_resume = (uint32_t*)(d + o_res),
+    rc = zmi_inflate_impl(c, {.d_in = c->st_in.p, .d_in_off = d_ioff, .d_in_len = d_ilen, .n = nseg,
+                              .wrap = ZMI_WRAP_RAW, .d_out = c->sp_out.p, .d_out_off = d_ooff,
+                              .d_out_cap = d_ocap, .d_out_hist = d_hist,
+                              .d_out_len = d_olen, .d_status = d_st, .d_in_used = d_used,
+                              .d_detail = d_det, .d_in_bit = d_bit, .d_resume = d_res,
                               .stream = hs, .decode_only = true, .out_limit = scratch + (1ull << 16), .scratch = &dec});
     if (rc) { (void)hipStreamSynchronize(hs); return rc; }
     std::vector<uint32_t> r(8 * n), codes(nseg, 0u);   // olen | status | used | detail | resume[4n]
-    ZMI_HIPS(hipMemcpyAsync(r.data(), d + o_olen, 32 * n, hipMemcpyDeviceToHost, hs));
+    ZMI_HIPS(hipMemcpyAsync(r.data(), d_olen, 32 * n, hipMemcpyDeviceToHost, hs));
     // (every segment's tables' size, see zmi_inflate_resume)
     ZMI_HIPS(hipMemcpyAsync(codes.data(), dec.check, 4u * (size_t)nseg, hipMemcpyDeviceToHost, hs));
     ZMI_HIPS(hipStreamSynchronize(hs));
@@ -2410,21 +2444,21 @@ static int zmi_split_core(zmi_ctx* c, const uint8_t* in, uint32_t in_len, uint32
     rc = zmi_reserve(c->inf_ptr, (size_t)total * 4u + 512u);
     if (rc) return rc;
     struct { uint64_t off; uint32_t len, err; } one = {0ull, (uint32_t)total, 0u};
-    ZMI_HIPS(hipMemcpyAsync(d + o_soff, soff.data(), 8 * (take + 1u), hipMemcpyHostToDevice, hs));
-    ZMI_HIPS(hipMemcpyAsync(d + o_one, &one, sizeof(one), hipMemcpyHostToDevice, hs));
-    if (trimmed) ZMI_HIPS(hipMemcpyAsync(d + o_olen, olen, 4 * (size_t)take, hipMemcpyHostToDevice, hs));
+    ZMI_HIPS(hipMemcpyAsync(d_soff, soff.data(), 8 * (take + 1u), hipMemcpyHostToDevice, hs));
+    ZMI_HIPS(hipMemcpyAsync(d_one_off, &one, sizeof(one), hipMemcpyHostToDevice, hs));
+    if (trimmed) ZMI_HIPS(hipMemcpyAsync(d_olen, olen, 4 * (size_t)take, hipMemcpyHostToDevice, hs));
     uint8_t* d_fin = (uint8_t*)c->st_out.p + base;
-    zmi_launch_copy_ranges((const uint8_t*)c->sp_out.p, (const uint64_t*)(d + o_ooff), 0, (const uint32_t*)(d + o_olen), take, d_fin,
-                           (const uint64_t*)(d + o_soff), total, 0xFFFFFFFFu, hs);
+    zmi_launch_copy_ranges((const uint8_t*)c->sp_out.p, d_ooff, 0, d_olen, take, d_fin,
+                           d_soff, total, 0xFFFFFFFFu, hs);
     uint32_t rounds = 2u;   // ceil(log3(total)) + 1
     for (uint64_t span = 3u; rounds < 34u && span < total; span *= 3u) ++rounds;
     {
         zmi_scope_timer tm(c, ZMI_K_RESOLVE, hs);
-        zmi_launch_resolve_jump_segments(d_fin, (const uint64_t*)(d + o_soff), take, dec.bitmap, dec.bm_off, (int32_t*)c->inf_ptr.p, total, hist_len, rounds, (uint32_t*)((uint8_t*)c->inf_ptr.p + (size_t)total * 4u),
-                                         (uint32_t*)(d + o_one + 12), (const uint64_t*)(d + o_one), (const uint32_t*)(d + o_one + 8), hs);
+        zmi_launch_resolve_jump_segments(d_fin, d_soff, take, dec.bitmap, dec.bm_off, (int32_t*)c->inf_ptr.p, total, hist_len, rounds, (uint32_t*)((uint8_t*)c->inf_ptr.p + (size_t)total * 4u),
+                                         d_one_err, d_one_off, d_one_len, hs);
     }
     uint32_t err = 0;
-    ZMI_HIPS(hipMemcpyAsync(&err, d + o_one + 12, 4, hipMemcpyDeviceToHost, hs));
+    ZMI_HIPS(hipMemcpyAsync(&err, d_one_err, 4, hipMemcpyDeviceToHost, hs));
     double sp_t2 = 0.0;
     if (sp_trace) { ZMI_HIPS(hipStreamSynchronize(hs)); sp_t2 = sp_now(); }
     { const int crc = zmi_d2h(c, out, d_fin, (size_t)total, hs); if (crc) return crc; }
@@ -3290,41 +3324,45 @@ static int zmi_inflate_stream_body(zmi_ctx* c, const void* d_in, uint64_t in_len
     const uint64_t stride = ((uint64_t)piece_out_max + ZMI_SI_CH - 1u) & ~(uint64_t)(ZMI_SI_CH - 1u);
     // per piece: decode bytes + symbols + its window + bitmap and tables; per block of the scan: a map and a window
     const uint64_t per = stride * 3u + ZMI_SI_WIN + stride / 8u + 128u + (3u * ZMI_SI_WIN) / ZMI_SI_B + 64u;
-    uint64_t group = c->scratch_limit / per;
-    if (const char* gv = zmi_tune("ZMI_STREAM_GROUP")) if (atoll(gv) > 0) group = (uint64_t)atoll(gv);
+    const uint64_t group = zmi_plan_groups_per(c->scratch_limit, zmi_group_override(), n_cuts, per).group;
     if (group == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one piece");
-    if (group > n_cuts) group = n_cuts;
     const uint32_t G = (uint32_t)group, nblk = (G + ZMI_SI_B - 1u) / ZMI_SI_B;
-    const size_t n = n_cuts;
-    // per-call tables: off u64[n + 1] | bad u64 | tail u64 | len u32[n] | clen u32[n] | adler u32[n] | crc u32[n] | hdr u32[4] |
-    // combined checks u32[2] | carried window
-    const size_t m_off = 0, m_bad = 8 * (n + 1), m_tail = m_bad + 8, m_len = m_tail + 8, m_clen = m_len + 4 * n, m_adler = m_clen + 4 * n,
-                 m_crc = m_adler + 4 * n, m_hdr = m_crc + 4 * n, m_chk = m_hdr + 16, m_carry = (m_chk + 8 + 15) & ~(size_t)15,
-                 meta_bytes = m_carry + ZMI_SI_WIN;
-    // launch group: in_off u64 | out_off u64 | in_n | ocap | hist | olen | st | used | det | start bit (u32[G] each) | res u32[4G] |
-    // agg u16[nblk * 32 Ki] | wstart | win | sym | dec
-    const size_t g = G;
-    const size_t w_ioff = 0, w_ooff = 8 * g, w_in = 16 * g, w_cap = w_in + 4 * g, w_hist = w_cap + 4 * g, w_olen = w_hist + 4 * g, w_st = w_olen + 4 * g,
-                 w_used = w_st + 4 * g, w_det = w_used + 4 * g, w_bit = w_det + 4 * g, w_res = w_bit + 4 * g, w_agg = (w_res + 16 * g + 255) & ~(size_t)255,
-                 w_wst = w_agg + (size_t)nblk * ZMI_SI_WIN * 2u, w_win = w_wst + (size_t)nblk * ZMI_SI_WIN, w_sym = w_win + g * ZMI_SI_WIN,
-                 w_dec = w_sym + g * stride * 2u + ZMI_SI_SLACK, work_bytes = w_dec + g * stride + ZMI_SI_SLACK;
-    int rc = zmi_reserve(c->si_meta, meta_bytes);
-    if (!rc) rc = zmi_reserve(c->si_work, work_bytes);
+    const size_t n = n_cuts, g = G;
+    uint64_t *d_off, *d_bad, *d_tail;
+    uint32_t *d_len, *d_clen, *d_adler, *d_crc, *d_hdr, *d_chk;
+    uint8_t* d_carry;
+    int rc = zmi_carve(c->si_meta, [&](zmi_carver k) {   // the call's tables
+        k.take(n + 1, d_off);            // the pieces' places in d_out
+        k.take(1, d_bad, d_tail);        // the first piece that did not verify, and the tail word (zmi_launch_si_verify)
+        k.take(n, d_len, d_clen, d_adler, d_crc);   // per piece: decoded size, that clamped to out_cap, check values
+        k.take(4, d_hdr);                // what the header said
+        k.take(2, d_chk);                // the combined checks
+        k.align(16u);
+        k.take(ZMI_SI_WIN, d_carry);     // the window carried into the next group
+        return k.end();
+    });
     if (rc) return rc;
-    uint8_t* M = (uint8_t*)c->si_meta.p;
-    uint8_t* W = (uint8_t*)c->si_work.p;
-    uint64_t* d_off = (uint64_t*)(M + m_off);
-    uint64_t* d_bad = (uint64_t*)(M + m_bad);
-    uint64_t* d_tail = (uint64_t*)(M + m_tail);
-    uint32_t* d_len = (uint32_t*)(M + m_len);
-    uint32_t* d_clen = (uint32_t*)(M + m_clen);
-    uint32_t* d_adler = (uint32_t*)(M + m_adler);
-    uint32_t* d_crc = (uint32_t*)(M + m_crc);
-    uint32_t* d_hdr = (uint32_t*)(M + m_hdr);
-    uint32_t* d_chk = (uint32_t*)(M + m_chk);
-    uint8_t* d_carry = M + m_carry;
-    uint16_t* d_sym = (uint16_t*)(W + w_sym);
-    uint8_t* d_dec = W + w_dec;
+    uint64_t *g_ioff, *g_ooff;
+    uint32_t *g_in, *g_cap, *g_hist, *g_olen, *g_used, *g_bit, *g_res;
+    int32_t *g_st, *g_det;
+    uint16_t *g_agg, *d_sym;
+    uint8_t *g_wst, *g_win, *d_dec;
+    rc = zmi_carve(c->si_work, [&](zmi_carver k) {       // one launch group's tables and regions
+        k.take(g, g_ioff, g_ooff);       // the decode's request (zmi_inf_req)
+        k.take(g, g_in, g_cap, g_hist, g_olen, g_st, g_used, g_det);
+        k.take(g, g_bit);                // the start bits (the bit forms)
+        k.take(4 * g, g_res);            // the resume words
+        k.align(256u);
+        k.take((size_t)nblk * ZMI_SI_WIN, g_agg);   // per block of the window scan: a map
+        k.take((size_t)nblk * ZMI_SI_WIN, g_wst);   // ... and the window it starts with
+        k.take(g * ZMI_SI_WIN, g_win);   // per piece: its window
+        k.take(g * stride, d_sym);       // ... its symbols
+        k.skip(ZMI_SI_SLACK);
+        k.take(g * stride, d_dec);       // ... its decoded bytes
+        k.skip(ZMI_SI_SLACK);
+        return k.end();
+    });
+    if (rc) return rc;
     ZMI_HIP(hipMemsetAsync(d_off, 0, 8, stream));
     ZMI_HIP(hipMemsetAsync(d_bad, 0xFF, 8, stream));
     ZMI_HIP(hipMemsetAsync(d_tail, 0, 8, stream));
@@ -3344,27 +3382,19 @@ static int zmi_inflate_stream_body(zmi_ctx* c, const void* d_in, uint64_t in_len
         const uint32_t f = (uint32_t)first;
         {
             zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
-            if (bits)
-                zmi_launch_si_setup_bits(d_cuts, n_cuts, in_len, f, cnt, stride, piece_out_max, (uint64_t*)(W + w_ioff), (uint32_t*)(W + w_in),
-                                         (uint64_t*)(W + w_ooff), (uint32_t*)(W + w_cap), (uint32_t*)(W + w_hist), (uint32_t*)(W + w_bit), stream);
-            else
-                zmi_launch_si_setup(d_cuts, n_cuts, in_len, f, cnt, stride, piece_out_max, (uint64_t*)(W + w_ioff), (uint32_t*)(W + w_in),
-                                    (uint64_t*)(W + w_ooff), (uint32_t*)(W + w_cap), (uint32_t*)(W + w_hist), stream);
+            if (bits) zmi_launch_si_setup_bits(d_cuts, n_cuts, in_len, f, cnt, stride, piece_out_max, g_ioff, g_in, g_ooff, g_cap, g_hist, g_bit, stream);
+            else zmi_launch_si_setup(d_cuts, n_cuts, in_len, f, cnt, stride, piece_out_max, g_ioff, g_in, g_ooff, g_cap, g_hist, stream);
         }
         zmi_inf_scratch dec;   // (the decode's bitmap covers one group's regions; the symbolic resolve reads it)
-        rc = zmi_inflate_impl(c, {.d_in = d_in, .d_in_off = (const uint64_t*)(W + w_ioff), .d_in_len = (const uint32_t*)(W + w_in), .n = cnt,
-                                  .wrap = ZMI_WRAP_RAW, .d_out = d_dec, .d_out_off = (const uint64_t*)(W + w_ooff),
-                                  .d_out_cap = (const uint32_t*)(W + w_cap), .d_out_hist = (const uint32_t*)(W + w_hist),
-                                  .d_out_len = (uint32_t*)(W + w_olen), .d_status = (int32_t*)(W + w_st), .d_in_used = (uint32_t*)(W + w_used),
-                                  .d_detail = (int32_t*)(W + w_det), .d_in_bit = bits ? (const uint32_t*)(W + w_bit) : nullptr,
-                                  .d_resume = (uint32_t*)(W + w_res), .stream = stream_, .decode_only = true,
-                                  .out_limit = group * stride + (1ull << 16), .scratch = &dec});
+        rc = zmi_inflate_impl(c, {.d_in = d_in, .d_in_off = g_ioff, .d_in_len = g_in, .n = cnt, .wrap = ZMI_WRAP_RAW, .d_out = d_dec,
+                                  .d_out_off = g_ooff, .d_out_cap = g_cap, .d_out_hist = g_hist, .d_out_len = g_olen, .d_status = g_st,
+                                  .d_in_used = g_used, .d_detail = g_det, .d_in_bit = bits ? g_bit : nullptr, .d_resume = g_res,
+                                  .stream = stream_, .decode_only = true, .out_limit = group * stride + (1ull << 16), .scratch = &dec});
         if (rc) return rc;
         {
             zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
-            (bits ? zmi_launch_si_verify_bits : zmi_launch_si_verify)(d_cuts, n_cuts, f, cnt, (const uint32_t*)(W + w_in), (const uint32_t*)(W + w_olen),
-                                                                      (const int32_t*)(W + w_st), (const int32_t*)(W + w_det),
-                                                                      (const uint32_t*)(W + w_res), piece_out_max, d_len, d_bad, d_tail, stream);
+            (bits ? zmi_launch_si_verify_bits : zmi_launch_si_verify)(d_cuts, n_cuts, f, cnt, g_in, g_olen, g_st, g_det, g_res, piece_out_max,
+                                                                      d_len, d_bad, d_tail, stream);
         }
         {
             zmi_scope_timer tm(c, ZMI_K_PACK, stream);
@@ -3376,21 +3406,21 @@ static int zmi_inflate_stream_body(zmi_ctx* c, const void* d_in, uint64_t in_len
         }
         {
             zmi_scope_timer tm(c, ZMI_K_PARSE, stream);   // (the window scan; an inflate call runs no cost parse)
-            zmi_launch_si_window_scan(d_sym, stride, d_len + f, cnt, ZMI_SI_B, (uint16_t*)(W + w_agg), d_carry, W + w_wst, W + w_win, stream);
+            zmi_launch_si_window_scan(d_sym, stride, d_len + f, cnt, ZMI_SI_B, g_agg, d_carry, g_wst, g_win, stream);
         }
         {
             zmi_scope_timer tm(c, ZMI_K_PACK, stream);
-            zmi_launch_si_subst(d_sym, stride, d_len + f, d_off + f, W + w_win, cnt, piece_out_max, f, (uint8_t*)d_out, out_cap, d_bad, stream);
+            zmi_launch_si_subst(d_sym, stride, d_len + f, d_off + f, g_win, cnt, piece_out_max, f, (uint8_t*)d_out, out_cap, d_bad, stream);
             zmi_launch_si_clamp(d_len + f, d_off + f, cnt, out_cap, d_clen + f, stream);
         }
         if (kind) {
             zmi_scope_timer tm(c, ZMI_K_CHECKSUM, stream);
             zmi_launch_checksum((const uint8_t*)d_out, d_off + f, d_clen + f, cnt, kind, d_adler + f, d_crc + f, stream);
         }
-        if (ix) {   // the group's points (the walk goes on from the device words the group before left), then their windows out of w_win
+        if (ix) {   // the group's points (the walk goes on from the device words the group before left), then their windows out of g_win
             zmi_scope_timer tm(c, ZMI_K_PACK, stream);
             zmi_launch_ix_select(d_cuts, d_off + f, f, cnt, ix->span, ix->bit, ix->out, ix->cap, ix->n_points, ix->max_gap, stream);
-            if (ix->win) zmi_launch_ix_gather(d_cuts, d_off + f, f, cnt, ix->bit, ix->out, ix->n_points, W + w_win, ix->win, stream);
+            if (ix->win) zmi_launch_ix_gather(d_cuts, d_off + f, f, cnt, ix->bit, ix->out, ix->n_points, g_win, ix->win, stream);
         }
         ZMI_HIP(hipGetLastError());
     }
@@ -3463,37 +3493,41 @@ extern "C" int zmi_inflate_ranges_dev(zmi_ctx* c, const void* d_in, uint64_t in_
     if (group > n_ranges) group = n_ranges;
     const uint32_t G = (uint32_t)group;
     const size_t g = G;
-    // launch group: in_off | out_off | copy src | copy dst (u64[G] each) | in_n | cap | hist | bit | skip | need | k | pre | olen | st |
-    // used | det | copy len (u32[G] each) | res u32[4G] | the regions
-    const size_t w_ioff = 0, w_ooff = 8 * g, w_csrc = 16 * g, w_cdst = 24 * g, w_u32 = 32 * g, w_olen = w_u32 + 32 * g, w_st = w_olen + 4 * g,
-                 w_used = w_st + 4 * g, w_det = w_used + 4 * g, w_clen = w_det + 4 * g, w_res = w_clen + 4 * g,
-                 w_reg = (w_res + 16 * g + 255) & ~(size_t)255, work_bytes = w_reg + g * rstride;
-    int rc = zmi_reserve(c->si_work, work_bytes);
+    uint64_t *g_ioff, *g_ooff, *g_csrc, *g_cdst;
+    uint32_t *d_u32, *g_olen, *g_used, *g_clen, *g_res;
+    int32_t *g_st, *g_det;
+    uint8_t* g_reg;
+    int rc = zmi_carve(c->si_work, [&](zmi_carver k) {   // one launch group's tables and regions
+        k.take(g, g_ioff, g_ooff);
+        k.take(g, g_csrc, g_cdst);       // the trimmed copy: from, to
+        k.take(8 * g, d_u32);            // in_n | cap | hist | bit | skip | need | k | pre (rg_tab, inflate.hip)
+        k.take(g, g_olen, g_st, g_used, g_det);
+        k.take(g, g_clen);               // the trimmed copy's lengths
+        k.take(4 * g, g_res);
+        k.align(256u);
+        k.take(g * rstride, g_reg);      // the regions
+        return k.end();
+    });
     if (rc) return rc;
-    uint8_t* W = (uint8_t*)c->si_work.p;
-    uint32_t* d_u32 = (uint32_t*)(W + w_u32);   // in_n | cap | hist | bit | ... (rg_tab, inflate.hip)
     for (uint64_t first = 0; first < n_ranges; first += group) {
         const uint32_t cnt = (uint32_t)(n_ranges - first < group ? n_ranges - first : group);
         const uint32_t f = (uint32_t)first;
         {
             zmi_scope_timer tm(c, ZMI_K_PARSE, stream);   // (plan and history; an inflate call runs no cost parse)
             zmi_launch_rg_plan(d_ix_bit, d_ix_out, n_points, d_ix_win ? 1u : 0u, in_len, max_gap, d_lo, d_len, f, cnt, max_len, rstride,
-                               (uint64_t*)(W + w_ioff), (uint64_t*)(W + w_ooff), d_u32, G, stream);
-            if (d_ix_win) zmi_launch_rg_hist((const uint8_t*)d_ix_win, d_u32, G, cnt, rstride, W + w_reg, stream);
+                               g_ioff, g_ooff, d_u32, G, stream);
+            if (d_ix_win) zmi_launch_rg_hist((const uint8_t*)d_ix_win, d_u32, G, cnt, rstride, g_reg, stream);
         }
-        rc = zmi_inflate_impl(c, {.d_in = d_in, .d_in_off = (const uint64_t*)(W + w_ioff), .d_in_len = d_u32, .n = cnt, .wrap = ZMI_WRAP_RAW,
-                                  .d_out = W + w_reg, .d_out_off = (const uint64_t*)(W + w_ooff), .d_out_cap = d_u32 + g, .d_out_hist = d_u32 + 2 * g,
-                                  .d_out_len = (uint32_t*)(W + w_olen), .d_status = (int32_t*)(W + w_st), .d_in_used = (uint32_t*)(W + w_used),
-                                  .d_detail = (int32_t*)(W + w_det), .d_in_bit = d_u32 + 3 * g, .d_resume = (uint32_t*)(W + w_res),
-                                  .stream = stream_, .out_limit = group * room + (1ull << 16)});   // (the decode's bitmap covers one group's rooms)
+        rc = zmi_inflate_impl(c, {.d_in = d_in, .d_in_off = g_ioff, .d_in_len = d_u32, .n = cnt, .wrap = ZMI_WRAP_RAW, .d_out = g_reg,
+                                  .d_out_off = g_ooff, .d_out_cap = d_u32 + g, .d_out_hist = d_u32 + 2 * g, .d_out_len = g_olen, .d_status = g_st,
+                                  .d_in_used = g_used, .d_detail = g_det, .d_in_bit = d_u32 + 3 * g, .d_resume = g_res, .stream = stream_,
+                                  .out_limit = group * room + (1ull << 16)});   // (the decode's bitmap covers one group's rooms)
         if (rc) return rc;
         {
             zmi_scope_timer tm(c, ZMI_K_PACK, stream);
-            zmi_launch_rg_finish((uint64_t*)(W + w_ioff), (uint64_t*)(W + w_ooff), d_u32, G, (const uint32_t*)(W + w_olen), (const int32_t*)(W + w_st),
-                                 (const int32_t*)(W + w_det), f, cnt, d_out_off, out_stride, d_got, d_status, (uint64_t*)(W + w_csrc),
-                                 (uint32_t*)(W + w_clen), (uint64_t*)(W + w_cdst), stream);
-            zmi_launch_copy_ranges(W + w_reg, (const uint64_t*)(W + w_csrc), 0, (const uint32_t*)(W + w_clen), cnt, (uint8_t*)d_out,
-                                   (const uint64_t*)(W + w_cdst), ~0ull, max_len, stream);
+            zmi_launch_rg_finish(g_ioff, g_ooff, d_u32, G, g_olen, g_st, g_det, f, cnt, d_out_off, out_stride, d_got, d_status, g_csrc, g_clen,
+                                 g_cdst, stream);
+            zmi_launch_copy_ranges(g_reg, g_csrc, 0, g_clen, cnt, (uint8_t*)d_out, g_cdst, ~0ull, max_len, stream);
         }
         ZMI_HIP(hipGetLastError());
     }
@@ -3617,27 +3651,22 @@ extern "C" int zmi_inflate_members_dev(zmi_ctx* c, const void* d_in, uint64_t in
     uint32_t repairs = ZMI_MM_REPAIR_PASSES;
     if (const char* rv = zmi_tune("ZMI_MM_REPAIR")) repairs = (uint32_t)atoi(rv);   // (the probe: what do the idle passes cost?)
     const size_t n = n_starts;
-    // words u32[16] | last resort: in_off u64, out_off u64, in, cap, olen, st, used, det | off u64[n + 1] | rank u64[n + 1] |
-    // group: in_off u64[n], out_off u64[n] | tables u32[8n] | group: in, cap, olen, st, used, det u32[n] each
-    const size_t m_w = 0, m_lr = 64, m_off = 128, m_rank = m_off + 8 * (n + 1), m_gio = m_rank + 8 * (n + 1), m_goo = m_gio + 8 * n,
-                 m_tab = m_goo + 8 * n, m_g = m_tab + 32 * n, bytes = m_g + 24 * n;
-    int rc = zmi_reserve(c->mm_meta, bytes);
+    uint64_t *l_ioff, *l_ooff, *d_off, *d_rank, *g_ioff, *g_ooff;
+    uint32_t *d_w, *l_in, *l_cap, *l_olen, *l_used, *d_tab, *g_in, *g_cap, *g_olen, *g_used;
+    int32_t *l_st, *l_det, *g_st, *g_det;
+    int rc = zmi_carve(c->mm_meta, [&](zmi_carver k) {
+        k.take(16, d_w);             // the call's words
+        k.take(1, l_ioff, l_ooff);   // the last resort's launch of one member
+        k.take(1, l_in, l_cap, l_olen, l_st, l_used, l_det);
+        k.skip(24u);                 // (spare: the per-member tables have always started at byte 128)
+        k.take(n + 1, d_off);        // the members' planned places in d_out
+        k.take(n + 1, d_rank);       // the scan of the live flags
+        k.take(n, g_ioff, g_ooff);   // a launch group: one stream per proposal
+        k.take(8 * n, d_tab);        // the proposals' tables (mm_tab, inflate.hip)
+        k.take(n, g_in, g_cap, g_olen, g_st, g_used, g_det);
+        return k.end();
+    });
     if (rc) return rc;
-    uint8_t* M = (uint8_t*)c->mm_meta.p;
-    uint32_t* d_w = (uint32_t*)(M + m_w);
-    uint64_t* l_ioff = (uint64_t*)(M + m_lr);
-    uint64_t* l_ooff = l_ioff + 1;
-    uint32_t* l_in = (uint32_t*)(l_ooff + 1);
-    uint32_t *l_cap = l_in + 1, *l_olen = l_in + 2, *l_used = l_in + 4;
-    int32_t *l_st = (int32_t*)(l_in + 3), *l_det = (int32_t*)(l_in + 5);
-    uint64_t* d_off = (uint64_t*)(M + m_off);
-    uint64_t* d_rank = (uint64_t*)(M + m_rank);
-    uint64_t* g_ioff = (uint64_t*)(M + m_gio);
-    uint64_t* g_ooff = (uint64_t*)(M + m_goo);
-    uint32_t* d_tab = (uint32_t*)(M + m_tab);
-    uint32_t* g_in = (uint32_t*)(M + m_g);
-    uint32_t *g_cap = g_in + n, *g_olen = g_in + 2 * n, *g_used = g_in + 4 * n;
-    int32_t *g_st = (int32_t*)(g_in + 3 * n), *g_det = (int32_t*)(g_in + 5 * n);
     const uint64_t bm_limit = (out_cap > limit ? limit : out_cap) + (1ull << 16);   // the decode's bitmap covers one group's regions
     ZMI_HIP(hipMemsetAsync(d_w, 0, 64, stream));
     {

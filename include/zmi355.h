@@ -1113,7 +1113,7 @@ int zmi_tiff_write_dev(zmi_ctx* ctx, const zmi_tiff_write* w, const void* d_in, 
 /* ---- reading OpenEXR images (ZIP / ZIPS / NONE): the attribute list, a batch inflate of the chunks, the unzip --------------------------
  * Two calls, both asynchronous on `stream`, neither synchronises with the host, every per-file failure is a device word.  File i is
  * d_in[d_in_off[i] .. + d_in_len[i]), at any alignment.  OpenEXR is not part of the reference project: the contract is the format, as
- * stated here.  Not built, each a change of its own: writing EXR; RLE, PIZ, PXR24, B44, DWA; subsampled channels, mip / rip levels,
+ * stated here.  Not built, each a change of its own: RLE, PIZ, PXR24, B44, DWA; subsampled channels, mip / rip levels,
  * multi-part and deep files; a selection of rows or tiles inside a file; conversion of HALF to float.
  *
  * The format.  All integers and floats are little-endian.
@@ -1242,6 +1242,93 @@ int zmi_exr_read_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, c
                      const zmi_exr_channel* d_channels, uint32_t chan_cap, uint32_t n_files, const uint32_t* d_sel, uint32_t n_sel,
                      uint32_t chunk_cap, uint64_t decoded_bytes, uint32_t flags, uint32_t out_align, void* d_out, uint64_t out_cap,
                      uint64_t* d_out_off /* n_sel + 1 */, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, void* stream);
+
+/* ---- writing OpenEXR images (ZIP / ZIPS / NONE): the forward zip, deflate in pieces, chunks and offset table ------------------------------
+ * The inverse of the two calls above: a batch of images of ONE layout (a frame sequence) in device memory becomes a batch of complete
+ * single-part .exr files in one device buffer, one asynchronous call on `stream` that never synchronises with the host; every per-image
+ * failure is a device word.  The layout is the caller's (*w and the channel list are host memory, read during the call), so the chunk
+ * count, every chunk's raw size n and the header's bytes follow on the host and every table is sized exactly.  Not written: the other
+ * compressions, subsampled channels, mip / rip levels, multi-part and deep files, line orders other than increasing y, further attributes.
+ *
+ *   Arguments   ZMI_E_ARG as the return value, with a zmi_last_error text and nothing launched: an inverted window; a width, height,
+ *               pixel count, row, region or chunk that does not fit 32 bits (what the reader flags ZMI_XE_BIG); zero channels; a pixel
+ *               type above 2; a name that is NULL, empty or longer than 255 bytes; names that are not strictly ascending bytewise (the
+ *               order every other writer keeps, so the file reads elsewhere); a compression other than 0, 2, 3; exactly one of tile_w /
+ *               tile_h being 0; piece_bytes outside 1 .. 2^30; level outside -1 .. 9; strategy outside 0 .. 4; out_align not a power of
+ *               two in 1 .. 4096; flags other than 0; a file bound above 2^32 - 1; more than 2^31 - 1 pieces or chunks in the call;
+ *               a NULL table that is not optional.
+ *   Input       image i is exactly the region zmi_exr_read_dev writes, at d_in + d_in_off[i], at any alignment: the channels' [H, W]
+ *               planes in list order, little-endian, each at the next multiple of 4 bytes; the pad bytes are not read.
+ *   File        every byte is fixed:
+ *                 76 2f 31 01 | u32 version = 2, | 0x200 where tiled, | 0x400 where a channel name is longer than 31 bytes
+ *                 the attributes, each name\0 type\0 i32 size value, in this order:
+ *                   channels chlist            per channel name\0 | i32 pixelType | u8 pLinear 0 | 00 00 00 | i32 1 | i32 1; then 00
+ *                   compression compression    1 byte
+ *                   dataWindow box2i           4 x i32
+ *                   displayWindow box2i        4 x i32
+ *                   lineOrder lineOrder        1 byte, 0
+ *                   pixelAspectRatio float     1.0
+ *                   screenWindowCenter v2f     0.0, 0.0
+ *                   screenWindowWidth float    1.0
+ *                   tiles tiledesc             tiled files only: u32 tile_w | u32 tile_h | u8 mode 0
+ *                 00 | the offset table, one u64 per chunk | the chunks in table order, dense: no gap and no padding inside a file,
+ *                 which ends with its last chunk.
+ *               Chunk k of a scanline file is i32 y = yMin + k * lines | i32 dataSize | data, of a tiled file i32 tileX | i32 tileY |
+ *               i32 0 | i32 0 | i32 dataSize | data with k = tileY * tilesX + tileX; edge tiles are cropped.  With compression NONE,
+ *               windows (-1, 5, 1, 6) / (0, 0, 2, 1), channels G HALF = 1 .. 6 and Z FLOAT = 0.5 .. 5.5 the file is these 363 bytes:
+ *                 762f3101 02000000 "channels\0chlist\0" 25000000 "G\0" 01000000 00000000 01000000 01000000 "Z\0" 02000000 00000000
+ *                 01000000 01000000 00 "compression\0compression\0" 01000000 00 "dataWindow\0box2i\0" 10000000 ffffffff 05000000
+ *                 01000000 06000000 "displayWindow\0box2i\0" 10000000 00000000 00000000 02000000 01000000 "lineOrder\0lineOrder\0"
+ *                 01000000 00 "pixelAspectRatio\0float\0" 04000000 0000803f "screenWindowCenter\0v2f\0" 08000000 00000000 00000000
+ *                 "screenWindowWidth\0float\0" 04000000 0000803f 00 | 3701000000000000 5101000000000000 | 05000000 12000000
+ *                 003c 0040 0042 0000003f 0000c03f 00002040 | 06000000 12000000 0044 0045 0046 00006040 00009040 0000b040
+ *   Chunk data  the raw bytes are the chunk's rows, every row the planar runs of its channels (the reader's comment above).  The zip
+ *               forward transform with h = (n + 1) / 2: t[i] = raw[2 i], t[h + i] = raw[2 i + 1]; d[0] = t[0], d[i] = (t[i] - t[i - 1]
+ *               + 128) mod 256.  The candidate stream is the IDAT payload zmi_png_encode_dev would write for d: the two zlib header bytes
+ *               zmi_deflate_stream_dev writes for that level and strategy; d in pieces of piece_bytes, each compressed exactly as
+ *               zmi_deflate_pieces_dev(ZMI_STREAM_INDEPENDENT) does with max_len = piece_bytes; the big-endian Adler-32 of d.
+ *   Raw rule    the reader takes dataSize == n to mean raw bytes, so: where the candidate's length is >= n the chunk's data is the n
+ *               RAW bytes (not d) and dataSize = n; otherwise the data is the candidate and dataSize < n.  Level 0 therefore stores
+ *               every chunk raw, and so does a chunk of 2 bytes; compression NONE skips the encoder altogether.  A file's bytes are a
+ *               function of its pixels and *w alone -- not of n_images, the image's index, the alignment of d_in, the scratch limit,
+ *               the launch grouping or the wave schedule.
+ *   Words       as zmi_png_encode_dev: d_out_off[i] = the lengths in front, each rounded up to out_align; d_out_off[n_images] = the room
+ *               the batch needs, whether or not it fitted; a file that crosses out_cap has Z_BUF_ERROR and length 0 (nothing is promised
+ *               about its bytes in front of out_cap); nothing at or behind d_out + out_cap and nothing in the alignment gaps is written.
+ *               d_status[i] = 0, Z_BUF_ERROR, or the first encoder status among the image's pieces (such a chunk is stored raw, the
+ *               length is 0).  d_chunk_len (NULL or n_images * n_chunks) = every chunk's dataSize.  d_written / d_written_channels
+ *               (NULL or n_images / n_images * n_channels records) = exactly what zmi_exr_headers_dev lists for the written file with
+ *               chan_cap = n_channels, name_pos included; zeros and the status for an image whose status is not 0.  n_images 0 writes
+ *               d_out_off[0] = 0 and nothing else.
+ *   zmi_exr_bound   header + table + every chunk's header + n, rounded up to out_align, times n_images: with the raw rule no file is
+ *               longer.  0 where *w is not valid.
+ *   Plan        one piece table of exactly the call's pieces; launch groups of whole chunks -- the raw decision needs a chunk's whole
+ *               candidate length before its first byte is placed -- of floor(pieces the scratch limit allows / pieces of the largest
+ *               chunk) chunks (ZMI_STREAM_GROUP is rounded down the same way, to at least one chunk; a limit too small for one chunk is
+ *               ZMI_E_NOMEM); the place kernel decides per chunk, the running offset stays in a device word.  Chunk sizes, piece counts
+ *               and item counts are device scans over the chunks of the call.  Raw chunks are gathered from the planes straight into
+ *               the file; no copy of the image stands in scratch.
+ *   Scratch of the context: d of every chunk of the call, each at a multiple of 16, NOT capped by the scratch limit (nothing under
+ *   NONE); 56 bytes per chunk, 36 bytes and 1 bit per piece, 4 per image, 8 per launch group, 24 per channel and the header's bytes; one
+ *   group's slots as in zmi_zip_write_dev.  Scratch that cannot be reserved is ZMI_E_NOMEM.
+ *   Event timing, as zmi_tiff_write_dev: 3 = the forward zip kernel, 0 = Adler-32 of the pieces and the fold per chunk, 1 / 5 / 2 =
+ *   match search, parse, encode, 7 = the chunk and piece tables, places, pack and the raw gather, 4 = the fixed bytes and the words. */
+typedef struct zmi_exr_write_channel { const char* name; int32_t pixel_type; } zmi_exr_write_channel;   /* 0 UINT, 1 HALF, 2 FLOAT */
+typedef struct zmi_exr_write {      /* host memory, read during the call */
+    int32_t  data_window[4], display_window[4];   /* xMin, yMin, xMax, yMax */
+    uint32_t n_channels;
+    const zmi_exr_write_channel* channels;        /* sorted by name */
+    uint32_t compression;             /* 0 NONE, 2 ZIPS, 3 ZIP */
+    uint32_t tile_w, tile_h;          /* both 0: scanlines */
+    uint32_t flags, piece_bytes, out_align;
+    int32_t  level, strategy;
+} zmi_exr_write;
+uint32_t zmi_exr_zip_trip(void);    /* raw bytes one trip of the forward zip kernel covers per wave (for tests that place run lengths around it) */
+uint64_t zmi_exr_bound(const zmi_exr_write* w, uint32_t n_images);   /* the room the batch needs at most; 0 where w is not valid */
+int zmi_exr_write_dev(zmi_ctx* ctx, const zmi_exr_write* w, const void* d_in, const uint64_t* d_in_off, uint32_t n_images, void* d_out,
+                      uint64_t out_cap, uint64_t* d_out_off /* n_images + 1 */, uint32_t* d_out_len, uint32_t* d_chunk_len /* NULL or n_images * n_chunks */,
+                      zmi_exr_image* d_written /* NULL or n_images */, zmi_exr_channel* d_written_channels /* NULL or n_images * n_channels */,
+                      int32_t* d_status, void* stream);
 
 /* ---- host-buffer convenience wrappers: copy in, run the batch on the GPU, copy back ---- */
 int zmi_deflate_batch(zmi_ctx* ctx, const uint8_t* in, const uint64_t* in_off, const uint32_t* in_len, uint32_t n_shards,

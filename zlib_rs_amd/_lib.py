@@ -16,6 +16,18 @@ class TiffWrite(C.Structure):
                 ("piece_bytes", C.c_uint32), ("out_align", C.c_uint32), ("level", C.c_int32), ("strategy", C.c_int32)]
 
 
+class ExrWriteChannel(C.Structure):
+    """zmi_exr_write_channel (include/zmi355.h)"""
+    _fields_ = [("name", C.c_char_p), ("pixel_type", C.c_int32)]
+
+
+class ExrWrite(C.Structure):
+    """zmi_exr_write (include/zmi355.h): host memory, read during zmi_exr_bound / zmi_exr_write_dev"""
+    _fields_ = [("data_window", C.c_int32 * 4), ("display_window", C.c_int32 * 4), ("n_channels", C.c_uint32),
+                ("channels", C.POINTER(ExrWriteChannel)), ("compression", C.c_uint32), ("tile_w", C.c_uint32), ("tile_h", C.c_uint32),
+                ("flags", C.c_uint32), ("piece_bytes", C.c_uint32), ("out_align", C.c_uint32), ("level", C.c_int32), ("strategy", C.c_int32)]
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -117,6 +129,12 @@ def lib():
     L.zmi_tiff_bound.restype = u64
     L.zmi_tiff_bound.argtypes = [C.POINTER(TiffWrite)]
     L.zmi_tiff_write_dev.argtypes = [vp, C.POINTER(TiffWrite), vp, vp, vp, u64, vp, vp, vp, vp, vp, vp]
+    # writing OpenEXR images: the forward zip, deflate in pieces, chunks and offset table (csrc/exr_write_kernels.h, zmi_api.hip); w: an ExrWrite
+    L.zmi_exr_zip_trip.restype = u32
+    L.zmi_exr_zip_trip.argtypes = []
+    L.zmi_exr_bound.restype = u64
+    L.zmi_exr_bound.argtypes = [C.POINTER(ExrWrite), u32]
+    L.zmi_exr_write_dev.argtypes = [vp, C.POINTER(ExrWrite), vp, vp, u32, vp, u64, vp, vp, vp, vp, vp, vp, vp]
     # the multi-GPU stitch (csrc/exchange.hip); RCCL itself is loaded by the library on first use
     L.zmi_comm_unique_id.argtypes = [vp]
     L.zmi_comm_create.argtypes = [C.POINTER(vp), vp, i32, i32, vp]

@@ -1200,3 +1200,6 @@ extern "C" int zmi_launch_zip_close(uint8_t* d_out, uint64_t out_cap, const uint
 
 // ---- reading OpenEXR images (zmi_exr_headers_dev / zmi_exr_read_dev) ----------------------------------------------------------------------
 #include "exr_kernels.h"
+
+// ---- writing OpenEXR images (zmi_exr_bound / zmi_exr_write_dev) ---------------------------------------------------------------------------
+#include "exr_write_kernels.h"

@@ -2218,6 +2218,318 @@ extern "C" int zmi_tiff_write_dev(zmi_ctx* c, const zmi_tiff_write* w, const voi
     return ZMI_E_OK;
 }
 
+// ---- writing OpenEXR images (include/zmi355.h; the kernels: exr_write_kernels.h, checksum.hip) ----------------------
+// zmi_tiff_write_dev's plan with chunks in place of segments and one more step: the place kernel of a launch group decides per chunk
+// between the candidate stream and the raw bytes, so a group holds whole chunks.  The layout is host data: the plan, the header's bytes
+// and the records of a written file are made here (zmi_exr_wplan); the plan goes to the kernels by value, the channel records and the
+// header's bytes through kernel arguments into the scratch (they have no fixed size).
+struct zmi_xw_host {
+    zmi_xw_plan g;
+    std::vector<uint8_t> blob;       // n_ch zmi_exr_channel records | the header's hdr_len bytes
+    uint64_t file_bound = 0;         // header + table + every chunk's header + n
+    uint64_t ppi = 0, ssi = 0, ipi = 0;   // per image: pieces, bytes of d in the scratch, work items of the forward kernel
+    uint32_t n_max = 0;              // the raw size of the largest chunk
+    uint64_t pp[2][2] = {{0, 0}, {0, 0}};   // the pieces of a chunk in an inner / the last column [0 / 1], an inner / the last row
+};
+static void zmi_xw_attr(std::vector<uint8_t>& b, const char* name, const char* type, const void* value, uint32_t size) {
+    b.insert(b.end(), (const uint8_t*)name, (const uint8_t*)name + strlen(name) + 1u);
+    b.insert(b.end(), (const uint8_t*)type, (const uint8_t*)type + strlen(type) + 1u);
+    uint8_t s[4];
+    zmi_tw_le(s, size, 4u);
+    b.insert(b.end(), s, s + 4);
+    b.insert(b.end(), (const uint8_t*)value, (const uint8_t*)value + size);
+}
+// the checks every container writer shares (their texts stand once, above); *level: -1 resolved
+static int zmi_exr_wcheck(const zmi_exr_write* w, int* level) {
+    if (!w) return zmi_fail(ZMI_E_ARG, "zmi_exr_write: null");
+    *level = w->level;
+    int rc = zmi_check_piece_bytes(w->piece_bytes);
+    if (!rc) rc = zmi_check_level_strategy(*level, w->strategy);
+    if (!rc) rc = zmi_check_out_align(w->out_align);
+    return rc;
+}
+// NULL, or what else is wrong with *w (zmi_exr_wcheck has passed)
+static const char* zmi_exr_wplan(const zmi_exr_write* w, uint32_t n_images, zmi_xw_host* h) {
+    if (w->data_window[2] < w->data_window[0] || w->data_window[3] < w->data_window[1]) return "zmi_exr_write: an inverted data window";
+    if (w->display_window[2] < w->display_window[0] || w->display_window[3] < w->display_window[1]) return "zmi_exr_write: an inverted display window";
+    if (w->n_channels == 0u || !w->channels) return "zmi_exr_write: no channels";
+    if (w->compression != 0u && w->compression != 2u && w->compression != 3u) return "zmi_exr_write: compression must be 0 (NONE), 2 (ZIPS) or 3 (ZIP)";
+    if ((w->tile_w == 0u) != (w->tile_h == 0u)) return "zmi_exr_write: tile_w and tile_h must both be 0 or both be set";
+    if (w->flags != 0u) return "zmi_exr_write: unknown flag";
+    bool long_names = false;
+    uint64_t per_px = 0;
+    for (uint32_t c = 0; c < w->n_channels; ++c) {
+        const zmi_exr_write_channel& ch = w->channels[c];
+        if (ch.pixel_type < 0 || ch.pixel_type > 2) return "zmi_exr_write: a pixel type must be 0 (UINT), 1 (HALF) or 2 (FLOAT)";
+        if (!ch.name || ch.name[0] == 0) return "zmi_exr_write: an empty channel name";
+        const size_t nl = strnlen(ch.name, 256u);
+        if (nl > 255u) return "zmi_exr_write: a channel name longer than 255 bytes";
+        if (nl > 31u) long_names = true;
+        if (c && strcmp(w->channels[c - 1u].name, ch.name) >= 0) return "zmi_exr_write: channel names must be strictly ascending";
+        per_px += ch.pixel_type == 1 ? 2u : 4u;
+    }
+    // what xr_geometry (exr_kernels.h) calls big
+    const uint64_t W = (uint64_t)((int64_t)w->data_window[2] - (int64_t)w->data_window[0] + 1);
+    const uint64_t H = (uint64_t)((int64_t)w->data_window[3] - (int64_t)w->data_window[1] + 1);
+    const char* big = "zmi_exr_write: the image does not fit 32 bits (width, height, pixels, a row, the region or a chunk)";
+    if (W > 0xFFFFFFFFull || H > 0xFFFFFFFFull || W * H > 0xFFFFFFFFull || per_px > 0xFFFFFFFFull) return big;
+    const bool tiled = w->tile_w != 0u;
+    const uint32_t lines = w->compression == 3u ? 16u : 1u;
+    const uint64_t box_w = tiled ? w->tile_w : W, box_h = tiled ? w->tile_h : lines;
+    const uint64_t cw0 = box_w < W ? box_w : W, rows0 = box_h < H ? box_h : H;
+    uint64_t region = 0;
+    for (uint32_t c = 0; c < w->n_channels; ++c) region = ((region + 3u) & ~3ull) + W * H * (w->channels[c].pixel_type == 1 ? 2u : 4u);
+    if (W * per_px > 0xFFFFFFFFull || region > 0xFFFFFFFFull || rows0 * cw0 * per_px > 0xFFFFFFFFull) return big;
+    const uint64_t across = (W + box_w - 1u) / box_w, down = (H + box_h - 1u) / box_h;
+    if (across > 0x7FFFFFFFull / down || across * down * (n_images ? n_images : 1u) > 0x7FFFFFFFull)
+        return "zmi_exr_write: more than 2^31 - 1 chunks";
+    const uint64_t nc = across * down;
+    const bool none = w->compression == 0u;
+
+    // the header
+    std::vector<uint8_t> hd = {0x76u, 0x2Fu, 0x31u, 0x01u, 0u, 0u, 0u, 0u};
+    zmi_tw_le(hd.data() + 4, 2u | (tiled ? 0x200u : 0u) | (long_names ? 0x400u : 0u), 4u);
+    std::vector<uint8_t> chl;
+    std::vector<uint32_t> name_pos(w->n_channels);
+    const uint32_t chl_at = 8u + 9u + 7u + 4u;                             // "channels\0" "chlist\0" size
+    for (uint32_t c = 0; c < w->n_channels; ++c) {
+        const char* nm = w->channels[c].name;
+        name_pos[c] = chl_at + (uint32_t)chl.size();
+        chl.insert(chl.end(), (const uint8_t*)nm, (const uint8_t*)nm + strlen(nm) + 1u);
+        uint8_t e[16] = {0};
+        zmi_tw_le(e, (uint32_t)w->channels[c].pixel_type, 4u);
+        zmi_tw_le(e + 8, 1u, 4u);
+        zmi_tw_le(e + 12, 1u, 4u);
+        chl.insert(chl.end(), e, e + 16);
+    }
+    chl.push_back(0u);
+    if (chl.size() > 0x7FFFFFFFull) return "zmi_exr_write: the channel list passes 2^31 - 1 bytes";
+    uint8_t box[16], one[4], zero8[8] = {0}, v1[1], td[9];
+    zmi_tw_le(one, 0x3F800000u, 4u);
+    zmi_xw_attr(hd, "channels", "chlist", chl.data(), (uint32_t)chl.size());
+    v1[0] = (uint8_t)w->compression;
+    zmi_xw_attr(hd, "compression", "compression", v1, 1u);
+    for (uint32_t k = 0; k < 4u; ++k) zmi_tw_le(box + 4u * k, (uint32_t)w->data_window[k], 4u);
+    zmi_xw_attr(hd, "dataWindow", "box2i", box, 16u);
+    for (uint32_t k = 0; k < 4u; ++k) zmi_tw_le(box + 4u * k, (uint32_t)w->display_window[k], 4u);
+    zmi_xw_attr(hd, "displayWindow", "box2i", box, 16u);
+    v1[0] = 0u;
+    zmi_xw_attr(hd, "lineOrder", "lineOrder", v1, 1u);
+    zmi_xw_attr(hd, "pixelAspectRatio", "float", one, 4u);
+    zmi_xw_attr(hd, "screenWindowCenter", "v2f", zero8, 8u);
+    zmi_xw_attr(hd, "screenWindowWidth", "float", one, 4u);
+    if (tiled) {
+        zmi_tw_le(td, w->tile_w, 4u);
+        zmi_tw_le(td + 4, w->tile_h, 4u);
+        td[8] = 0u;
+        zmi_xw_attr(hd, "tiles", "tiledesc", td, 9u);
+    }
+    hd.push_back(0u);
+    const uint64_t hdr_len = hd.size();
+    const uint32_t chdr = tiled ? 20u : 8u;
+    const uint64_t file_bound = hdr_len + nc * (8u + chdr) + H * W * per_px;
+    if (file_bound > 0xFFFFFFFFull) return "zmi_exr_write: a file may pass 2^32 - 1 bytes";
+
+    // the four sizes a chunk has: inner or last column, inner or last row
+    const uint64_t cw_last = W - (across - 1u) * box_w, rows_last = H - (down - 1u) * box_h;
+    uint64_t ppi = 0, ssi = 0, ipi = 0;
+    for (uint32_t cx = 0; cx < 2u; ++cx)
+        for (uint32_t cy = 0; cy < 2u; ++cy) {
+            const uint64_t count = (cx ? 1u : across - 1u) * (cy ? 1u : down - 1u);
+            const uint64_t cw = cx ? cw_last : cw0, rows = cy ? rows_last : rows0, n = rows * cw * per_px;
+            uint64_t per_row = 0;
+            for (uint32_t c = 0; c < w->n_channels; ++c) per_row += (cw * (w->channels[c].pixel_type == 1 ? 2u : 4u) + 8191u) / 8192u;   // (XW_PIECE)
+            ipi += count * rows * per_row;
+            if (!none) {
+                h->pp[cx][cy] = (n + w->piece_bytes - 1u) / w->piece_bytes;
+                ppi += count * h->pp[cx][cy];
+                ssi += count * ((n + 15u) & ~15ull);
+            }
+        }
+    if (ppi * (n_images ? n_images : 1u) > 0x7FFFFFFFull) return "zmi_exr_write: more than 2^31 - 1 pieces";
+
+    zmi_xw_plan& g = h->g;
+    memset(&g, 0, sizeof g);
+    g.W = (uint32_t)W; g.H = (uint32_t)H; g.box_w = (uint32_t)(box_w > 0xFFFFFFFFull ? 0xFFFFFFFFull : box_w); g.box_h = (uint32_t)box_h;
+    g.across = (uint32_t)across; g.down = (uint32_t)down; g.nc = (uint32_t)nc;
+    g.n_ch = w->n_channels; g.per_px = (uint32_t)per_px; g.tiled = tiled ? 1u : 0u; g.comp = w->compression; g.chdr = chdr;
+    g.ymin = w->data_window[1]; g.hdr_len = (uint32_t)hdr_len; g.n_images = n_images; g.ncc = (uint32_t)(nc * n_images);
+    g.piece_bytes = w->piece_bytes; g.out_align = w->out_align;
+    zmi_exr_image r;
+    memset(&r, 0, sizeof r);
+    r.version = 2u | (tiled ? 0x200u : 0u) | (long_names ? 0x400u : 0u);
+    r.compression = (uint8_t)w->compression; r.tiled = tiled ? 1u : 0u;
+    for (uint32_t k = 0; k < 4u; ++k) { r.data_window[k] = w->data_window[k]; r.display_window[k] = w->display_window[k]; }
+    r.width = g.W; r.height = g.H; r.lines_per_chunk = lines; r.tile_w = w->tile_w; r.tile_h = w->tile_h;
+    r.n_channels = w->n_channels; r.n_chunks = g.nc; r.row_bytes = (uint32_t)(W * per_px); r.region_bytes = (uint32_t)region;
+    r.table_pos = hdr_len;
+    static_assert(sizeof r == sizeof g.rec, "zmi_exr_image is 88 bytes");
+    memcpy(g.rec, &r, sizeof r);
+    h->blob.assign((size_t)w->n_channels * sizeof(zmi_exr_channel), 0u);
+    uint64_t off = 0;
+    for (uint32_t c = 0; c < w->n_channels; ++c) {
+        zmi_exr_channel e;
+        off = (off + 3u) & ~3ull;
+        e.name_pos = name_pos[c]; e.name_len = (uint32_t)strlen(w->channels[c].name); e.pixel_type = w->channels[c].pixel_type;
+        e.x_sampling = e.y_sampling = 1; e.plane_off = (uint32_t)off;
+        off += W * H * (e.pixel_type == 1 ? 2u : 4u);
+        memcpy(h->blob.data() + (size_t)c * sizeof e, &e, sizeof e);
+    }
+    h->blob.insert(h->blob.end(), hd.begin(), hd.end());
+    h->file_bound = file_bound; h->ppi = ppi; h->ssi = ssi; h->ipi = ipi; h->n_max = (uint32_t)(rows0 * cw0 * per_px);
+    return nullptr;
+}
+
+extern "C" uint64_t zmi_exr_bound(const zmi_exr_write* w, uint32_t n_images) {
+    zmi_xw_host h;
+    int level;
+    if (zmi_exr_wcheck(w, &level) || zmi_exr_wplan(w, n_images, &h)) return 0;
+    const uint64_t am = (uint64_t)w->out_align - 1u;
+    return (uint64_t)n_images * ((h.file_bound + am) & ~am);
+}
+
+extern "C" int zmi_exr_write_dev(zmi_ctx* c, const zmi_exr_write* w, const void* d_in, const uint64_t* d_in_off, uint32_t n_images, void* d_out,
+                                 uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_out_len, uint32_t* d_chunk_len, zmi_exr_image* d_written,
+                                 zmi_exr_channel* d_written_channels, int32_t* d_status, void* stream_) {
+    if (!c) return zmi_fail(ZMI_E_ARG, "null context");
+    zmi_xw_host h;
+    int level = 0;
+    int rc = zmi_exr_wcheck(w, &level);
+    if (rc) return rc;
+    if (const char* what = zmi_exr_wplan(w, n_images, &h)) return zmi_fail(ZMI_E_ARG, what);
+    if (!d_out_off) return zmi_fail(ZMI_E_ARG, "d_out_off is required");
+    if ((out_cap && !d_out) || (n_images && (!d_in || !d_in_off || !d_out_len || !d_status))) return zmi_fail(ZMI_E_ARG, "null argument");
+    const zmi_xw_plan& g = h.g;
+    const int strategy = w->strategy;
+    const uint32_t piece_bytes = w->piece_bytes, n = n_images, ncc = g.ncc;
+    const bool none = g.comp == 0u;
+    const uint64_t np64 = h.ppi * n, scan_bytes = h.ssi * n, items = h.ipi * n;
+    if (scan_bytes > (1ull << 44)) return zmi_fail(ZMI_E_NOMEM, "the call's raw bytes size the scratch");
+    const uint32_t np = (uint32_t)np64;
+    hipStream_t stream = (hipStream_t)stream_;
+    ZMI_ON_DEVICE(c);
+    if (n == 0) {
+        ZMI_HIP(hipMemsetAsync(d_out_off, 0, sizeof(uint64_t), stream));
+        return ZMI_E_OK;
+    }
+
+    // launch groups of whole chunks: the pieces the limit (or ZMI_STREAM_GROUP) allows, in units of the largest chunk's pieces; slots
+    // and match scratch follow the longest piece there is, the bytes are those of pieces of piece_bytes (zmi_tiff_write_dev)
+    const uint32_t max_len = h.n_max < piece_bytes ? h.n_max : piece_bytes;
+    const uint64_t pp_max = ((uint64_t)h.n_max + piece_bytes - 1u) / piece_bytes;
+    uint64_t stride = 0, gch = ncc, gp = 0;   // a slot; the chunks and the most pieces of a group
+    if (!none) {
+        stride = zmi_piece_slot_stride(max_len, piece_bytes, level);
+        const uint64_t over = zmi_group_override();
+        const zmi_group_plan plan = zmi_plan_groups(c->scratch_limit, over, np, max_len, stride);
+        gch = plan.group / pp_max;
+        if (gch == 0 && over) gch = 1;
+        if (gch == 0) return zmi_fail(ZMI_E_NOMEM, "scratch limit too small for one chunk");
+        if (gch > ncc) gch = ncc;
+        gp = gch * pp_max < np ? gch * pp_max : np;
+        rc = zmi_reserve(c->sd_slots, (size_t)(gp * stride));
+        if (rc) return rc;
+    }
+    const uint64_t n_groups = (ncc + gch - 1u) / gch;
+    const uint32_t wpg = (uint32_t)((gp + 31u) / 32u);
+    const size_t bm_words = none ? 0u : (size_t)(n_groups * wpg);
+    const size_t n_rec = (size_t)g.n_ch * sizeof(zmi_exr_channel);
+
+    uint64_t *d_cfirst, *d_soff, *d_item_off, *d_cpos, *d_poff, *d_ppos, *d_run;
+    zmi_words4 neff;
+    uint32_t *d_csz, *d_npc, *d_ssz, *d_items, *d_cds, *d_cadler, *d_plen, *d_olen, *d_padler, *d_phead, *d_bad, *d_ends;
+    int32_t* d_st;
+    uint8_t *d_blob, *d_scan;
+    rc = zmi_carve(c->exr, [&](zmi_carver k) {
+        k.take(ncc + 1u, d_cfirst, d_soff, d_item_off);   // per chunk: the scans of its pieces, of its room in the scratch, of its items
+        k.take(ncc, d_cpos);                              // ... its header's place in d_out
+        k.take(np, d_poff, d_ppos);                       // per piece: its place in the scratch and in d_out
+        k.take(n_groups + 1u, d_run);                     // where every launch group starts in d_out
+        k.take(neff);                                     // the chunks that are live: all
+        k.take(ncc, d_csz, d_npc, d_ssz, d_items);        // per chunk: raw size, pieces, room, items
+        k.take_unless(d_chunk_len, ncc, d_cds);           // ... its dataSize
+        k.take(ncc, d_cadler);                            // ... the Adler-32 of its d
+        k.take(np, d_plen, d_olen, d_st, d_padler, d_phead);   // per piece: length, encoder's size and status, Adler-32, hole (void: raw chunk)
+        k.take(n, d_bad);                                 // per image: the least piece with a status
+        k.take(bm_words, d_ends);                         // the bitmap of the pieces that end a chunk's stream
+        k.align(8u);
+        k.take(h.blob.size(), d_blob);                    // the channel records | the header's bytes
+        k.align(256u);
+        k.region(d_scan, (size_t)scan_bytes, 64u);        // d of every chunk, each at a multiple of 16
+        return k.end();
+    });
+    if (rc) return rc;
+    const zmi_exr_channel* d_chs = (const zmi_exr_channel*)d_blob;
+    const uint8_t* in = (const uint8_t*)d_in;
+
+    if (bm_words) ZMI_HIP(hipMemsetAsync(d_ends, 0, bm_words * 4u, stream));
+    {
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        for (size_t at = 0; at < h.blob.size(); at += sizeof(zmi_xw_slice::b)) {
+            zmi_xw_slice s;
+            s.at = at;
+            s.len = (uint32_t)(h.blob.size() - at < sizeof s.b ? h.blob.size() - at : sizeof s.b);
+            memcpy(s.b, h.blob.data() + at, s.len);
+            zmi_launch_exr_wslice(s, d_blob, stream);
+        }
+        zmi_launch_exr_wchunks(g, d_chs, d_csz, d_npc, d_ssz, d_items, d_cds, neff.w, d_bad, d_run, stream);
+        zmi_launch_scan_sizes(d_npc, ncc, d_cfirst, stream);
+        zmi_launch_scan_sizes(d_ssz, ncc, d_soff, stream);
+        zmi_launch_scan_sizes(d_items, ncc, d_item_off, stream);
+        if (!none) zmi_launch_exr_wpieces(g, d_cfirst, d_soff, d_csz, (uint32_t)gch, wpg, np, d_poff, d_plen, d_ends, stream);
+    }
+    if (!none) {
+        {
+            zmi_scope_timer tm(c, ZMI_K_INFLATE, stream);
+            zmi_launch_exr_zip(g, d_chs, in, d_in_off, d_item_off, items, d_soff, d_scan, stream);
+        }
+        rc = zmi_piece_checks(c, d_scan, d_poff, d_plen, np, ZMI_WRAP_ZLIB, d_padler, stream);
+        if (rc) return rc;
+    }
+    uint64_t first_piece = 0;
+    for (uint64_t grp = 0; grp < n_groups; ++grp) {
+        const uint32_t q0 = (uint32_t)(grp * gch), cnt_ch = (uint32_t)(ncc - q0 < gch ? ncc - q0 : gch);
+        if (!none) {
+            // the pieces in front of chunk q0 + cnt_ch, counted as the device scan counts them: whole images, whole rows of boxes above
+            // (never the last row), boxes to the left (never the last column)
+            const uint64_t q1 = (uint64_t)q0 + cnt_ch, k1 = q1 % g.nc, tx = k1 % g.across, ty = k1 / g.across;
+            const uint64_t last_piece = (q1 / g.nc) * h.ppi + ty * ((g.across - 1u) * h.pp[0][0] + h.pp[1][0]) +
+                                        tx * h.pp[0][ty + 1u == g.down ? 1u : 0u];
+            const uint32_t cnt = (uint32_t)(last_piece - first_piece);
+            rc = zmi_deflate_impl(c, {.d_in = d_scan, .d_in_off = d_poff + first_piece, .d_in_len = d_plen + first_piece, .n = cnt, .max_len = max_len,
+                                      .level = level, .strategy = strategy, .wrap = ZMI_WRAP_RAW, .chain_mode = 2u, .d_out = c->sd_slots.p,
+                                      .out_stride = stride, .d_out_len = d_olen + first_piece, .d_status = d_st + first_piece, .stream = stream_,
+                                      .carry = 0, .ends = d_ends + grp * wpg, .geom_len = piece_bytes});
+            if (rc) return rc;
+            zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+            zmi_launch_exr_wplace(g, q0, cnt_ch, d_cfirst, d_csz, d_olen, d_st, d_run + grp, d_cds, d_cpos, d_ppos, d_phead, d_out_off, d_bad, stream);
+            zmi_launch_zip_pack(nullptr, d_poff + first_piece, d_phead + first_piece, (const uint8_t*)c->sd_slots.p, stride, d_olen + first_piece, cnt,
+                                stride > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)stride, (uint8_t*)d_out, d_ppos + first_piece, out_cap, stream);
+            first_piece = last_piece;
+        } else {
+            zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+            zmi_launch_exr_wplace(g, q0, cnt_ch, d_cfirst, d_csz, d_olen, d_st, d_run + grp, d_cds, d_cpos, d_ppos, d_phead, d_out_off, d_bad, stream);
+        }
+    }
+    {
+        // the chunks that fell back, or all of them: from the planes straight to their place
+        zmi_scope_timer tm(c, ZMI_K_PACK, stream);
+        zmi_launch_exr_gather(g, d_chs, in, d_in_off, d_item_off, items, d_csz, d_cds, d_cpos, (uint8_t*)d_out, out_cap, stream);
+    }
+    if (!none) {
+        zmi_scope_timer tm(c, ZMI_K_CHECKSUM, stream);
+        zmi_launch_combine_segments_adler(d_padler, d_plen, d_cfirst, ncc, neff.w, d_cadler, stream);
+    }
+    {
+        zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
+        zmi_launch_exr_wframe(g, d_blob + n_rec, d_csz, d_cds, d_cpos, d_cadler, d_out_off, (uint32_t)level, (uint32_t)strategy, (uint8_t*)d_out,
+                              out_cap, stream);
+        zmi_launch_exr_wwords(g, d_chs, d_cds, d_cpos, d_out_off, d_bad, d_st, out_cap, d_out_len, d_status, d_written, d_written_channels, stream);
+    }
+    ZMI_HIP(hipGetLastError());
+    return ZMI_E_OK;
+}
+
 static int zmi_host_pipeline_init(zmi_ctx* c) {   // three streams (in / kernels / out) and the events of the two slots
     if (c->hb_live) return 0;
     ZMI_HIP(hipStreamCreateWithFlags(&c->hs_in, hipStreamNonBlocking));

@@ -92,6 +92,26 @@ struct zmi_tw_meta {
     uint64_t b_pos;
 };
 
+// zmi_exr_write_dev: what the host works out of *w; the kernels of exr_write_kernels.h take it by value.  A chunk is a box of the data
+// window -- box_w = the tile's width (scanline files: the image's), box_h = the tile's height (scanline files: the lines of a chunk) --,
+// chunk k of an image the box (k % across, k / across), cropped at the right and the bottom edge: up to four sizes.
+struct zmi_xw_plan {
+    uint32_t W, H, box_w, box_h, across, down, nc;   // nc = across * down: the chunks of one image
+    uint32_t n_ch, per_px;             // channels; the bytes of a pixel over all of them
+    uint32_t tiled, comp, chdr;        // chdr: the bytes of a chunk's header, 8 or 20
+    int32_t ymin;
+    uint32_t hdr_len;                  // magic, version word, attributes and the 00 behind them: the offset table starts here
+    uint32_t n_images, ncc;            // ncc = n_images * nc: the chunks of the call
+    uint32_t piece_bytes, out_align;
+    uint8_t rec[88];                   // the zmi_exr_image of a written file
+};
+// a slice of the host's bytes on its way into the context's scratch (kernel arguments are the one copy that needs no staging)
+struct zmi_xw_slice {
+    uint8_t b[2048];
+    uint32_t len;
+    uint64_t at;
+};
+
 extern "C" {
 int zmi_launch_gen(uint8_t* d_out, uint64_t seed, uint32_t first_shard, uint32_t n_shards, uint32_t shard_bytes,
                    hipStream_t stream);
@@ -405,4 +425,29 @@ int zmi_launch_exr_finish(const zmi_exr_image* d_images, const uint32_t* d_sel, 
                           const uint32_t* d_pcap, const uint64_t* d_ch_off, const uint64_t* d_raw_off, uint64_t chunk_cap, uint64_t decoded_bytes,
                           const uint32_t* d_csz, const uint32_t* d_scap, const uint32_t* d_rawlen, const uint32_t* d_fl, const uint32_t* d_slen,
                           const int32_t* d_sst, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, hipStream_t stream);
+// writing OpenEXR images (exr_write_kernels.h, compiled into pack.hip; the payload copies are zmi_launch_zip_pack, the fold per chunk
+// zmi_launch_combine_segments_adler): a slice of the host's bytes into the scratch; per chunk of the call its raw size, pieces, room in
+// the scratch and work items (and the words the later kernels start from); the piece table over the scans of those; the forward zip
+// over the items into the scratch; one launch group's places -- chunks first .. first + count, the raw decision, d_run[0] -> d_run[1];
+// the raw chunks' gather from the planes; the fixed bytes; the images' words
+uint32_t zmi_exr_zip_trip(void);
+int zmi_launch_exr_wslice(zmi_xw_slice slice, uint8_t* d_blob, hipStream_t stream);
+int zmi_launch_exr_wchunks(zmi_xw_plan plan, const zmi_exr_channel* d_chs, uint32_t* d_csz, uint32_t* d_npc, uint32_t* d_ssz, uint32_t* d_items,
+                           uint32_t* d_cds, uint32_t* d_neff, uint32_t* d_bad, uint64_t* d_run, hipStream_t stream);
+int zmi_launch_exr_wpieces(zmi_xw_plan plan, const uint64_t* d_cfirst, const uint64_t* d_soff, const uint32_t* d_csz, uint32_t group_chunks,
+                           uint32_t wpg, uint32_t np, uint64_t* d_poff, uint32_t* d_plen, uint32_t* d_ends, hipStream_t stream);
+int zmi_launch_exr_zip(zmi_xw_plan plan, const zmi_exr_channel* d_chs, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_item_off,
+                       uint64_t bound, const uint64_t* d_soff, uint8_t* d_scan, hipStream_t stream);
+int zmi_launch_exr_wplace(zmi_xw_plan plan, uint32_t first, uint32_t count, const uint64_t* d_cfirst, const uint32_t* d_csz,
+                          const uint32_t* d_olen, const int32_t* d_st, uint64_t* d_run, uint32_t* d_cds, uint64_t* d_cpos, uint64_t* d_ppos,
+                          uint32_t* d_phead, uint64_t* d_out_off, uint32_t* d_bad, hipStream_t stream);
+int zmi_launch_exr_gather(zmi_xw_plan plan, const zmi_exr_channel* d_chs, const uint8_t* d_in, const uint64_t* d_in_off,
+                          const uint64_t* d_item_off, uint64_t bound, const uint32_t* d_csz, const uint32_t* d_cds, const uint64_t* d_cpos,
+                          uint8_t* d_out, uint64_t out_cap, hipStream_t stream);
+int zmi_launch_exr_wframe(zmi_xw_plan plan, const uint8_t* d_hdr, const uint32_t* d_csz, const uint32_t* d_cds, const uint64_t* d_cpos,
+                          const uint32_t* d_cadler, const uint64_t* d_out_off, uint32_t level, uint32_t strategy, uint8_t* d_out, uint64_t out_cap,
+                          hipStream_t stream);
+int zmi_launch_exr_wwords(zmi_xw_plan plan, const zmi_exr_channel* d_chs, const uint32_t* d_cds, const uint64_t* d_cpos,
+                          const uint64_t* d_out_off, const uint32_t* d_bad, const int32_t* d_st, uint64_t out_cap, uint32_t* d_out_len,
+                          int32_t* d_status, zmi_exr_image* d_written, zmi_exr_channel* d_written_channels, hipStream_t stream);
 }

@@ -510,6 +510,8 @@ class Engine:
         self.last_png_written = None     # png_encode: the table zmi_png_headers_dev would list for the files of the last call
         self.last_tiff_detail = None     # tiff_read: the TP_* / TE_* tensor of the last call
         self.last_exr_detail = None      # exr_read: the XE_* tensor of the last call (the first bad chunk above the low 8 bits)
+        self.last_exr_written = None     # exr_write: (uint8 [n, 88], uint8 [n, C, 24]), the records exr_headers would list for the files
+        self.last_exr_chunk_len = None   # exr_write: int32 [n, n_chunks], every chunk's dataSize
         if scratch_bytes:
             _lib.check(self.L.zmi_ctx_set_scratch_limit(self._ctx, int(scratch_bytes)), "zmi_ctx_set_scratch_limit")
 
@@ -1624,6 +1626,130 @@ class Engine:
         host = torch.cat([file_len, status[-1:].to(torch.int64)]).tolist()
         if host[1] != 0:
             raise RuntimeError("zmi_tiff_write_dev: status %d" % host[1])
+        return out[:host[0]].cpu().numpy().tobytes()
+
+    # ---- writing OpenEXR images (include/zmi355.h) ----
+    _EXR_TYPES = {torch.int32: 0, torch.float16: 1, torch.float32: 2}
+    _EXR_COMPRESSION = {"none": 0, "zips": 2, "zip": 3}
+
+    def _exr_desc(self, shape, channels, compression, tile, origin, display_window, level, strategy, piece_bytes, align):
+        """the zmi_exr_write of images of `shape` = (H, W) and channels [(name, torch dtype)] sorted by name -> (the struct, what keeps
+        its channel array alive)"""
+        import ctypes
+        h, w = (int(v) for v in shape)
+        if compression not in self._EXR_COMPRESSION:
+            raise ValueError("exr_write: compression must be 'zip', 'zips' or 'none'")
+        for _, dt in channels:
+            if dt not in self._EXR_TYPES:
+                raise ValueError("exr_write: dtype %s is not one an OpenEXR channel has (float16, float32, int32)" % (dt,))
+        arr = (_lib.ExrWriteChannel * max(1, len(channels)))(*[_lib.ExrWriteChannel(n.encode("latin-1"), self._EXR_TYPES[dt]) for n, dt in channels])
+        x0, y0 = (int(v) for v in origin)
+        dw = (x0, y0, x0 + w - 1, y0 + h - 1)
+        disp = tuple(int(v) for v in display_window) if display_window is not None else (0, 0, w - 1, h - 1)
+        tw, th = (0, 0) if tile is None else ((int(tile), int(tile)) if isinstance(tile, int) else (int(tile[0]), int(tile[1])))
+        d = _lib.ExrWrite((ctypes.c_int32 * 4)(*dw), (ctypes.c_int32 * 4)(*disp), len(channels), arr, self._EXR_COMPRESSION[compression], tw, th,
+                          0, int(piece_bytes), int(align), int(level), int(strategy))
+        return d, arr
+
+    def exr_bound(self, shape, channels, n_images=1, compression="zip", tile=None, origin=(0, 0), display_window=None, level=6, strategy=0,
+                  piece_bytes=1 << 20, align=16):
+        """the room n_images files of images of shape (H, W) need at most; channels: [(name, torch dtype)]; keywords as exr_write's"""
+        import ctypes
+        d, keep = self._exr_desc(shape, sorted(channels, key=lambda c: c[0].encode("latin-1")), compression, tile, origin, display_window, level, strategy, piece_bytes, align)
+        bound = int(self.L.zmi_exr_bound(ctypes.byref(d), int(n_images)))
+        if bound == 0:
+            raise ValueError("exr_bound: these arguments describe no image zmi_exr_write_dev writes")
+        return bound
+
+    def exr_write(self, images, channels=None, compression="zip", tile=None, origin=(0, 0), display_window=None, level=6, strategy=0,
+                  piece_bytes=1 << 20, align=16, out=None):
+        """A batch of images of ONE layout as complete OpenEXR files in one device buffer -> (out, out_off int64 [n + 1], out_len int32
+        [n], status int32 [n]): file i is out[out_off[i] : out_off[i] + out_len[i]], out_off[-1] the room the batch needs whether or
+        not it fitted (Z_BUF_ERROR with length 0 where out is too small).  images: a [N, C, H, W] or [C, H, W] device tensor of
+        float16, float32 or int32 (UINT bits) with `channels` = the C names; or a dict, or a list of dicts, name -> [H, W] tensor, of
+        mixed dtypes.  The names are sorted here, as the file wants them, and the planes laid out as exr_read returns them; every
+        image must have the layout of the first.  compression "zip" (16 scanlines a chunk), "zips" (one) or "none"; tile: None for
+        scanlines, an int or (tile_w, tile_h); origin: (xMin, yMin) of the data window; display_window None: (0, 0, W - 1, H - 1).
+        last_exr_written keeps the records exr_headers would list for the files, last_exr_chunk_len every chunk's dataSize (== the
+        chunk's raw size where it was stored raw).  No synchronisation."""
+        import ctypes
+        dense = None
+        if isinstance(images, torch.Tensor):
+            t = images if images.dim() == 4 else images.unsqueeze(0)
+            if t.dim() != 4 or t.device != self.device or t.numel() == 0:
+                raise ValueError("exr_write: a tensor must be [N, C, H, W] or [C, H, W] on %s" % (self.device,))
+            if channels is None or len(channels) != t.shape[1]:
+                raise ValueError("exr_write: a tensor needs `channels`, one name per plane")
+            names = [str(nm) for nm in channels]
+            if len(set(names)) != len(names):
+                raise ValueError("exr_write: a channel name stands twice")
+            plane = int(t.shape[2]) * int(t.shape[3]) * t.element_size()
+            if t.is_contiguous() and plane % 4 == 0 and names == sorted(names, key=lambda s: s.encode("latin-1")):
+                dense = t                                                    # the tensor IS the regions, one behind the other: no copy
+            images = [{nm: t[i, c] for c, nm in enumerate(names)} for i in range(t.shape[0])]
+        elif isinstance(images, dict):
+            images = [images]
+        if not images or not images[0]:
+            raise ValueError("exr_write: no image, or no channel")
+        names = sorted(images[0], key=lambda s: s.encode("latin-1"))
+        layout = [(nm, images[0][nm].dtype) for nm in names]
+        h, w = (int(v) for v in images[0][names[0]].shape)
+        parts, offs, at = [], [], 0
+        if dense is not None:
+            parts, offs = [dense.view(-1).view(torch.uint8)], [i * len(names) * plane for i in range(len(images))]
+        for im in ([] if dense is not None else images):
+            if sorted(im, key=lambda s: s.encode("latin-1")) != names:
+                raise ValueError("exr_write: every image must have the channels of the first")
+            offs.append(at)
+            for nm, dt in layout:
+                p = im[nm]
+                if p.dtype != dt or tuple(p.shape) != (h, w) or p.device != self.device:
+                    raise ValueError("exr_write: channel %r differs from the first image's in dtype, shape or device" % nm)
+                pad = -at % 4
+                if pad:
+                    parts.append(torch.zeros(pad, dtype=torch.uint8, device=self.device))
+                    at += pad
+                parts.append(p.contiguous().view(-1).view(torch.uint8))
+                at += int(parts[-1].numel())
+            pad = -at % 4                                                     # the next image's first plane starts at a multiple of 4
+            if pad:
+                parts.append(torch.zeros(pad, dtype=torch.uint8, device=self.device))
+                at += pad
+        data = torch.cat(parts) if len(parts) > 1 else parts[0]
+        if out is not None and (out.dtype != torch.uint8 or out.device != self.device or not out.is_contiguous()):
+            raise ValueError("exr_write: out must be a contiguous uint8 tensor on %s" % (self.device,))
+        d, keep = self._exr_desc((h, w), layout, compression, tile, origin, display_window, level, strategy, piece_bytes, align)
+        n = len(images)
+        bound = int(self.L.zmi_exr_bound(ctypes.byref(d), n))
+        if bound == 0:
+            raise ValueError("exr_write: these arguments describe no image zmi_exr_write_dev writes")
+        tw, th = (d.tile_w, d.tile_h) if d.tile_w else (w, 16 if d.compression == 3 else 1)
+        nc = -(-w // tw) * -(-h // th)
+        if out is None:
+            out = torch.empty(bound, dtype=torch.uint8, device=self.device)
+        in_off = torch.tensor(offs, dtype=torch.int64).to(self.device)
+        out_off = torch.zeros(n + 1, dtype=torch.int64, device=self.device)
+        out_len = torch.zeros(n, dtype=torch.int32, device=self.device)
+        status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        chunk_len = torch.zeros((n, nc), dtype=torch.int32, device=self.device)
+        written = torch.zeros((n, EXR_IMAGE_BYTES), dtype=torch.uint8, device=self.device)
+        wch = torch.zeros((n, len(layout), EXR_CHANNEL_BYTES), dtype=torch.uint8, device=self.device)
+        self.last_exr_written, self.last_exr_chunk_len = (written, wch), chunk_len
+        _lib.check(self.L.zmi_exr_write_dev(self._ctx, ctypes.byref(d), data.data_ptr(), in_off.data_ptr(), n,
+                                            out.data_ptr() if out.numel() else None, int(out.numel()), out_off.data_ptr(), out_len.data_ptr(),
+                                            chunk_len.data_ptr(), written.data_ptr(), wch.data_ptr(), status.data_ptr(), _stream_ptr()),
+                   "zmi_exr_write_dev")
+        return out, out_off, out_len, status
+
+    def save_exr(self, image, **kw):
+        """One image (a [C, H, W] tensor with channels=..., or a dict name -> [H, W] tensor) -> the bytes of its .exr file; a status
+        that is not 0 raises.  Keywords as exr_write's."""
+        out, out_off, out_len, status = self.exr_write(image, **kw)
+        if int(status.numel()) != 1:
+            raise ValueError("save_exr: one image")
+        host = torch.cat([out_len.to(torch.int64), status.to(torch.int64)]).tolist()
+        if host[1] != 0:
+            raise RuntimeError("zmi_exr_write_dev: status %d" % host[1])
         return out[:host[0]].cpu().numpy().tobytes()
 
     # ---- writing ZIP archives (include/zmi355.h, DESIGN.md section 21) ----

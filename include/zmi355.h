@@ -1110,10 +1110,10 @@ int zmi_tiff_write_dev(zmi_ctx* ctx, const zmi_tiff_write* w, const void* d_in, 
                        void* d_out, uint64_t out_cap, uint64_t* d_file_len, uint32_t* d_seg_len /* NULL or n_segs */,
                        int32_t* d_status /* n_segs */, int32_t* d_file_status, zmi_tiff_page* d_written /* NULL or 1 */, void* stream);
 
-/* ---- reading OpenEXR images (ZIP / ZIPS / NONE): the attribute list, a batch inflate of the chunks, the unzip --------------------------
+/* ---- reading OpenEXR images (ZIP / ZIPS / PXR24 / NONE): the attribute list, a batch inflate of the chunks, the unzip ------------------
  * Two calls, both asynchronous on `stream`, neither synchronises with the host, every per-file failure is a device word.  File i is
  * d_in[d_in_off[i] .. + d_in_len[i]), at any alignment.  OpenEXR is not part of the reference project: the contract is the format, as
- * stated here.  Not built, each a change of its own: RLE, PIZ, PXR24, B44, DWA; subsampled channels, mip / rip levels,
+ * stated here.  Not built, each a change of its own: RLE, PIZ, B44, DWA; subsampled channels, mip / rip levels,
  * multi-part and deep files; a selection of rows or tiles inside a file; conversion of HALF to float.
  *
  * The format.  All integers and floats are little-endian.
@@ -1145,6 +1145,24 @@ int zmi_tiff_write_dev(zmi_ctx* ctx, const zmi_tiff_write* w, const void* d_in, 
  *               (t[i - 1] + d[i] - 128) mod 256 -- equivalently t[i] = (sum_{k <= i} d[k] - 128 i) mod 256: an inclusive byte sum with 128
  *               subtracted at odd i.  Interleave: with h = (n + 1) / 2, raw[2 i] = t[i] and raw[2 i + 1] = t[h + i].
  *               Example: d = 00 80 80 80 e6 19 bd 84 82 82 6a gives raw = 00 3c 00 40 00 42 00 44 66 2e ff.
+ *   PXR24       compression 5: 16 scanlines per chunk, or one tile; chunk headers, the table, the line orders and the raw rule
+ *               (dataSize == n: the n raw bytes, floats at their full 32 bits) exactly as for ZIP.  dataSize < n: one zlib stream that
+ *               inflates to exactly m = rows * sum_c width * p_c bytes with p = 4 / 2 / 3 for UINT / HALF / FLOAT (m <= n, and m < n as
+ *               soon as there is a FLOAT channel).  The inflated bytes: for every scanline of the chunk in increasing y, for every
+ *               channel in list order, a run of p * w bytes (w = the pixels of that row in the chunk): p planes of w bytes, most
+ *               significant byte first, that hold diff[x] = v[x] - v[x - 1] mod 2^(8p) with v[-1] = 0 at the start of every run -- byte
+ *               k of plane j is (diff[k] >> 8 (p - 1 - j)) & 255.  v is the UINT value, the HALF's 16 bits, and f24(bits) of a FLOAT.
+ *               Reading accumulates v[x] = (v[x - 1] + diff[x]) mod 2^(8p) and writes v, for FLOAT v << 8: the low byte of every float
+ *               read from a compressed chunk is 0.  f24 of the 32 float bits u, with s = u & 0x80000000, e = u & 0x7f800000, m = u &
+ *               0x007fffff: if e == 0x7f800000 and m != 0, m >>= 8 and i = (e >> 8) | m | (m == 0 ? 1 : 0) -- a NaN stays a NaN --; if
+ *               e == 0x7f800000 and m == 0, i = e >> 8; otherwise i = ((e | m) + (m & 0x80)) >> 8, and if i >= 0x7f8000 then i = (e |
+ *               m) >> 8 -- rounding never produces an infinity.  f24 = (s >> 8) | i.  Pinned: 3f000000 -> 3f0000, 3f8000ff -> 3f8001,
+ *               3f80007f -> 3f8000, 3f800080 -> 3f8001, 7f7fffff -> 7f7fff, 7f800000 -> 7f8000, 7f800001 -> 7f8001, ffc12345 ->
+ *               ffc123, 80000000 -> 800000, 000000ff -> 000001, bfc00000 -> bfc000.
+ *               Example: one row of width 3, channels G HALF = 1, 2, 3; Z FLOAT = 0.5, -1.5, 2.5; id UINT = 7, 5, 0x01020304.  Raw, 30
+ *               bytes: 003c 0040 0042 0000003f 0000c0bf 00002040 07000000 05000000 04030201.  Inflated, 27 bytes: 3c 04 02 00 00 00 |
+ *               3f 80 80 00 c0 60 00 00 00 | 00 ff 01 00 ff 02 00 ff 02 07 fe ff.  (zlib level 6 makes 33 bytes of them, so a writer
+ *               stores this chunk raw; a crafted file may still carry the stream.)
  *
  * zmi_exr_headers_dev   one lane per file walks the attributes (the chain is serial; the batch is the parallelism) and writes one
  *               zmi_exr_image per file and the first chan_cap channels of file i to d_channels[i * chan_cap ..) (the records behind the
@@ -1158,7 +1176,7 @@ int zmi_tiff_write_dev(zmi_ctx* ctx, const zmi_tiff_write* w, const void* d_in, 
  *                       offset table that leaves the file; more than ZMI_EXR_ATTRS_MAX attributes (the walk is one lane's: it ends
  *                       there, as the TIFF chain ends at 65 535 IFDs).  Only version, the tiled flag and the status are set.
  *   ZMI_XE_KIND         deep or multi-part flags
- *   ZMI_XE_COMPRESSION  anything but 0, 2, 3: the file is listed with its dimensions and channels, and flagged
+ *   ZMI_XE_COMPRESSION  anything but 0, 2, 3, 5: the file is listed with its dimensions and channels, and flagged
  *   ZMI_XE_SAMPLING     a sampling other than 1
  *   ZMI_XE_LEVELS       mipmap or ripmap (n_chunks: those of level 0)
  *   ZMI_XE_CHANNELS     more than chan_cap channels; n_channels still holds the true count, row_bytes and region_bytes are 0
@@ -1179,10 +1197,12 @@ int zmi_tiff_write_dev(zmi_ctx* ctx, const zmi_tiff_write* w, const void* d_in, 
  *               front, each rounded up to out_align; d_out_off[n_sel] = the room the selection needs; a flagged or failed slot has
  *               length 0; nothing at or behind d_out + out_cap and nothing in the gaps is written.
  *   Reading     one kernel reads every chunk's table entry and header; compressed chunks go through the batch decoder with
- *               ZMI_WRAP_ZLIB and capacity n into scratch, every chunk at a multiple of 16, and the decoder checks the
- *               Adler-32; raw chunks go through the range copy into the same scratch; the unzip kernel (exr_kernels.h) undoes the
- *               predictor and the interleave and writes every run at its place in its plane; one kernel writes the slot's words.
- *               flags must be 0.
+ *               ZMI_WRAP_ZLIB and capacity n (PXR24: m, in a place of n bytes) into scratch, every chunk at a multiple of 16, and
+ *               the decoder checks the Adler-32; raw chunks go through the range copy into the same scratch; the unzip kernel
+ *               (exr_kernels.h) undoes the predictor and the interleave and writes every run at its place in its plane -- the streams
+ *               of PXR24 files go through zmi_exr_pxr24_undo_kernel instead: one wave per (chunk, row, channel) run, a prefix sum of
+ *               16-, 24- or 32-bit words --; one kernel writes the slot's words.  One call may mix NONE, ZIPS, ZIP and PXR24 files in
+ *               any slot order.  flags must be 0.
  *   d_status / d_detail   after the record's own flag (Z_DATA_ERROR for MAGIC and HEADER, Z_BUF_ERROR for CHANNELS, else
  *               Z_VERSION_ERROR; detail = the ZMI_XE_* code) the first of these that holds for any chunk of the file; d_detail = the
  *               code, with the index of the first chunk that has it above the low 8 bits:
@@ -1193,14 +1213,14 @@ int zmi_tiff_write_dev(zmi_ctx* ctx, const zmi_tiff_write* w, const void* d_in, 
  *                                               file; compression NONE with dataSize != n
  *               Z_DATA_ERROR / ZMI_XE_MISSING   a table entry of 0, the mark of an unfinished file
  *               Z_DATA_ERROR / ZMI_XE_DATA      a corrupt stream, a wrong Adler-32, FDICT
- *               Z_DATA_ERROR / ZMI_XE_LENGTH    the stream does not end at exactly n bytes
+ *               Z_DATA_ERROR / ZMI_XE_LENGTH    the stream does not end at exactly n bytes (PXR24: m bytes)
  *   d_out_len[j] = the region's size with status 0, otherwise 0.  Never status 0 with wrong bytes; one bad file does not touch its
  *   neighbours.  n_sel 0 writes d_out_off[0] = 0 and nothing else.  Bytes and words do not depend on the alignment of d_in, on the
  *   slot index, on n_files or on the decode-kernel selection.
- *   Scratch of the context: 40 bytes per slot, 80 per chunk of chunk_cap, 8 per 1024 bytes of decoded_bytes; the inflated chunks,
+ *   Scratch of the context: 40 bytes per slot, 100 per chunk of chunk_cap, 8 per 1024 bytes of decoded_bytes; the inflated chunks,
  *   decoded_bytes + 16 bytes per chunk + 96; and the decoder's, sized by this call.  Scratch that cannot be reserved is ZMI_E_NOMEM.
  *   Event timing: 5 = headers; slot and chunk tables, plans, 3 / 6 = decode, resolve, 7 = the copies of raw chunks, 2 = block sums, their
- *   scans and the unzip, 4 = the slot words. */
+ *   scans, the unzip and the PXR24 undo, 4 = the slot words. */
 #define ZMI_XE_MAGIC 1        /* zmi_exr_image.status and the slot's detail: Z_DATA_ERROR */
 #define ZMI_XE_HEADER 2       /* Z_DATA_ERROR */
 #define ZMI_XE_KIND 3         /* Z_VERSION_ERROR */
@@ -1236,6 +1256,7 @@ typedef struct zmi_exr_image {      /* 88 bytes */
 } zmi_exr_image;
 uint32_t zmi_exr_trip(void);    /* output bytes one trip of the unzip kernel covers per wave (for tests that place run lengths around it) */
 uint32_t zmi_exr_piece(void);   /* the longest piece of a run one work item of the unzip kernel writes: a whole number of trips */
+uint32_t zmi_exr_pxr24_trip(void);   /* pixels one trip of the PXR24 undo kernel (and of the forward kernel) covers per wave */
 int zmi_exr_headers_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n_files,
                         zmi_exr_image* d_images, zmi_exr_channel* d_channels /* n_files * chan_cap */, uint32_t chan_cap, void* stream);
 int zmi_exr_read_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, const zmi_exr_image* d_images,
@@ -1243,7 +1264,7 @@ int zmi_exr_read_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, c
                      uint32_t chunk_cap, uint64_t decoded_bytes, uint32_t flags, uint32_t out_align, void* d_out, uint64_t out_cap,
                      uint64_t* d_out_off /* n_sel + 1 */, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, void* stream);
 
-/* ---- writing OpenEXR images (ZIP / ZIPS / NONE): the forward zip, deflate in pieces, chunks and offset table ------------------------------
+/* ---- writing OpenEXR images (ZIP / ZIPS / PXR24 / NONE): the forward transform, deflate in pieces, chunks and offset table -----------------
  * The inverse of the two calls above: a batch of images of ONE layout (a frame sequence) in device memory becomes a batch of complete
  * single-part .exr files in one device buffer, one asynchronous call on `stream` that never synchronises with the host; every per-image
  * failure is a device word.  The layout is the caller's (*w and the channel list are host memory, read during the call), so the chunk
@@ -1253,7 +1274,7 @@ int zmi_exr_read_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, c
  *   Arguments   ZMI_E_ARG as the return value, with a zmi_last_error text and nothing launched: an inverted window; a width, height,
  *               pixel count, row, region or chunk that does not fit 32 bits (what the reader flags ZMI_XE_BIG); zero channels; a pixel
  *               type above 2; a name that is NULL, empty or longer than 255 bytes; names that are not strictly ascending bytewise (the
- *               order every other writer keeps, so the file reads elsewhere); a compression other than 0, 2, 3; exactly one of tile_w /
+ *               order every other writer keeps, so the file reads elsewhere); a compression other than 0, 2, 3, 5; exactly one of tile_w /
  *               tile_h being 0; piece_bytes outside 1 .. 2^30; level outside -1 .. 9; strategy outside 0 .. 4; out_align not a power of
  *               two in 1 .. 4096; flags other than 0; a file bound above 2^32 - 1; more than 2^31 - 1 pieces or chunks in the call;
  *               a NULL table that is not optional.
@@ -1287,9 +1308,16 @@ int zmi_exr_read_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, c
  *               + 128) mod 256.  The candidate stream is the IDAT payload zmi_png_encode_dev would write for d: the two zlib header bytes
  *               zmi_deflate_stream_dev writes for that level and strategy; d in pieces of piece_bytes, each compressed exactly as
  *               zmi_deflate_pieces_dev(ZMI_STREAM_INDEPENDENT) does with max_len = piece_bytes; the big-endian Adler-32 of d.
+ *   PXR24       compression 5 (16 scanlines a chunk, or one tile): d is the chunk's m bytes of byte planes stated with the reader --
+ *               zmi_exr_pxr24_forward_kernel: a work item is one trip of a run, f24 on FLOAT, the predecessor from the lane below,
+ *               no scan -- and everything behind it is the ZIP path with length m: pieces, Adler-32, candidate.  The raw rule compares
+ *               the candidate with n, and a chunk stored raw holds the n raw bytes with full 32-bit floats.  Writing is therefore
+ *               lossy for FLOAT channels only, and only in the chunks that are stored compressed: such a float reads back as
+ *               f24(bits) << 8.  UINT and HALF are exact.  zmi_exr_bound is unchanged.
  *   Raw rule    the reader takes dataSize == n to mean raw bytes, so: where the candidate's length is >= n the chunk's data is the n
  *               RAW bytes (not d) and dataSize = n; otherwise the data is the candidate and dataSize < n.  Level 0 therefore stores
- *               every chunk raw, and so does a chunk of 2 bytes; compression NONE skips the encoder altogether.  A file's bytes are a
+ *               every chunk raw (under PXR24: every chunk without a FLOAT channel; m + the stored blocks' bytes may stay below n), and
+ *               so does a chunk of 2 bytes; compression NONE skips the encoder altogether.  A file's bytes are a
  *               function of its pixels and *w alone -- not of n_images, the image's index, the alignment of d_in, the scratch limit,
  *               the launch grouping or the wave schedule.
  *   Words       as zmi_png_encode_dev: d_out_off[i] = the lengths in front, each rounded up to out_align; d_out_off[n_images] = the room
@@ -1309,16 +1337,16 @@ int zmi_exr_read_dev(zmi_ctx* ctx, const void* d_in, const uint64_t* d_in_off, c
  *               and item counts are device scans over the chunks of the call.  Raw chunks are gathered from the planes straight into
  *               the file; no copy of the image stands in scratch.
  *   Scratch of the context: d of every chunk of the call, each at a multiple of 16, NOT capped by the scratch limit (nothing under
- *   NONE); 56 bytes per chunk, 36 bytes and 1 bit per piece, 4 per image, 8 per launch group, 24 per channel and the header's bytes; one
+ *   NONE; m of them under PXR24); 72 bytes per chunk, 36 bytes and 1 bit per piece, 4 per image, 8 per launch group, 24 per channel and the header's bytes; one
  *   group's slots as in zmi_zip_write_dev.  Scratch that cannot be reserved is ZMI_E_NOMEM.
- *   Event timing, as zmi_tiff_write_dev: 3 = the forward zip kernel, 0 = Adler-32 of the pieces and the fold per chunk, 1 / 5 / 2 =
+ *   Event timing, as zmi_tiff_write_dev: 3 = the forward zip kernel (PXR24: the forward kernel), 0 = Adler-32 of the pieces and the fold per chunk, 1 / 5 / 2 =
  *   match search, parse, encode, 7 = the chunk and piece tables, places, pack and the raw gather, 4 = the fixed bytes and the words. */
 typedef struct zmi_exr_write_channel { const char* name; int32_t pixel_type; } zmi_exr_write_channel;   /* 0 UINT, 1 HALF, 2 FLOAT */
 typedef struct zmi_exr_write {      /* host memory, read during the call */
     int32_t  data_window[4], display_window[4];   /* xMin, yMin, xMax, yMax */
     uint32_t n_channels;
     const zmi_exr_write_channel* channels;        /* sorted by name */
-    uint32_t compression;             /* 0 NONE, 2 ZIPS, 3 ZIP */
+    uint32_t compression;             /* 0 NONE, 2 ZIPS, 3 ZIP, 5 PXR24 */
     uint32_t tile_w, tile_h;          /* both 0: scanlines */
     uint32_t flags, piece_bytes, out_align;
     int32_t  level, strategy;

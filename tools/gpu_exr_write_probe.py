@@ -8,7 +8,11 @@ Pixels: gen_shards data, the planes of the regions as they stand.  Workloads, th
 RGBA HALF in chunks of 16 scanlines; one 4096 x 4096 RGBA HALF; 4096 tiles of 256 x 256 FLOAT in one file.  Every written batch is read
 back by zmi_exr_read_dev and compared with the pixels.  One JSON line per run; the committed one is profiles/exr_write.json.
 
-    python tools/gpu_exr_write_probe.py [--frames 64] [--big 4096] [--tiles 4096] [--reps 5] [--out profiles/exr_write.json]
+--compression pxr24 writes the same workloads with compression 5: the PXR24 forward kernel in the forward slot,
+the yardstick on the chunks' forward bytes (m a chunk, made on the host), and FLOAT pixels read back as f24(..) << 8 in the chunks that
+were not stored raw.  The committed line is in profiles/exr_pxr24.json.
+
+    python tools/gpu_exr_write_probe.py [--compression zip] [--frames 64] [--big 4096] [--tiles 4096] [--reps 5] [--out profiles/exr_write.json]
 """
 import argparse
 import concurrent.futures
@@ -21,6 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np      # noqa: E402
 import torch            # noqa: E402
 from zlib_rs_amd.engine import Engine, WRAP_ZLIB   # noqa: E402
+from gpu_exr_probe import HALF, FLOAT, f24, pxr24_forward   # noqa: E402  (tools/: the host side of PXR24)
 
 SLOTS = {"adler": 0, "match": 1, "encode": 2, "forward": 3, "words": 4, "parse": 5, "tables_pack_gather": 7}
 
@@ -53,7 +58,7 @@ def med(xs):
     return xs[len(xs) // 2], xs[-1] - xs[0]
 
 
-def measure(e, n_files, n_ch, H, W, dtype, tile, reps, pool):
+def measure(e, n_files, n_ch, H, W, dtype, tile, reps, pool, compression="zip"):
     dev = e.device
     size = 2 if dtype == torch.float16 else 4
     total = n_files * n_ch * H * W * size
@@ -62,6 +67,8 @@ def measure(e, n_files, n_ch, H, W, dtype, tile, reps, pool):
     images = pixels.view(dtype).view(n_files, n_ch, H, W)
     names = ["A", "B", "G", "R"][:n_ch] if n_ch > 1 else ["Z"]
     kw = dict(channels=names, tile=tile or None, level=6, piece_bytes=1 << 20, align=16)
+    if compression != "zip":
+        kw["compression"] = compression
     bound = e.exr_bound((H, W), [(n, dtype) for n in names], n_files, tile=tile or None)
     out = torch.empty(bound, dtype=torch.uint8, device=dev)
     _, off, ln, st = e.exr_write(images, out=out, **kw)
@@ -73,14 +80,21 @@ def measure(e, n_files, n_ch, H, W, dtype, tile, reps, pool):
     assert all(b.readable) and b.shape(0) == (n_ch, H, W)
     back = torch.empty(total, dtype=torch.uint8, device=dev)
     _, _, _, rst = e.exr_read(b, out=back, align=4)
-    assert bool((rst == 0).all()) and torch.equal(back, pixels), "the written files do not read back as the pixels"
-    del back, b
     th, tw = (tile, tile) if tile else (16, W)
     boxes = [(x0, y0, min(tw, W - x0), min(th, H - y0)) for y0 in range(0, H, th) for x0 in range(0, W, tw)]
     raws = [w * h * n_ch * size for _, _, w, h in boxes] * n_files
+    want = pixels
+    if compression == "pxr24" and dtype == torch.float32:
+        # PXR24 keeps 24 bits of a FLOAT in the chunks that shrank (one file of one channel in whole tiles: the mask is a grid)
+        assert n_files == 1 and n_ch == 1 and tile and H % tile == 0 and W % tile == 0
+        bits = pixels.cpu().numpy().view("<u4").reshape(H, W)
+        shrank = (clen.reshape(H // tile, W // tile) != tile * tile * size).repeat(tile, axis=0).repeat(tile, axis=1)
+        want = torch.from_numpy(np.where(shrank, f24(bits) << np.uint32(8), bits).astype("<u4").view(np.uint8).reshape(-1)).to(dev)
+    assert bool((rst == 0).all()) and torch.equal(back, want), "the written files do not read back as the pixels"
+    del back, b, want
     res = {"files": n_files, "channels": n_ch, "height": H, "width": W, "pixel_bytes_each": size, "tile": tile, "chunks": len(raws),
            "pixel_bytes": total, "file_bytes": int(sum(ln_h)), "chunks_stored_raw": int((clen.reshape(-1) == np.array(raws)).sum()),
-           "trip": int(e.L.zmi_exr_zip_trip())}
+           "compression": compression, "trip": int(e.L.zmi_exr_pxr24_trip()) if compression == "pxr24" else int(e.L.zmi_exr_zip_trip())}
 
     def call():
         e.exr_write(images, out=out, **kw)
@@ -117,7 +131,10 @@ def measure(e, n_files, n_ch, H, W, dtype, tile, reps, pool):
 
     def one(job):
         f, (x0, y0, w, h) = job
-        return zip_forward(np.ascontiguousarray(host[f, :, y0:y0 + h, x0 * size:(x0 + w) * size].transpose(1, 0, 2)).reshape(-1))
+        rows = np.ascontiguousarray(host[f, :, y0:y0 + h, x0 * size:(x0 + w) * size].transpose(1, 0, 2))
+        if compression == "pxr24":
+            return np.frombuffer(pxr24_forward(rows, HALF if size == 2 else FLOAT)[0], dtype=np.uint8)
+        return zip_forward(rows.reshape(-1))
 
     ds = list(pool.map(one, [(f, box) for f in range(n_files) for box in boxes]))
     offs = np.zeros(len(ds), dtype=np.int64)
@@ -128,10 +145,11 @@ def measure(e, n_files, n_ch, H, W, dtype, tile, reps, pool):
     flat = np.zeros(at + 64, dtype=np.uint8)
     for k, d in enumerate(ds):
         flat[offs[k]:offs[k] + d.size] = d
-    del ds, host
+    del host
     d_in, d_off = torch.from_numpy(flat).to(dev), torch.from_numpy(offs).to(dev)
-    d_len = torch.tensor(raws, dtype=torch.int32, device=dev)
-    max_len = max(raws)
+    d_len = torch.tensor([d.size for d in ds], dtype=torch.int32, device=dev)
+    max_len = max(d.size for d in ds)
+    del ds
     yo, yl, ys = e.deflate_batch(d_in, d_off, d_len, max_len, level=6, wrap=WRAP_ZLIB)
     torch.cuda.synchronize()
     assert bool((ys == 0).all())
@@ -155,23 +173,25 @@ def main():
     ap.add_argument("--tiles", type=int, default=4096)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--compression", choices=["zip", "pxr24"], default="zip")
     a = ap.parse_args()
+    comp = a.compression
     if not torch.cuda.is_available():
         sys.exit("gpu_exr_write_probe needs an MI355X: nothing is measured without one")
     e = Engine(0)
     L, vp, u32, i32 = e.L, C.c_void_p, C.c_uint32, C.c_int
     L.zmi_ctx_set_timing.argtypes = [vp, i32]
     L.zmi_ctx_get_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(u32)]
-    line = {"probe": "exr_write", "level": 6, "reps": a.reps, "device": torch.cuda.get_device_name(0)}
+    line = {"probe": "exr_write" if comp == "zip" else "exr_write_pxr24", "level": 6, "reps": a.reps, "device": torch.cuda.get_device_name(0)}
     with concurrent.futures.ThreadPoolExecutor(16) as pool:
         if a.frames:
-            line["frames_2048x1080_rgba_half"] = measure(e, a.frames, 4, 1080, 2048, torch.float16, 0, a.reps, pool)
+            line["frames_2048x1080_rgba_half"] = measure(e, a.frames, 4, 1080, 2048, torch.float16, 0, a.reps, pool, comp)
         if a.big:
-            line["one_%d_square_rgba_half" % a.big] = measure(e, 1, 4, a.big, a.big, torch.float16, 0, a.reps, pool)
+            line["one_%d_square_rgba_half" % a.big] = measure(e, 1, 4, a.big, a.big, torch.float16, 0, a.reps, pool, comp)
         if a.tiles:
             across = int(round(a.tiles ** 0.5))
             assert across * across == a.tiles
-            line["tiles_256_float"] = measure(e, 1, 1, across * 256, across * 256, torch.float32, 256, a.reps, pool)
+            line["tiles_256_float"] = measure(e, 1, 1, across * 256, across * 256, torch.float32, 256, a.reps, pool, comp)
     text = json.dumps(line)
     print(text)
     if a.out:

@@ -121,6 +121,8 @@ def lib():
     L.zmi_exr_trip.argtypes = []
     L.zmi_exr_piece.restype = u32
     L.zmi_exr_piece.argtypes = []
+    L.zmi_exr_pxr24_trip.restype = u32
+    L.zmi_exr_pxr24_trip.argtypes = []
     L.zmi_exr_headers_dev.argtypes = [vp, vp, vp, vp, u32, vp, vp, u32, vp]
     L.zmi_exr_read_dev.argtypes = [vp, vp, vp, vp, vp, vp, u32, u32, vp, u32, u32, u64, u32, u32, vp, u64, vp, vp, vp, vp, vp]
     # writing TIFF files: the forward predictor, deflate in pieces, the IFD (csrc/tiff_write_kernels.h, zmi_api.hip); w: a TiffWrite

@@ -1,4 +1,4 @@
-// exr_kernels.h -- reading OpenEXR images with ZIP / ZIPS compression (zmi_exr_headers_dev / zmi_exr_read_dev, include/zmi355.h, which
+// exr_kernels.h -- reading OpenEXR images with ZIP / ZIPS / PXR24 compression (zmi_exr_headers_dev / zmi_exr_read_dev, include/zmi355.h, which
 // states the format); included by pack.hip.
 //
 // A file is a list of attributes, a table of chunk positions and the chunks: 16 scanlines (ZIP), one (ZIPS, NONE) or one tile each, every
@@ -12,6 +12,7 @@
 //   zmi_exr_blocksum_kernel  one byte sum per EXR_BLOCK bytes of every inflated chunk, and zmi_exr_blockscan_kernel, their scan per chunk:
 //                            the carries of the unzip
 //   zmi_exr_unzip_kernel     the hot path, below
+//   zmi_exr_pxr24_undo_kernel   the same for the streams of PXR24 files, which inflate to byte planes of differences: further below
 //   zmi_exr_finish_kernel    one wave per slot: the slot's final words
 #pragma once
 
@@ -46,6 +47,8 @@ static __device__ __forceinline__ uint32_t xr_lines(uint32_t compression) {
     return compression < 3u ? 1u : (compression == 3u || compression == 5u ? 16u : (compression == 9u ? 256u : 32u));
 }
 static __device__ __forceinline__ uint32_t xr_type_bytes(int32_t pixel_type) { return pixel_type == 1 ? 2u : 4u; }
+// the bytes of a sample inside a PXR24 stream: a FLOAT keeps 24 bits
+static __device__ __forceinline__ uint32_t xr_p24_bytes(int32_t pixel_type) { return pixel_type == 1 ? 2u : (pixel_type == 2 ? 3u : 4u); }
 
 // What follows from the windows, the compression, the tile description and the channel types alone: the sizes the record keeps.
 struct xr_geo {
@@ -194,7 +197,7 @@ __global__ void __launch_bounds__(64) zmi_exr_headers_kernel(const uint8_t* __re
         }
     }
     if (version & 0x1800u) r.status = ZMI_XE_KIND;
-    else if (comp != 0u && comp != 2u && comp != 3u) r.status = ZMI_XE_COMPRESSION;
+    else if (comp != 0u && comp != 2u && comp != 3u && comp != 5u) r.status = ZMI_XE_COMPRESSION;
     else if (sampled) r.status = ZMI_XE_SAMPLING;
     else if (r.tiled && (mode & 15u) != 0u) r.status = ZMI_XE_LEVELS;
     else if (many) r.status = ZMI_XE_CHANNELS;
@@ -206,7 +209,7 @@ __global__ void __launch_bounds__(64) zmi_exr_headers_kernel(const uint8_t* __re
 // derived again and compared).
 static __device__ __forceinline__ bool xr_rec_ok(const zmi_exr_image& r, const zmi_exr_channel* ch, uint32_t chan_cap, uint64_t L) {
     if ((r.version & 0xFFu) != 2u || (r.version & 0x1800u) != 0u || (r.tiled != 0u) != ((r.version & 0x200u) != 0u) || r.tiled > 1u) return false;
-    if (r.compression != 0u && r.compression != 2u && r.compression != 3u) return false;
+    if (r.compression != 0u && r.compression != 2u && r.compression != 3u && r.compression != 5u) return false;
     if (r.lines_per_chunk != xr_lines(r.compression) || r.line_order > 2u) return false;
     if (r.data_window[2] < r.data_window[0] || r.data_window[3] < r.data_window[1]) return false;
     if (r.n_channels == 0u || r.n_channels > chan_cap) return false;
@@ -286,8 +289,9 @@ static __device__ __forceinline__ void xr_chunk_of(const zmi_exr_image& r, uint3
 
 // One thread per chunk q of the table of chunk_cap entries; the chunks of slot j are ch_off[j] .. ch_off[j + 1).  For a chunk of a live
 // slot whose table entry and header are right: csz[q] = its raw size n, zin_off[q] = where its data stands in d_in, and either zin_len[q]
-// = dataSize (a zlib stream, nblk[q] blocks of byte sums) or rawlen[q] = n (stored raw); items[q] = the pieces of its runs.  Every other
-// entry is all zeros but fl[q] (EXR_FL_*).
+// = dataSize (a zlib stream, nblk[q] blocks of byte sums) or rawlen[q] = n (stored raw); items[q] = the pieces of its runs; cm[q] = the
+// bytes its stream must inflate to: n, but m for a PXR24 stream (compression 5), which has no blocks and no items of the unzip --
+// pitems[q] = its runs, the items of zmi_exr_pxr24_undo_kernel.  Every other entry is all zeros but fl[q] (EXR_FL_*).
 __global__ void __launch_bounds__(256) zmi_exr_chunks_kernel(const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
                                                              const uint32_t* __restrict__ in_len, const zmi_exr_image* __restrict__ images,
                                                              const zmi_exr_channel* __restrict__ chans, uint32_t chan_cap,
@@ -295,11 +299,12 @@ __global__ void __launch_bounds__(256) zmi_exr_chunks_kernel(const uint8_t* __re
                                                              const uint32_t* __restrict__ live, uint32_t chunk_cap, uint64_t* __restrict__ zin_off,
                                                              uint32_t* __restrict__ zin_len, uint32_t* __restrict__ csz, uint32_t* __restrict__ rawlen,
                                                              uint32_t* __restrict__ fl, uint32_t* __restrict__ items, uint32_t* __restrict__ nblk,
-                                                             uint32_t* __restrict__ cslot) {
+                                                             uint32_t* __restrict__ cslot, uint32_t* __restrict__ cm,
+                                                             uint32_t* __restrict__ pitems) {
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
     if (q >= chunk_cap) return;
     uint64_t zo = 0ull;
-    uint32_t zl = 0u, n_raw = 0u, rl = 0u, flag = 0u, it = 0u, nb = 0u, slot = 0u;
+    uint32_t zl = 0u, n_raw = 0u, rl = 0u, flag = 0u, it = 0u, nb = 0u, slot = 0u, want = 0u, pit = 0u;
     if ((uint64_t)q < ch_off[n_sel]) {
         const uint32_t j = xr_find(ch_off, n_sel, q);
         slot = j;
@@ -312,10 +317,11 @@ __global__ void __launch_bounds__(256) zmi_exr_chunks_kernel(const uint8_t* __re
             const uint32_t k = q - (uint32_t)ch_off[j];
             xr_chunk c;
             xr_chunk_of(r, k, &c);
-            uint32_t per_px = 0u, pieces = 0u;
+            uint32_t per_px = 0u, pieces = 0u, per_p = 0u;
             for (uint32_t x = 0u; x < r.n_channels; ++x) {
                 const uint32_t s = xr_type_bytes(ch[x].pixel_type);
                 per_px += s;
+                per_p += xr_p24_bytes(ch[x].pixel_type);
                 pieces += (c.cw * s + EXR_PIECE - 1u) / EXR_PIECE;          // (a chunk's raw size fits 32 bits, so does a run's)
             }
             const uint32_t n = c.rows * c.cw * per_px;
@@ -332,15 +338,17 @@ __global__ void __launch_bounds__(256) zmi_exr_chunks_kernel(const uint8_t* __re
                 if (!ok || ds < 0 || (uint32_t)ds > n || (uint64_t)ds > L - e - hdr || (r.compression == 0u && (uint32_t)ds != n)) flag = EXR_FL_CHUNK;
                 else {
                     zo = in_off[f] + e + hdr;
-                    n_raw = n;
-                    if ((uint32_t)ds == n) rl = n;
-                    else { zl = (uint32_t)ds; nb = (n + EXR_BLOCK - 1u) / EXR_BLOCK; }
+                    n_raw = want = n;
                     it = c.rows * pieces;
+                    if ((uint32_t)ds == n) rl = n;
+                    else if (r.compression == 5u) { zl = (uint32_t)ds; want = c.rows * c.cw * per_p; it = 0u; pit = c.rows * r.n_channels; }
+                    else { zl = (uint32_t)ds; nb = (n + EXR_BLOCK - 1u) / EXR_BLOCK; }
                 }
             }
         }
     }
     zin_off[q] = zo; zin_len[q] = zl; csz[q] = n_raw; rawlen[q] = rl; fl[q] = flag; items[q] = it; nblk[q] = nb; cslot[q] = slot;
+    cm[q] = want; pitems[q] = pit;
 }
 
 // ---- the unzip (the predictor and the interleave of a ZIP / ZIPS chunk) and the placement ----------------------------------------------------
@@ -571,6 +579,119 @@ __global__ void __launch_bounds__(64) zmi_exr_unzip_kernel(const zmi_exr_image* 
     }
 }
 
+// ---- the PXR24 undo (compression 5; include/zmi355.h states the layout) -----------------------------------------------------------------------
+// The inflated chunk is d[0 .. m): for every row, for every channel, a run of p planes of w bytes, most significant first, that hold
+// the differences of neighbouring samples as p-byte integers (p = 2 / 3 / 4 for HALF / FLOAT / UINT).  The scan is a prefix sum of
+// 16-, 24- or 32-bit words and spans one run only, so there are no block sums: the work item is a whole (chunk, row, channel) run, one
+// wave an item, the items numbered by a scan of their own (pitems of zmi_exr_chunks_kernel).  A trip is EXR_P24_TRIP pixels, four
+// consecutive ones a lane: the lane's 4 bytes of every plane are two aligned dwords joined by v_alignbyte (a plane starts at any byte
+// offset; every address depends on the lane; a dword is loaded only where it holds a byte of the lane's own), the
+// planes are transposed into per-pixel words with v_perm_b32, the lane sums its four, the lane totals go through the DPP wave scan, the
+// carry from trip to trip is wave-uniform; sums are taken in 32 bits and masked to 8 p bits (2^(8p) divides 2^32), FLOAT is shifted
+// left by 8.  Stores: 16 bytes a lane for UINT and FLOAT where the destination stands at a multiple of 16, dwords otherwise (such a
+// row is always 4-aligned); a HALF lane has 8 bytes: two dwords where 4-aligned, halves otherwise.
+// Bounds: loads as for the unzip -- at most 3 bytes in front of and behind the chunk's m <= n bytes, inside the scratch's margins.
+#define EXR_P24_TRIP 256u            // pixels of one trip of a wave: 64 lanes x 4
+// the v <= 4 bytes at p (any alignment), zeros behind them
+static __device__ __forceinline__ uint32_t xr_ld4(const uint8_t* p, uint32_t v) {
+    const uint32_t mis = (uint32_t)((uintptr_t)p & 3u);
+    const uint32_t* q = (const uint32_t*)(p - mis);
+    const uint32_t lo = v != 0u ? q[0] : 0u;
+    const uint32_t hi = mis + v > 4u ? q[1] : 0u;
+    return xr_keep(__builtin_amdgcn_alignbyte(hi, lo, mis), v);
+}
+
+__global__ void __launch_bounds__(64) zmi_exr_pxr24_undo_kernel(const zmi_exr_image* __restrict__ images, const zmi_exr_channel* __restrict__ chans,
+                                                                uint32_t chan_cap, const uint32_t* __restrict__ sel, const uint64_t* __restrict__ ch_off,
+                                                                const uint32_t* __restrict__ cslot, uint32_t chunk_cap,
+                                                                const uint64_t* __restrict__ pitem_off, const uint8_t* __restrict__ sbuf,
+                                                                const uint64_t* __restrict__ soff, const uint32_t* __restrict__ csz,
+                                                                const uint32_t* __restrict__ scap, const uint32_t* __restrict__ cm,
+                                                                const uint32_t* __restrict__ slen, const int32_t* __restrict__ sst, uint8_t* out,
+                                                                const uint64_t* __restrict__ out_off) {
+    const uint32_t lane = threadIdx.x;
+    const uint64_t total = pitem_off[chunk_cap];
+    for (uint64_t it = blockIdx.x; it < total; it += gridDim.x) {
+        const uint32_t q = xr_find(pitem_off, chunk_cap, it);
+        const uint32_t idx = (uint32_t)(it - pitem_off[q]);
+        const uint32_t n = csz[q];
+        if (n == 0u || scap[q] != n || sst[q] != 0 || slen[q] != cm[q]) continue;                   // the slot reports why
+        const uint32_t j = cslot[q];
+        const uint32_t f = sel ? sel[j] : j;
+        const zmi_exr_image r = images[f];
+        const zmi_exr_channel* ch = chans + (uint64_t)f * chan_cap;
+        xr_chunk c;
+        xr_chunk_of(r, q - (uint32_t)ch_off[j], &c);
+        const uint32_t row = idx / r.n_channels, x = idx % r.n_channels;
+        uint32_t per_row = 0u, choff = 0u;
+        for (uint32_t y = 0u; y < r.n_channels; ++y) {
+            const uint32_t run = c.cw * xr_p24_bytes(ch[y].pixel_type);
+            if (y < x) choff += run;
+            per_row += run;
+        }
+        const int32_t type = ch[x].pixel_type;
+        const uint32_t p = xr_p24_bytes(type), size = xr_type_bytes(type), w = c.cw;
+        const uint32_t mask = p == 4u ? 0xFFFFFFFFu : (1u << (8u * p)) - 1u, sh = type == 2 ? 8u : 0u;
+        const uint8_t* src = sbuf + soff[q] + (uint64_t)row * per_row + choff;
+        uint8_t* dst = out + out_off[j] + ch[x].plane_off + ((uint64_t)(c.y0 + row) * r.width + c.x0) * size;
+        uint32_t carry = 0u;
+        for (uint32_t t0 = 0u; t0 < w; t0 += EXR_P24_TRIP) {
+            const uint32_t left = w - t0 < EXR_P24_TRIP ? w - t0 : EXR_P24_TRIP;
+            const uint32_t v = 4u * lane < left ? (left - 4u * lane < 4u ? left - 4u * lane : 4u) : 0u;
+            const uint32_t px = t0 + 4u * lane;
+            uint32_t a[4];
+#pragma unroll
+            for (uint32_t k = 0u; k < 4u; ++k) a[k] = k < p ? xr_ld4(src + (uint64_t)k * w + px, v) : 0u;
+            // b0 .. b3: the planes of bits 24 - 31 .. 0 - 7
+            const uint32_t b3 = p == 4u ? a[3] : (p == 3u ? a[2] : a[1]), b2 = p == 4u ? a[2] : (p == 3u ? a[1] : a[0]);
+            const uint32_t b1 = p == 4u ? a[1] : (p == 3u ? a[0] : 0u), b0 = p == 4u ? a[0] : 0u;
+            const uint32_t lo01 = xr_perm(b2, b3, 0x05010400u), lo23 = xr_perm(b2, b3, 0x07030602u);
+            const uint32_t hi01 = xr_perm(b0, b1, 0x05010400u), hi23 = xr_perm(b0, b1, 0x07030602u);
+            uint32_t s[4];
+            s[0] = xr_perm(hi01, lo01, 0x05040100u);
+            s[1] = s[0] + xr_perm(hi01, lo01, 0x07060302u);
+            s[2] = s[1] + xr_perm(hi23, lo23, 0x05040100u);
+            s[3] = s[2] + xr_perm(hi23, lo23, 0x07060302u);
+            const uint32_t incl = zmi_wave_incl_scan(s[3]);
+            const uint32_t excl = incl - s[3] + carry;
+            carry += zmi_readlane(incl, 63u);
+            uint32_t o[4];
+#pragma unroll
+            for (uint32_t k = 0u; k < 4u; ++k) o[k] = ((excl + s[k]) & mask) << sh;
+            if (v == 0u) {
+            } else if (size == 4u) {
+                uint32_t* p4 = (uint32_t*)(dst + 4ull * px);
+                if (v == 4u && ((uintptr_t)p4 & 15u) == 0u) {
+                    uint4 u;
+                    u.x = o[0]; u.y = o[1]; u.z = o[2]; u.w = o[3];
+                    *(uint4*)p4 = u;
+                } else {
+#pragma unroll
+                    for (uint32_t k = 0u; k < 4u; ++k)
+                        if (k < v) p4[k] = o[k];
+                }
+            } else {
+                uint8_t* p2 = dst + 2ull * px;
+                if (v == 4u && ((uintptr_t)p2 & 3u) == 0u) {
+                    ((uint32_t*)p2)[0] = o[0] | o[1] << 16;
+                    ((uint32_t*)p2)[1] = o[2] | o[3] << 16;
+                } else {
+#pragma unroll
+                    for (uint32_t k = 0u; k < 4u; ++k)
+                        if (k < v) ((uint16_t*)p2)[k] = (uint16_t)o[k];
+                }
+            }
+        }
+    }
+}
+
+// the decoder's capacity of chunk q: the bytes its stream must inflate to, where the plan gave the chunk its room in the scratch
+__global__ void __launch_bounds__(256) zmi_exr_deccap_kernel(const uint32_t* __restrict__ csz, const uint32_t* __restrict__ scap,
+                                                             const uint32_t* __restrict__ cm, uint32_t chunk_cap, uint32_t* __restrict__ dcap) {
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+    if (q < chunk_cap) dcap[q] = scap[q] == csz[q] ? cm[q] : 0u;
+}
+
 // One wave per slot, behind everything else: the slot's final words (include/zmi355.h states the order).
 __global__ void __launch_bounds__(64) zmi_exr_finish_kernel(const zmi_exr_image* __restrict__ images, const uint32_t* __restrict__ sel, uint32_t n_sel,
                                                             const uint32_t* __restrict__ kind, const uint32_t* __restrict__ size,
@@ -578,7 +699,8 @@ __global__ void __launch_bounds__(64) zmi_exr_finish_kernel(const zmi_exr_image*
                                                             const uint64_t* __restrict__ ch_off, const uint64_t* __restrict__ raw_off,
                                                             uint64_t chunk_cap, uint64_t decoded_bytes, const uint32_t* __restrict__ csz,
                                                             const uint32_t* __restrict__ scap, const uint32_t* __restrict__ rawlen,
-                                                            const uint32_t* __restrict__ fl, const uint32_t* __restrict__ slen,
+                                                            const uint32_t* __restrict__ fl, const uint32_t* __restrict__ cm,
+                                                            const uint32_t* __restrict__ slen,
                                                             const int32_t* __restrict__ sst, uint32_t* __restrict__ out_len,
                                                             int32_t* __restrict__ status, int32_t* __restrict__ detail) {
     const uint32_t j = blockIdx.x, lane = threadIdx.x;
@@ -607,7 +729,7 @@ __global__ void __launch_bounds__(64) zmi_exr_finish_kernel(const zmi_exr_image*
                 if (ds == EXR_MEM_ERROR) cq = ZMI_XE_SCRATCH;
                 else if (ds == ZMI_BUF_ERROR) cq = ZMI_XE_LENGTH;     // the stream wants more input, or more room than the chunk
                 else if (ds != ZMI_OK) cq = ZMI_XE_DATA;
-                else if (slen[q] != csz[q]) cq = ZMI_XE_LENGTH;
+                else if (slen[q] != cm[q]) cq = ZMI_XE_LENGTH;
             }
             if (cq != 0u && cq < code) { code = cq; at = q - q0; }
         }
@@ -648,10 +770,10 @@ extern "C" int zmi_launch_exr_chunks(const uint8_t* d_in, const uint64_t* d_in_o
                                      const zmi_exr_channel* d_chans, uint32_t chan_cap, const uint32_t* d_sel, uint32_t n_sel,
                                      const uint64_t* d_ch_off, const uint32_t* d_live, uint32_t chunk_cap, uint64_t* d_zin_off, uint32_t* d_zin_len,
                                      uint32_t* d_csz, uint32_t* d_rawlen, uint32_t* d_fl, uint32_t* d_items, uint32_t* d_nblk, uint32_t* d_cslot,
-                                     hipStream_t stream) {
+                                     uint32_t* d_cm, uint32_t* d_pitems, hipStream_t stream) {
     if (chunk_cap == 0) return 0;
     ZMI_LAUNCH(zmi_exr_chunks_kernel, dim3((chunk_cap + 255u) / 256u), dim3(256), 0, stream, d_in, d_in_off, d_in_len, d_images, d_chans, chan_cap,
-               d_sel, n_sel, d_ch_off, d_live, chunk_cap, d_zin_off, d_zin_len, d_csz, d_rawlen, d_fl, d_items, d_nblk, d_cslot);
+               d_sel, n_sel, d_ch_off, d_live, chunk_cap, d_zin_off, d_zin_len, d_csz, d_rawlen, d_fl, d_items, d_nblk, d_cslot, d_cm, d_pitems);
     return 0;
 }
 // bound: the most blocks the call can have (decoded_bytes / EXR_BLOCK and one a chunk); d_bsum and d_bpre hold as many words
@@ -677,14 +799,33 @@ extern "C" int zmi_launch_exr_unzip(const zmi_exr_image* d_images, const zmi_exr
                d_sbuf, d_soff, d_csz, d_scap, d_slen, d_sst, d_rawlen, d_blk_off, d_bpre, d_out, d_out_off);
     return 0;
 }
+extern "C" uint32_t zmi_exr_pxr24_trip(void) { return EXR_P24_TRIP; }
+extern "C" int zmi_launch_exr_deccap(const uint32_t* d_csz, const uint32_t* d_scap, const uint32_t* d_cm, uint32_t chunk_cap, uint32_t* d_dcap,
+                                     hipStream_t stream) {
+    if (chunk_cap == 0) return 0;
+    ZMI_LAUNCH(zmi_exr_deccap_kernel, dim3((chunk_cap + 255u) / 256u), dim3(256), 0, stream, d_csz, d_scap, d_cm, chunk_cap, d_dcap);
+    return 0;
+}
+// bound: the most items the call can have (decoded_bytes / 2: a run holds at least one pixel of 2 bytes); a fixed grid takes them in turn
+extern "C" int zmi_launch_exr_pxr24_undo(const zmi_exr_image* d_images, const zmi_exr_channel* d_chans, uint32_t chan_cap, const uint32_t* d_sel,
+                                         const uint64_t* d_ch_off, const uint32_t* d_cslot, uint32_t chunk_cap, const uint64_t* d_pitem_off,
+                                         uint64_t bound, const uint8_t* d_sbuf, const uint64_t* d_soff, const uint32_t* d_csz,
+                                         const uint32_t* d_scap, const uint32_t* d_cm, const uint32_t* d_slen, const int32_t* d_sst, uint8_t* d_out,
+                                         const uint64_t* d_out_off, hipStream_t stream) {
+    if (chunk_cap == 0) return 0;
+    const uint32_t grid = bound < 1u ? 1u : (bound > 16384u ? 16384u : (uint32_t)bound);
+    ZMI_LAUNCH(zmi_exr_pxr24_undo_kernel, dim3(grid), dim3(64), 0, stream, d_images, d_chans, chan_cap, d_sel, d_ch_off, d_cslot, chunk_cap,
+               d_pitem_off, d_sbuf, d_soff, d_csz, d_scap, d_cm, d_slen, d_sst, d_out, d_out_off);
+    return 0;
+}
 extern "C" int zmi_launch_exr_finish(const zmi_exr_image* d_images, const uint32_t* d_sel, uint32_t n_sel,
                                      const uint32_t* d_kind, const uint32_t* d_size, const uint32_t* d_pcap,
                                      const uint64_t* d_ch_off, const uint64_t* d_raw_off, uint64_t chunk_cap, uint64_t decoded_bytes,
                                      const uint32_t* d_csz, const uint32_t* d_scap, const uint32_t* d_rawlen, const uint32_t* d_fl,
-                                     const uint32_t* d_slen, const int32_t* d_sst, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail,
+                                     const uint32_t* d_cm, const uint32_t* d_slen, const int32_t* d_sst, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail,
                                      hipStream_t stream) {
     if (n_sel == 0) return 0;
     ZMI_LAUNCH(zmi_exr_finish_kernel, dim3(n_sel), dim3(64), 0, stream, d_images, d_sel, n_sel, d_kind, d_size, d_pcap,
-               d_ch_off, d_raw_off, chunk_cap, decoded_bytes, d_csz, d_scap, d_rawlen, d_fl, d_slen, d_sst, d_out_len, d_status, d_detail);
+               d_ch_off, d_raw_off, chunk_cap, decoded_bytes, d_csz, d_scap, d_rawlen, d_fl, d_cm, d_slen, d_sst, d_out_len, d_status, d_detail);
     return 0;
 }

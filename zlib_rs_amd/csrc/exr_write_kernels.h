@@ -1,4 +1,4 @@
-// exr_write_kernels.h -- writing OpenEXR images with ZIP / ZIPS / NONE compression (zmi_exr_write_dev; every byte of the file:
+// exr_write_kernels.h -- writing OpenEXR images with ZIP / ZIPS / PXR24 / NONE compression (zmi_exr_write_dev; every byte of the file:
 // include/zmi355.h); included by pack.hip behind exr_kernels.h, whose helpers (xr_find, xr_perm, xr_type_bytes) it uses.
 //
 // A batch of images of ONE layout: the layout is the caller's, so the plan (zmi_xw_plan, zmi_kernels.h) is worked out on the host and
@@ -10,6 +10,7 @@
 //   zmi_exr_wchunks_kernel   one thread per chunk of the call: raw size, pieces, room in the scratch, work items (their scans follow)
 //   zmi_exr_wpieces_kernel   the piece table: piece p belongs to the chunk the scan of the piece counts names, by bisection
 //   zmi_exr_zip_kernel       the hot path, below
+//   zmi_exr_pxr24_forward_kernel   its place under PXR24: d is m bytes of byte planes, everything behind it runs with m where ZIP has n
 //   zmi_exr_wplace_kernel    one launch group: every chunk's candidate length, the raw decision, its dataSize and its place -- a scan
 //                            over (size, ends a file) pairs, the running offset a device word --, its pieces' places
 //   zmi_exr_gather_kernel    the raw chunks (all of them under NONE): the runs from the planes straight to their place in the file
@@ -20,6 +21,7 @@
 #define XW_TRIP 2048u                // raw bytes of one trip of a wave: 64 lanes x 32 bytes, 16 to each of the two streams
 #define XW_PIECE (4u * XW_TRIP)      // the longest piece of a run one work item reads
 #define XW_VOID 0xFFFFFFFFu          // head[] of a piece zmi_zip_pack_kernel leaves alone (ZW_VOID): a piece of a chunk stored raw
+#define XW_P24_TRIP 256u             // pixels of one trip of the PXR24 forward: 64 lanes x 4 (EXR_P24_TRIP of the reader)
 
 struct xw_box { uint32_t x0, y0, cw, rows, tx, ty; };
 static __device__ __forceinline__ void xw_box_of(const zmi_xw_plan& g, uint32_t k, xw_box* b) {
@@ -43,10 +45,12 @@ __global__ void __launch_bounds__(256) zmi_exr_wslice_kernel(zmi_xw_slice s, uin
 // encoded); items = the work items of its runs; cds = n, the dataSize of a chunk stored raw, until the place kernel decides.  The words
 // the later kernels start from: *n_eff = the chunks (the fold of the Adler-32 values), bad[i] = no piece of image i has a status,
 // run[0] = 0, where the first file starts.
+// PXR24 (compression 5): cm = the bytes m of the chunk's d -- rows * cw * per_p, where ZIP has n; pieces and room follow m -- and
+// fitems = the trips of its runs, the work items of zmi_exr_pxr24_forward_kernel (0 otherwise).
 __global__ void __launch_bounds__(256) zmi_exr_wchunks_kernel(zmi_xw_plan g, const zmi_exr_channel* __restrict__ chs, uint32_t* __restrict__ csz,
                                                               uint32_t* __restrict__ npc, uint32_t* __restrict__ ssz, uint32_t* __restrict__ items,
                                                               uint32_t* __restrict__ cds, uint32_t* __restrict__ n_eff, uint32_t* __restrict__ bad,
-                                                              uint64_t* __restrict__ run) {
+                                                              uint64_t* __restrict__ run, uint32_t* __restrict__ cm, uint32_t* __restrict__ fitems) {
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
     if (q == 0u) { *n_eff = g.ncc; run[0] = 0ull; }
     if (q >= g.ncc) return;
@@ -55,10 +59,12 @@ __global__ void __launch_bounds__(256) zmi_exr_wchunks_kernel(zmi_xw_plan g, con
     xw_box b;
     xw_box_of(g, k, &b);
     const uint32_t n = b.rows * b.cw * g.per_px;
-    csz[q] = n; cds[q] = n;
-    npc[q] = g.comp == 0u ? 0u : (uint32_t)(((uint64_t)n + g.piece_bytes - 1u) / g.piece_bytes);
-    ssz[q] = g.comp == 0u ? 0u : (uint32_t)(((uint64_t)n + 15ull) & ~15ull);
+    const uint32_t m = g.comp == 5u ? b.rows * b.cw * g.per_p : n;
+    csz[q] = n; cds[q] = n; cm[q] = m;
+    npc[q] = g.comp == 0u ? 0u : (uint32_t)(((uint64_t)m + g.piece_bytes - 1u) / g.piece_bytes);
+    ssz[q] = g.comp == 0u ? 0u : (uint32_t)(((uint64_t)m + 15ull) & ~15ull);
     items[q] = b.rows * xw_row_items(g, chs, b.cw);
+    fitems[q] = g.comp == 5u ? b.rows * g.n_ch * ((b.cw + XW_P24_TRIP - 1u) / XW_P24_TRIP) : 0u;
 }
 
 // One thread per piece.  p_off / p_len: the piece's bytes in the scratch; the bit of a chunk's last piece is set in `ends` (zeroed by
@@ -258,6 +264,98 @@ __global__ void __launch_bounds__(64) zmi_exr_gather_kernel(zmi_xw_plan g, const
     }
 }
 
+// ---- the PXR24 forward (compression 5; include/zmi355.h states the layout) --------------------------------------------------------------------
+// d of a chunk is, for every row and channel, a run of p planes of cw bytes (p = 2 / 3 / 4 for HALF / FLOAT / UINT), most significant
+// first, that hold diff[x] = v[x] - v[x - 1] mod 2^(8p), v[-1] = 0, v = the sample (a FLOAT rounded to 24 bits, xw_f24).  Nothing here
+// is a scan: the work item is one trip of XW_P24_TRIP pixels of a (chunk, row, channel) run, every run of a chunk has the same number
+// of trips, so an item's place follows by division.  A lane loads its 4 consecutive pixels from the plane (xr_ld16: aligned dwords
+// joined by v_alignbyte, every address lane-dependent), takes the predecessor of its first from the lane below (DPP) -- lane 0 loads
+// the pixel in front of the trip with byte loads, and has 0 at the start of a run --, subtracts, splits the four differences into
+// byte planes with v_perm_b32 and stores 4 bytes to each plane: a dword where they stand 4-aligned, bytes otherwise (a plane starts at
+// any byte offset of d).  Bounds: loads touch the dwords that hold a lane's own bytes only; stores write d[0 .. m) of the chunk.
+static __device__ __forceinline__ uint32_t xw_f24(uint32_t u) {
+    const uint32_t s = u & 0x80000000u, e = u & 0x7F800000u;
+    uint32_t m = u & 0x007FFFFFu, i;
+    if (e == 0x7F800000u) {
+        if (m != 0u) { m >>= 8; i = (e >> 8) | m | (m == 0u ? 1u : 0u); }      // a NaN stays a NaN
+        else i = e >> 8;
+    } else {
+        i = ((e | m) + (m & 0x80u)) >> 8;
+        if (i >= 0x7F8000u) i = (e | m) >> 8;                                   // rounding never produces an infinity
+    }
+    return (s >> 8) | i;
+}
+
+__global__ void __launch_bounds__(64) zmi_exr_pxr24_forward_kernel(zmi_xw_plan g, const zmi_exr_channel* __restrict__ chs,
+                                                                   const uint8_t* __restrict__ in, const uint64_t* __restrict__ in_off,
+                                                                   const uint64_t* __restrict__ fitem_off, const uint64_t* __restrict__ soff,
+                                                                   uint8_t* __restrict__ scan) {
+    const uint32_t lane = threadIdx.x;
+    const uint64_t total = fitem_off[g.ncc];
+    for (uint64_t it = blockIdx.x; it < total; it += gridDim.x) {
+        const uint32_t q = xr_find(fitem_off, g.ncc, it);
+        const uint32_t idx = (uint32_t)(it - fitem_off[q]);
+        const uint32_t img = q / g.nc;
+        xw_box b;
+        xw_box_of(g, q - img * g.nc, &b);
+        const uint32_t tp = (b.cw + XW_P24_TRIP - 1u) / XW_P24_TRIP;
+        const uint32_t row = idx / (g.n_ch * tp), x = (idx / tp) % g.n_ch, t0 = (idx % tp) * XW_P24_TRIP;
+        uint32_t choff = 0u;
+        for (uint32_t y = 0u; y < x; ++y) choff += b.cw * xr_p24_bytes(chs[y].pixel_type);
+        const int32_t type = chs[x].pixel_type;
+        const uint32_t p = xr_p24_bytes(type), size = xr_type_bytes(type), w = b.cw;
+        const uint32_t mask = p == 4u ? 0xFFFFFFFFu : (1u << (8u * p)) - 1u;
+        const uint8_t* src = in + in_off[img] + chs[x].plane_off + ((uint64_t)(b.y0 + row) * g.W + b.x0) * size;
+        uint8_t* dst = scan + soff[q] + (uint64_t)row * w * g.per_p + choff;
+        const uint32_t left = w - t0 < XW_P24_TRIP ? w - t0 : XW_P24_TRIP;
+        const uint32_t v = 4u * lane < left ? (left - 4u * lane < 4u ? left - 4u * lane : 4u) : 0u;
+        const uint32_t px = t0 + 4u * lane;
+        uint32_t ld[4] = {0u, 0u, 0u, 0u}, val[4];
+        if (v != 0u) xr_ld16(src + (uint64_t)px * size, v * size, ld);
+        uint32_t front = 0u;                                  // the pixel in front of the trip: lane 0 alone loads it
+        if (lane == 0u && t0 != 0u) {
+            const uint8_t* f = src + (uint64_t)(t0 - 1u) * size;
+            front = (uint32_t)f[0] | (uint32_t)f[1] << 8;
+            if (size == 4u) front |= (uint32_t)f[2] << 16 | (uint32_t)f[3] << 24;
+        }
+        if (size == 2u) {
+            val[0] = ld[0] & 0xFFFFu; val[1] = ld[0] >> 16; val[2] = ld[1] & 0xFFFFu; val[3] = ld[1] >> 16;
+        } else {
+#pragma unroll
+            for (uint32_t k = 0u; k < 4u; ++k) val[k] = type == 2 ? xw_f24(ld[k]) : ld[k];
+            if (type == 2) front = xw_f24(front);
+        }
+        // (a lane with pixels has a full lane below it)
+        const uint32_t up = zmi_lane_up1(val[3]);
+        const uint32_t prev = lane == 0u ? front : up;
+        uint32_t d[4];
+        d[0] = (val[0] - prev) & mask;
+#pragma unroll
+        for (uint32_t k = 1u; k < 4u; ++k) d[k] = (val[k] - val[k - 1u]) & mask;
+        const uint32_t t01 = xr_perm(d[1], d[0], 0x05010400u), u01 = xr_perm(d[1], d[0], 0x07030602u);
+        const uint32_t t23 = xr_perm(d[3], d[2], 0x05010400u), u23 = xr_perm(d[3], d[2], 0x07030602u);
+        // b0 .. b3: the planes of bits 24 - 31 .. 0 - 7
+        const uint32_t b3 = xr_perm(t23, t01, 0x05040100u), b2 = xr_perm(t23, t01, 0x07060302u);
+        const uint32_t b1 = xr_perm(u23, u01, 0x05040100u), b0 = xr_perm(u23, u01, 0x07060302u);
+        uint32_t a[4];
+        a[0] = p == 4u ? b0 : (p == 3u ? b1 : b2);
+        a[1] = p == 4u ? b1 : (p == 3u ? b2 : b3);
+        a[2] = p == 4u ? b2 : b3;
+        a[3] = b3;
+#pragma unroll
+        for (uint32_t k = 0u; k < 4u; ++k) {
+            if (k >= p || v == 0u) continue;
+            uint8_t* o = dst + (uint64_t)k * w + px;
+            if (v == 4u && ((uintptr_t)o & 3u) == 0u) *(uint32_t*)o = a[k];
+            else {
+#pragma unroll
+                for (uint32_t i = 0u; i < 4u; ++i)
+                    if (i < v) o[i] = (uint8_t)(a[k] >> (8u * i));
+            }
+        }
+    }
+}
+
 // One launch group: chunks first .. first + n of the call, whose pieces the encoder has just left in their slots.  A chunk's candidate
 // is the zlib header, its pieces' payloads and the Adler-32; it is stored raw -- dataSize = n -- where that is not shorter than n, or
 // where a piece has a status (bad[image] = the least such piece).  A chunk takes its header and its data, an image's first chunk the
@@ -417,9 +515,10 @@ extern "C" int zmi_launch_exr_wslice(zmi_xw_slice slice, uint8_t* d_blob, hipStr
     return 0;
 }
 extern "C" int zmi_launch_exr_wchunks(zmi_xw_plan plan, const zmi_exr_channel* d_chs, uint32_t* d_csz, uint32_t* d_npc, uint32_t* d_ssz,
-                                      uint32_t* d_items, uint32_t* d_cds, uint32_t* d_neff, uint32_t* d_bad, uint64_t* d_run, hipStream_t stream) {
+                                      uint32_t* d_items, uint32_t* d_cds, uint32_t* d_neff, uint32_t* d_bad, uint64_t* d_run, uint32_t* d_cm,
+                                      uint32_t* d_fitems, hipStream_t stream) {
     ZMI_LAUNCH(zmi_exr_wchunks_kernel, dim3(plan.ncc / 256u + 1u), dim3(256), 0, stream, plan, d_chs, d_csz, d_npc, d_ssz, d_items, d_cds, d_neff,
-               d_bad, d_run);
+               d_bad, d_run, d_cm, d_fitems);
     return 0;
 }
 extern "C" int zmi_launch_exr_wpieces(zmi_xw_plan plan, const uint64_t* d_cfirst, const uint64_t* d_soff, const uint32_t* d_csz,
@@ -436,6 +535,16 @@ extern "C" int zmi_launch_exr_zip(zmi_xw_plan plan, const zmi_exr_channel* d_chs
     if (bound == 0) return 0;
     const uint32_t grid = bound > 16384u ? 16384u : (uint32_t)bound;
     ZMI_LAUNCH(zmi_exr_zip_kernel, dim3(grid), dim3(64), 0, stream, plan, d_chs, d_in, d_in_off, d_item_off, d_soff, d_scan);
+    return 0;
+}
+static_assert(XW_P24_TRIP == EXR_P24_TRIP, "zmi_exr_pxr24_trip() states the trip of both PXR24 kernels");
+// bound: the items of the call (the host's count)
+extern "C" int zmi_launch_exr_pxr24_forward(zmi_xw_plan plan, const zmi_exr_channel* d_chs, const uint8_t* d_in, const uint64_t* d_in_off,
+                                            const uint64_t* d_fitem_off, uint64_t bound, const uint64_t* d_soff, uint8_t* d_scan,
+                                            hipStream_t stream) {
+    if (bound == 0) return 0;
+    const uint32_t grid = bound > 16384u ? 16384u : (uint32_t)bound;
+    ZMI_LAUNCH(zmi_exr_pxr24_forward_kernel, dim3(grid), dim3(64), 0, stream, plan, d_chs, d_in, d_in_off, d_fitem_off, d_soff, d_scan);
     return 0;
 }
 extern "C" int zmi_launch_exr_wplace(zmi_xw_plan plan, uint32_t first, uint32_t count, const uint64_t* d_cfirst, const uint32_t* d_csz,

@@ -1424,7 +1424,8 @@ extern "C" int zmi_inflate_sizes_dev(zmi_ctx* c, const void* d_in, const uint64_
 static int zmi_inflate_packed_body(zmi_ctx* c, const void* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, uint32_t n, int wrap,
                                    const void* d_dict, uint32_t dict_len, const uint32_t* d_size, uint32_t* d_cap, uint32_t out_align,
                                    void* d_out, uint64_t out_cap, uint64_t* d_out_off, uint32_t* d_out_len, int32_t* d_status,
-                                   uint32_t* d_in_used, int32_t* d_detail, int plan_timer, void* stream_) {
+                                   uint32_t* d_in_used, int32_t* d_detail, int plan_timer, void* stream_, const uint32_t* d_want = nullptr,
+                                   uint32_t* d_dcap = nullptr) {
     hipStream_t stream = (hipStream_t)stream_;
     if (plan_timer >= 0) {
         zmi_scope_timer tm(c, plan_timer, stream);
@@ -1432,10 +1433,12 @@ static int zmi_inflate_packed_body(zmi_ctx* c, const void* d_in, const uint64_t*
     } else {
         zmi_launch_inflate_pack_plan(d_size, n, out_align, out_cap, d_out_off, d_cap, stream);
     }
+    // d_want (zmi_exr_read_dev): a stream must give d_want[i] <= d_size[i] bytes; its room stays the plan's
+    if (d_want) zmi_launch_exr_deccap(d_size, d_cap, d_want, n, d_dcap, stream);
     // the bitmap scratch covers what the planned capacities can sum to: out_cap (no stream holds more than 2^32 - 1 bytes)
     const uint64_t most = (uint64_t)n * 0xFFFFFFFFull;
     const zmi_inf_req q{.d_in = d_in, .d_in_off = d_in_off, .d_in_len = d_in_len, .n = n, .wrap = wrap, .d_out = d_out, .d_out_off = d_out_off,
-                        .d_out_cap = d_cap, .d_out_len = d_out_len, .d_status = d_status, .d_in_used = d_in_used, .d_detail = d_detail,
+                        .d_out_cap = d_want ? d_dcap : d_cap, .d_out_len = d_out_len, .d_status = d_status, .d_in_used = d_in_used, .d_detail = d_detail,
                         .stream = stream_, .out_limit = (out_cap < most ? out_cap : most) + (1ull << 16), .limit_exact = true};
     const int rc = d_dict ? zmi_inflate_shared_dict(c, q, d_dict, dict_len) : zmi_inflate_impl(c, q);
     if (rc) return rc;
@@ -1776,9 +1779,9 @@ extern "C" int zmi_exr_read_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_
     const size_t n = n_sel, cc = chunk_cap;
     const uint64_t nblk = decoded_bytes / 1024u + cc;                 // (EXR_BLOCK: every chunk ends with at most one short block)
     const uint64_t scan_cap = decoded_bytes + 16ull * cc + 64ull;
-    uint64_t *d_ch_off, *d_raw_off, *d_soff, *d_item_off, *d_blk_off, *d_zin_off;
+    uint64_t *d_ch_off, *d_raw_off, *d_soff, *d_item_off, *d_blk_off, *d_zin_off, *d_pitem_off;
     uint32_t *d_size, *d_pcap, *d_nch, *d_rawb, *d_kind, *d_live;
-    uint32_t *d_zin_len, *d_csz, *d_scap, *d_rawlen, *d_fl, *d_items, *d_nblk, *d_cslot, *d_slen, *d_sused, *d_bsum, *d_bpre;
+    uint32_t *d_zin_len, *d_csz, *d_scap, *d_rawlen, *d_fl, *d_items, *d_nblk, *d_cslot, *d_slen, *d_sused, *d_bsum, *d_bpre, *d_cm, *d_pitems, *d_dcap;
     int32_t *d_sst, *d_sdet;
     uint8_t* d_sbuf;
     rc = zmi_carve(c->exr, [&](zmi_carver k) {
@@ -1788,6 +1791,7 @@ extern "C" int zmi_exr_read_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_
         k.take(cc + 1, d_item_off);      // the scan of d_items
         k.take(cc + 1, d_blk_off);       // the scan of d_nblk
         k.take(cc + 1, d_zin_off);       // the chunk's data in d_in
+        k.take(cc + 1, d_pitem_off);     // the scan of d_pitems
         k.take(n, d_size);               // per slot: the region of a readable file, else 0
         k.take(n, d_pcap);               // ... where it fits out_cap, else 0
         k.take(n, d_nch);                // its chunks
@@ -1800,6 +1804,8 @@ extern "C" int zmi_exr_read_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_
         k.take(cc, d_items);             // the pieces of the chunk's runs
         k.take(cc, d_nblk);              // the blocks of byte sums of a compressed chunk
         k.take(cc, d_cslot);             // the chunk's slot
+        k.take(cc, d_cm, d_dcap);        // the bytes its stream must inflate to (PXR24: m < n); the decoder's capacity
+        k.take(cc, d_pitems);            // the runs of a PXR24 stream
         k.take(cc, d_slen, d_sused, d_sst, d_sdet);   // the decoder's words
         k.take(nblk, d_bsum);            // one byte sum per block
         k.take(nblk, d_bpre);            // ... and the sums in front of it inside its chunk
@@ -1820,14 +1826,15 @@ extern "C" int zmi_exr_read_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_
                              d_size, d_nch, d_rawb, d_kind, d_live, stream);
         if (chunk_cap) {
             zmi_launch_exr_chunks(in, d_in_off, d_in_len, d_images, d_channels, chan_cap, d_sel, n_sel, d_ch_off, d_live, chunk_cap, d_zin_off, d_zin_len,
-                                  d_csz, d_rawlen, d_fl, d_items, d_nblk, d_cslot, stream);
+                                  d_csz, d_rawlen, d_fl, d_items, d_nblk, d_cslot, d_cm, d_pitems, stream);
             zmi_launch_scan_sizes(d_items, chunk_cap, d_item_off, stream);
+            zmi_launch_scan_sizes(d_pitems, chunk_cap, d_pitem_off, stream);
             zmi_launch_scan_sizes(d_nblk, chunk_cap, d_blk_off, stream);
         }
     }
     if (chunk_cap) {
         rc = zmi_inflate_packed_body(c, d_in, d_zin_off, d_zin_len, chunk_cap, ZMI_WRAP_ZLIB, nullptr, 0u, d_csz, d_scap, 16u, d_sbuf, scan_cap, d_soff,
-                                     d_slen, d_sst, d_sused, d_sdet, ZMI_K_PARSE, stream_);
+                                     d_slen, d_sst, d_sused, d_sdet, ZMI_K_PARSE, stream_, d_cm, d_dcap);
         if (rc) return rc;
         {
             // chunks stored raw: their bytes as they stand (max_len only shapes the launch)
@@ -1840,12 +1847,14 @@ extern "C" int zmi_exr_read_dev(zmi_ctx* c, const void* d_in, const uint64_t* d_
             zmi_launch_exr_blocksum(d_sbuf, d_soff, d_csz, d_scap, d_blk_off, chunk_cap, nblk, d_bsum, d_bpre, stream);
             zmi_launch_exr_unzip(d_images, d_channels, chan_cap, d_sel, d_ch_off, d_cslot, chunk_cap, d_item_off, decoded_bytes / 2u, d_sbuf,
                                  d_soff, d_csz, d_scap, d_slen, d_sst, d_rawlen, d_blk_off, d_bpre, (uint8_t*)d_out, d_out_off, stream);
+            zmi_launch_exr_pxr24_undo(d_images, d_channels, chan_cap, d_sel, d_ch_off, d_cslot, chunk_cap, d_pitem_off, decoded_bytes / 2u, d_sbuf,
+                                      d_soff, d_csz, d_scap, d_cm, d_slen, d_sst, (uint8_t*)d_out, d_out_off, stream);
         }
     }
     {
         zmi_scope_timer tm(c, ZMI_K_VERIFY, stream);
         zmi_launch_exr_finish(d_images, d_sel, n_sel, d_kind, d_size, d_pcap, d_ch_off, d_raw_off, chunk_cap, decoded_bytes, d_csz, d_scap, d_rawlen,
-                              d_fl, d_slen, d_sst, d_out_len, d_status, d_detail, stream);
+                              d_fl, d_cm, d_slen, d_sst, d_out_len, d_status, d_detail, stream);
     }
     ZMI_HIP(hipGetLastError());
     return ZMI_E_OK;
@@ -2228,7 +2237,8 @@ struct zmi_xw_host {
     std::vector<uint8_t> blob;       // n_ch zmi_exr_channel records | the header's hdr_len bytes
     uint64_t file_bound = 0;         // header + table + every chunk's header + n
     uint64_t ppi = 0, ssi = 0, ipi = 0;   // per image: pieces, bytes of d in the scratch, work items of the forward kernel
-    uint32_t n_max = 0;              // the raw size of the largest chunk
+    uint64_t fpi = 0;                // ... the trips of the PXR24 forward (compression 5)
+    uint32_t n_max = 0;              // the bytes of d of the largest chunk: its raw size, m under PXR24
     uint64_t pp[2][2] = {{0, 0}, {0, 0}};   // the pieces of a chunk in an inner / the last column [0 / 1], an inner / the last row
 };
 static void zmi_xw_attr(std::vector<uint8_t>& b, const char* name, const char* type, const void* value, uint32_t size) {
@@ -2253,11 +2263,12 @@ static const char* zmi_exr_wplan(const zmi_exr_write* w, uint32_t n_images, zmi_
     if (w->data_window[2] < w->data_window[0] || w->data_window[3] < w->data_window[1]) return "zmi_exr_write: an inverted data window";
     if (w->display_window[2] < w->display_window[0] || w->display_window[3] < w->display_window[1]) return "zmi_exr_write: an inverted display window";
     if (w->n_channels == 0u || !w->channels) return "zmi_exr_write: no channels";
-    if (w->compression != 0u && w->compression != 2u && w->compression != 3u) return "zmi_exr_write: compression must be 0 (NONE), 2 (ZIPS) or 3 (ZIP)";
+    if (w->compression != 0u && w->compression != 2u && w->compression != 3u && w->compression != 5u)
+        return "zmi_exr_write: compression must be 0 (NONE), 2 (ZIPS), 3 (ZIP) or 5 (PXR24)";
     if ((w->tile_w == 0u) != (w->tile_h == 0u)) return "zmi_exr_write: tile_w and tile_h must both be 0 or both be set";
     if (w->flags != 0u) return "zmi_exr_write: unknown flag";
     bool long_names = false;
-    uint64_t per_px = 0;
+    uint64_t per_px = 0, per_p = 0;
     for (uint32_t c = 0; c < w->n_channels; ++c) {
         const zmi_exr_write_channel& ch = w->channels[c];
         if (ch.pixel_type < 0 || ch.pixel_type > 2) return "zmi_exr_write: a pixel type must be 0 (UINT), 1 (HALF) or 2 (FLOAT)";
@@ -2267,6 +2278,7 @@ static const char* zmi_exr_wplan(const zmi_exr_write* w, uint32_t n_images, zmi_
         if (nl > 31u) long_names = true;
         if (c && strcmp(w->channels[c - 1u].name, ch.name) >= 0) return "zmi_exr_write: channel names must be strictly ascending";
         per_px += ch.pixel_type == 1 ? 2u : 4u;
+        per_p += ch.pixel_type == 1 ? 2u : (ch.pixel_type == 2 ? 3u : 4u);
     }
     // what xr_geometry (exr_kernels.h) calls big
     const uint64_t W = (uint64_t)((int64_t)w->data_window[2] - (int64_t)w->data_window[0] + 1);
@@ -2274,7 +2286,8 @@ static const char* zmi_exr_wplan(const zmi_exr_write* w, uint32_t n_images, zmi_
     const char* big = "zmi_exr_write: the image does not fit 32 bits (width, height, pixels, a row, the region or a chunk)";
     if (W > 0xFFFFFFFFull || H > 0xFFFFFFFFull || W * H > 0xFFFFFFFFull || per_px > 0xFFFFFFFFull) return big;
     const bool tiled = w->tile_w != 0u;
-    const uint32_t lines = w->compression == 3u ? 16u : 1u;
+    const bool pxr24 = w->compression == 5u;
+    const uint32_t lines = w->compression == 3u || pxr24 ? 16u : 1u;
     const uint64_t box_w = tiled ? w->tile_w : W, box_h = tiled ? w->tile_h : lines;
     const uint64_t cw0 = box_w < W ? box_w : W, rows0 = box_h < H ? box_h : H;
     uint64_t region = 0;
@@ -2332,7 +2345,7 @@ static const char* zmi_exr_wplan(const zmi_exr_write* w, uint32_t n_images, zmi_
 
     // the four sizes a chunk has: inner or last column, inner or last row
     const uint64_t cw_last = W - (across - 1u) * box_w, rows_last = H - (down - 1u) * box_h;
-    uint64_t ppi = 0, ssi = 0, ipi = 0;
+    uint64_t ppi = 0, ssi = 0, ipi = 0, fpi = 0;
     for (uint32_t cx = 0; cx < 2u; ++cx)
         for (uint32_t cy = 0; cy < 2u; ++cy) {
             const uint64_t count = (cx ? 1u : across - 1u) * (cy ? 1u : down - 1u);
@@ -2340,10 +2353,12 @@ static const char* zmi_exr_wplan(const zmi_exr_write* w, uint32_t n_images, zmi_
             uint64_t per_row = 0;
             for (uint32_t c = 0; c < w->n_channels; ++c) per_row += (cw * (w->channels[c].pixel_type == 1 ? 2u : 4u) + 8191u) / 8192u;   // (XW_PIECE)
             ipi += count * rows * per_row;
+            if (pxr24) fpi += count * rows * w->n_channels * ((cw + 255u) / 256u);                                                      // (XW_P24_TRIP)
             if (!none) {
-                h->pp[cx][cy] = (n + w->piece_bytes - 1u) / w->piece_bytes;
+                const uint64_t m = pxr24 ? rows * cw * per_p : n;          // the bytes of the chunk's d
+                h->pp[cx][cy] = (m + w->piece_bytes - 1u) / w->piece_bytes;
                 ppi += count * h->pp[cx][cy];
-                ssi += count * ((n + 15u) & ~15ull);
+                ssi += count * ((m + 15u) & ~15ull);
             }
         }
     if (ppi * (n_images ? n_images : 1u) > 0x7FFFFFFFull) return "zmi_exr_write: more than 2^31 - 1 pieces";
@@ -2354,7 +2369,7 @@ static const char* zmi_exr_wplan(const zmi_exr_write* w, uint32_t n_images, zmi_
     g.across = (uint32_t)across; g.down = (uint32_t)down; g.nc = (uint32_t)nc;
     g.n_ch = w->n_channels; g.per_px = (uint32_t)per_px; g.tiled = tiled ? 1u : 0u; g.comp = w->compression; g.chdr = chdr;
     g.ymin = w->data_window[1]; g.hdr_len = (uint32_t)hdr_len; g.n_images = n_images; g.ncc = (uint32_t)(nc * n_images);
-    g.piece_bytes = w->piece_bytes; g.out_align = w->out_align;
+    g.piece_bytes = w->piece_bytes; g.out_align = w->out_align; g.per_p = (uint32_t)per_p;
     zmi_exr_image r;
     memset(&r, 0, sizeof r);
     r.version = 2u | (tiled ? 0x200u : 0u) | (long_names ? 0x400u : 0u);
@@ -2376,7 +2391,8 @@ static const char* zmi_exr_wplan(const zmi_exr_write* w, uint32_t n_images, zmi_
         memcpy(h->blob.data() + (size_t)c * sizeof e, &e, sizeof e);
     }
     h->blob.insert(h->blob.end(), hd.begin(), hd.end());
-    h->file_bound = file_bound; h->ppi = ppi; h->ssi = ssi; h->ipi = ipi; h->n_max = (uint32_t)(rows0 * cw0 * per_px);
+    h->file_bound = file_bound; h->ppi = ppi; h->ssi = ssi; h->ipi = ipi; h->fpi = fpi;
+    h->n_max = (uint32_t)(rows0 * cw0 * (pxr24 ? per_p : per_px));
     return nullptr;
 }
 
@@ -2435,18 +2451,20 @@ extern "C" int zmi_exr_write_dev(zmi_ctx* c, const zmi_exr_write* w, const void*
     const size_t bm_words = none ? 0u : (size_t)(n_groups * wpg);
     const size_t n_rec = (size_t)g.n_ch * sizeof(zmi_exr_channel);
 
-    uint64_t *d_cfirst, *d_soff, *d_item_off, *d_cpos, *d_poff, *d_ppos, *d_run;
+    uint64_t *d_cfirst, *d_soff, *d_item_off, *d_fitem_off, *d_cpos, *d_poff, *d_ppos, *d_run;
     zmi_words4 neff;
-    uint32_t *d_csz, *d_npc, *d_ssz, *d_items, *d_cds, *d_cadler, *d_plen, *d_olen, *d_padler, *d_phead, *d_bad, *d_ends;
+    uint32_t *d_csz, *d_cm, *d_fitems, *d_npc, *d_ssz, *d_items, *d_cds, *d_cadler, *d_plen, *d_olen, *d_padler, *d_phead, *d_bad, *d_ends;
     int32_t* d_st;
     uint8_t *d_blob, *d_scan;
     rc = zmi_carve(c->exr, [&](zmi_carver k) {
         k.take(ncc + 1u, d_cfirst, d_soff, d_item_off);   // per chunk: the scans of its pieces, of its room in the scratch, of its items
+        k.take(ncc + 1u, d_fitem_off);                    // ... of the trips of its runs (PXR24)
         k.take(ncc, d_cpos);                              // ... its header's place in d_out
         k.take(np, d_poff, d_ppos);                       // per piece: its place in the scratch and in d_out
         k.take(n_groups + 1u, d_run);                     // where every launch group starts in d_out
         k.take(neff);                                     // the chunks that are live: all
         k.take(ncc, d_csz, d_npc, d_ssz, d_items);        // per chunk: raw size, pieces, room, items
+        k.take(ncc, d_cm, d_fitems);                      // ... the bytes of its d (PXR24: m, else n), the trips of its runs
         k.take_unless(d_chunk_len, ncc, d_cds);           // ... its dataSize
         k.take(ncc, d_cadler);                            // ... the Adler-32 of its d
         k.take(np, d_plen, d_olen, d_st, d_padler, d_phead);   // per piece: length, encoder's size and status, Adler-32, hole (void: raw chunk)
@@ -2472,16 +2490,18 @@ extern "C" int zmi_exr_write_dev(zmi_ctx* c, const zmi_exr_write* w, const void*
             memcpy(s.b, h.blob.data() + at, s.len);
             zmi_launch_exr_wslice(s, d_blob, stream);
         }
-        zmi_launch_exr_wchunks(g, d_chs, d_csz, d_npc, d_ssz, d_items, d_cds, neff.w, d_bad, d_run, stream);
+        zmi_launch_exr_wchunks(g, d_chs, d_csz, d_npc, d_ssz, d_items, d_cds, neff.w, d_bad, d_run, d_cm, d_fitems, stream);
         zmi_launch_scan_sizes(d_npc, ncc, d_cfirst, stream);
         zmi_launch_scan_sizes(d_ssz, ncc, d_soff, stream);
         zmi_launch_scan_sizes(d_items, ncc, d_item_off, stream);
-        if (!none) zmi_launch_exr_wpieces(g, d_cfirst, d_soff, d_csz, (uint32_t)gch, wpg, np, d_poff, d_plen, d_ends, stream);
+        if (g.comp == 5u) zmi_launch_scan_sizes(d_fitems, ncc, d_fitem_off, stream);
+        if (!none) zmi_launch_exr_wpieces(g, d_cfirst, d_soff, d_cm, (uint32_t)gch, wpg, np, d_poff, d_plen, d_ends, stream);
     }
     if (!none) {
         {
             zmi_scope_timer tm(c, ZMI_K_INFLATE, stream);
-            zmi_launch_exr_zip(g, d_chs, in, d_in_off, d_item_off, items, d_soff, d_scan, stream);
+            if (g.comp == 5u) zmi_launch_exr_pxr24_forward(g, d_chs, in, d_in_off, d_fitem_off, h.fpi * n, d_soff, d_scan, stream);
+            else zmi_launch_exr_zip(g, d_chs, in, d_in_off, d_item_off, items, d_soff, d_scan, stream);
         }
         rc = zmi_piece_checks(c, d_scan, d_poff, d_plen, np, ZMI_WRAP_ZLIB, d_padler, stream);
         if (rc) return rc;

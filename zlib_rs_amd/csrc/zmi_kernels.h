@@ -103,6 +103,7 @@ struct zmi_xw_plan {
     uint32_t hdr_len;                  // magic, version word, attributes and the 00 behind them: the offset table starts here
     uint32_t n_images, ncc;            // ncc = n_images * nc: the chunks of the call
     uint32_t piece_bytes, out_align;
+    uint32_t per_p;                    // the bytes of a pixel inside a PXR24 stream: a FLOAT keeps 3
     uint8_t rec[88];                   // the zmi_exr_image of a written file
 };
 // a slice of the host's bytes on its way into the context's scratch (kernel arguments are the one copy that needs no staging)
@@ -413,7 +414,16 @@ int zmi_launch_exr_slots(const uint32_t* d_in_len, const zmi_exr_image* d_images
 int zmi_launch_exr_chunks(const uint8_t* d_in, const uint64_t* d_in_off, const uint32_t* d_in_len, const zmi_exr_image* d_images,
                           const zmi_exr_channel* d_chans, uint32_t chan_cap, const uint32_t* d_sel, uint32_t n_sel, const uint64_t* d_ch_off,
                           const uint32_t* d_live, uint32_t chunk_cap, uint64_t* d_zin_off, uint32_t* d_zin_len, uint32_t* d_csz,
-                          uint32_t* d_rawlen, uint32_t* d_fl, uint32_t* d_items, uint32_t* d_nblk, uint32_t* d_cslot, hipStream_t stream);
+                          uint32_t* d_rawlen, uint32_t* d_fl, uint32_t* d_items, uint32_t* d_nblk, uint32_t* d_cslot, uint32_t* d_cm, uint32_t* d_pitems,
+                          hipStream_t stream);
+// PXR24 (compression 5): the decoder's capacities from the lengths the streams must inflate to; the undo over the items of its own scan
+uint32_t zmi_exr_pxr24_trip(void);
+int zmi_launch_exr_deccap(const uint32_t* d_csz, const uint32_t* d_scap, const uint32_t* d_cm, uint32_t chunk_cap, uint32_t* d_dcap,
+                          hipStream_t stream);
+int zmi_launch_exr_pxr24_undo(const zmi_exr_image* d_images, const zmi_exr_channel* d_chans, uint32_t chan_cap, const uint32_t* d_sel,
+                              const uint64_t* d_ch_off, const uint32_t* d_cslot, uint32_t chunk_cap, const uint64_t* d_pitem_off, uint64_t bound,
+                              const uint8_t* d_sbuf, const uint64_t* d_soff, const uint32_t* d_csz, const uint32_t* d_scap, const uint32_t* d_cm,
+                              const uint32_t* d_slen, const int32_t* d_sst, uint8_t* d_out, const uint64_t* d_out_off, hipStream_t stream);
 int zmi_launch_exr_blocksum(const uint8_t* d_sbuf, const uint64_t* d_soff, const uint32_t* d_csz, const uint32_t* d_scap,
                             const uint64_t* d_blk_off, uint32_t chunk_cap, uint64_t bound, uint32_t* d_bsum, uint32_t* d_bpre, hipStream_t stream);
 int zmi_launch_exr_unzip(const zmi_exr_image* d_images, const zmi_exr_channel* d_chans, uint32_t chan_cap, const uint32_t* d_sel,
@@ -423,8 +433,9 @@ int zmi_launch_exr_unzip(const zmi_exr_image* d_images, const zmi_exr_channel* d
                          const uint64_t* d_out_off, hipStream_t stream);
 int zmi_launch_exr_finish(const zmi_exr_image* d_images, const uint32_t* d_sel, uint32_t n_sel, const uint32_t* d_kind, const uint32_t* d_size,
                           const uint32_t* d_pcap, const uint64_t* d_ch_off, const uint64_t* d_raw_off, uint64_t chunk_cap, uint64_t decoded_bytes,
-                          const uint32_t* d_csz, const uint32_t* d_scap, const uint32_t* d_rawlen, const uint32_t* d_fl, const uint32_t* d_slen,
-                          const int32_t* d_sst, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail, hipStream_t stream);
+                          const uint32_t* d_csz, const uint32_t* d_scap, const uint32_t* d_rawlen, const uint32_t* d_fl, const uint32_t* d_cm,
+                          const uint32_t* d_slen, const int32_t* d_sst, uint32_t* d_out_len, int32_t* d_status, int32_t* d_detail,
+                          hipStream_t stream);
 // writing OpenEXR images (exr_write_kernels.h, compiled into pack.hip; the payload copies are zmi_launch_zip_pack, the fold per chunk
 // zmi_launch_combine_segments_adler): a slice of the host's bytes into the scratch; per chunk of the call its raw size, pieces, room in
 // the scratch and work items (and the words the later kernels start from); the piece table over the scans of those; the forward zip
@@ -433,7 +444,10 @@ int zmi_launch_exr_finish(const zmi_exr_image* d_images, const uint32_t* d_sel, 
 uint32_t zmi_exr_zip_trip(void);
 int zmi_launch_exr_wslice(zmi_xw_slice slice, uint8_t* d_blob, hipStream_t stream);
 int zmi_launch_exr_wchunks(zmi_xw_plan plan, const zmi_exr_channel* d_chs, uint32_t* d_csz, uint32_t* d_npc, uint32_t* d_ssz, uint32_t* d_items,
-                           uint32_t* d_cds, uint32_t* d_neff, uint32_t* d_bad, uint64_t* d_run, hipStream_t stream);
+                           uint32_t* d_cds, uint32_t* d_neff, uint32_t* d_bad, uint64_t* d_run, uint32_t* d_cm, uint32_t* d_fitems,
+                           hipStream_t stream);
+int zmi_launch_exr_pxr24_forward(zmi_xw_plan plan, const zmi_exr_channel* d_chs, const uint8_t* d_in, const uint64_t* d_in_off,
+                                 const uint64_t* d_fitem_off, uint64_t bound, const uint64_t* d_soff, uint8_t* d_scan, hipStream_t stream);
 int zmi_launch_exr_wpieces(zmi_xw_plan plan, const uint64_t* d_cfirst, const uint64_t* d_soff, const uint32_t* d_csz, uint32_t group_chunks,
                            uint32_t wpg, uint32_t np, uint64_t* d_poff, uint32_t* d_plen, uint32_t* d_ends, hipStream_t stream);
 int zmi_launch_exr_zip(zmi_xw_plan plan, const zmi_exr_channel* d_chs, const uint8_t* d_in, const uint64_t* d_in_off, const uint64_t* d_item_off,

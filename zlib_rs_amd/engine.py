@@ -1630,7 +1630,7 @@ class Engine:
 
     # ---- writing OpenEXR images (include/zmi355.h) ----
     _EXR_TYPES = {torch.int32: 0, torch.float16: 1, torch.float32: 2}
-    _EXR_COMPRESSION = {"none": 0, "zips": 2, "zip": 3}
+    _EXR_COMPRESSION = {"none": 0, "zips": 2, "zip": 3, "pxr24": 5}
 
     def _exr_desc(self, shape, channels, compression, tile, origin, display_window, level, strategy, piece_bytes, align):
         """the zmi_exr_write of images of `shape` = (H, W) and channels [(name, torch dtype)] sorted by name -> (the struct, what keeps
@@ -1638,7 +1638,7 @@ class Engine:
         import ctypes
         h, w = (int(v) for v in shape)
         if compression not in self._EXR_COMPRESSION:
-            raise ValueError("exr_write: compression must be 'zip', 'zips' or 'none'")
+            raise ValueError("exr_write: compression must be 'zip', 'zips', 'pxr24' or 'none'")
         for _, dt in channels:
             if dt not in self._EXR_TYPES:
                 raise ValueError("exr_write: dtype %s is not one an OpenEXR channel has (float16, float32, int32)" % (dt,))
@@ -1668,8 +1668,8 @@ class Engine:
         not it fitted (Z_BUF_ERROR with length 0 where out is too small).  images: a [N, C, H, W] or [C, H, W] device tensor of
         float16, float32 or int32 (UINT bits) with `channels` = the C names; or a dict, or a list of dicts, name -> [H, W] tensor, of
         mixed dtypes.  The names are sorted here, as the file wants them, and the planes laid out as exr_read returns them; every
-        image must have the layout of the first.  compression "zip" (16 scanlines a chunk), "zips" (one) or "none"; tile: None for
-        scanlines, an int or (tile_w, tile_h); origin: (xMin, yMin) of the data window; display_window None: (0, 0, W - 1, H - 1).
+        image must have the layout of the first.  compression "zip" (16 scanlines a chunk), "zips" (one), "pxr24" (16; float32 channels
+        keep 24 bits in the chunks that shrink, every other value is exact) or "none"; tile: None for scanlines, an int or (tile_w, tile_h); origin: (xMin, yMin) of the data window; display_window None: (0, 0, W - 1, H - 1).
         last_exr_written keeps the records exr_headers would list for the files, last_exr_chunk_len every chunk's dataSize (== the
         chunk's raw size where it was stored raw).  No synchronisation."""
         import ctypes
@@ -1723,7 +1723,7 @@ class Engine:
         bound = int(self.L.zmi_exr_bound(ctypes.byref(d), n))
         if bound == 0:
             raise ValueError("exr_write: these arguments describe no image zmi_exr_write_dev writes")
-        tw, th = (d.tile_w, d.tile_h) if d.tile_w else (w, 16 if d.compression == 3 else 1)
+        tw, th = (d.tile_w, d.tile_h) if d.tile_w else (w, 16 if d.compression in (3, 5) else 1)
         nc = -(-w // tw) * -(-h // th)
         if out is None:
             out = torch.empty(bound, dtype=torch.uint8, device=self.device)
